@@ -12,6 +12,7 @@ points; Q = 572 k / 499 k / 307 k queries at 256^3, eps 3) taken round-robin as 
 weights offline).
 
   python bench.py --gpus N --steps K --warmup W [--model p2s_max|p2s_vanilla] [--bf16 M] [--rng-mode dataset|per_shape]
+                  [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 ``--model p2s_vanilla --bf16 4`` is BASELINE configs[3] (p2s_vanilla with QSTN, reduced-precision encoder + fp32 decoder)
@@ -100,6 +101,9 @@ def parse():
     ap.add_argument('--no-secondary', action='store_true', help='skip the secondary passes')
     ap.add_argument('--secondary-reps', type=int, default=3, help='timed shapes per secondary entry (median reported)')
     ap.add_argument('--backend', default=None, help='torch.distributed backend (default nccl = RCCL)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the SDF arrays of the last timed step (one per shape of that step, '
+                         'float32) as DIR/sdf_<k>.npy; at most 64 MB in all (larger: a fixed seeded sample + its indices)')
     # test hook (tests/test_gpu_bench_rehearsal.py): RANK:K -- that rank raises when it reaches its K-th own shape (0-based)
     ap.add_argument('--fault', default=None, help=argparse.SUPPRESS)
     return ap.parse_args()
@@ -210,11 +214,13 @@ def cpu_baseline(w, cfg, model_name, cloud_name, cloud, queries, target_seconds,
 def respawn(args):
     """``python bench.py --gpus N`` without a torchrun environment: N ranks on this node, or a loud error"""
     import socket
-    import torch
-    have = torch.cuda.device_count() if torch.cuda.is_available() else 0
-    if have < args.gpus and (args.backend or 'nccl') == 'nccl' and not os.environ.get('P2S_BENCH_SHARE_GPU'):
-        raise SystemExit('bench.py --gpus %d: %d ranks requested but %d device(s) visible -- refusing to report a '
-                         '%d-GPU number from fewer GPUs' % (args.gpus, args.gpus, have, args.gpus))
+    if (args.backend or 'nccl') == 'nccl' and not os.environ.get('P2S_BENCH_SHARE_GPU'):
+        # only where the check applies: a launcher that initialised HIP would hold the GPU open beside its N ranks
+        import torch
+        have = torch.cuda.device_count() if torch.cuda.is_available() else 0
+        if have < args.gpus:
+            raise SystemExit('bench.py --gpus %d: %d ranks requested but %d device(s) visible -- refusing to report a '
+                             '%d-GPU number from fewer GPUs' % (args.gpus, args.gpus, have, args.gpus))
     with socket.socket() as s:
         s.bind(('127.0.0.1', 0))
         port = s.getsockname()[1]
@@ -228,6 +234,31 @@ def reseed(rng, seed=SEED_DATA):
     """``RandomState(seed)`` on an existing device generator (init_genrand): the handle, its stream buffers and the
     weighted sub-sample's tables stay allocated -- a timed pass never allocates"""
     rng.set_state(np.random.RandomState(int(seed) & 0xffffffff).get_state()[1], 624)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """``--dump-outputs``: the host SDF arrays of the last timed step (one per shape, in dataset order) as
+    ``outdir/sdf_<k>.npy``.  Above DUMP_BYTES in all, every array is cut to the same fraction by a fixed seeded sample of
+    sorted indices, written beside it as ``sdf_<k>_index.npy`` (float64): the same sample for the same arguments.
+    -> {file name: shape}"""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = [a if a.dtype in (np.float32, np.float64) else a.astype(np.float64) for a in map(np.asarray, arrays)]
+    total = sum(a.nbytes for a in arrays)
+    keep = 1.0 if total <= DUMP_BYTES else DUMP_BYTES / (3.0 * total)      # value + float64 index per kept entry
+    written = {}
+    for k, a in enumerate(arrays):
+        name = 'sdf_%d' % k
+        if keep < 1.0:
+            idx = np.sort(np.random.RandomState(SEED_DATA + k).choice(a.shape[0], int(a.shape[0] * keep), replace=False))
+            np.save(os.path.join(outdir, name + '_index.npy'), idx.astype(np.float64))
+            written[name + '_index.npy'] = list(idx.shape)
+            a = a[idx]
+        np.save(os.path.join(outdir, name + '.npy'), a)
+        written[name + '.npy'] = list(a.shape)
+    return written
 
 
 def complete_shape(engine, model, pts_host, rng, res, chunk, ev=None):
@@ -482,6 +513,8 @@ def handoff_efficiency(t_i, t_s, n):
 
 def main():
     args = parse()
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit('bench.py --dump-outputs needs at least one timed step (--steps >= 1)')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         respawn(args)
     import torch
@@ -658,6 +691,19 @@ def main():
         if sharding.is_initialized() and gathered != total_queries:        # P2S_DIST_FORCE: the group at world size 1
             raise SystemExit('gather returned %d SDF values, the rank produced %d' % (gathered, total_queries))
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step = the last round of ``world`` shapes; other ranks' SDF from the gather (same offsets as the
+        # stream replay of the self-check below)
+        last = []
+        for g in range((n_rounds - 1) * world, n_rounds * world):
+            if parts is None:
+                last.append(mine_timed[-1][0].numpy())
+            else:
+                before = sum(q_of_cloud[cloud_of[k]] for k in range(args.warmup * world, g) if owner[k] == owner[g])
+                last.append(parts[owner[g]][before:before + q_of_cloud[cloud_of[g]]].cpu().numpy())
+        dumped = dump_outputs(args.dump_outputs, last)
+
     if rank == 0:
         value = total_queries / dt
         launches = max(acc.get('launches_chain', 0), 1)
@@ -720,6 +766,8 @@ def main():
                          'device_clock_rank0': device_clock},
             'stage_ms_rank0': stage,
         }
+        if dumped is not None:
+            out['outputs_dumped'] = {'dir': args.dump_outputs, 'files': dumped}
 
         def bail(what, check):
             out['self_check'] = check

@@ -5,6 +5,8 @@ import sys
 import pytest
 import torch
 
+from oracle import ref_shims
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DROPIN = os.path.join(REPO, 'points2surf_amd', 'dropin')
 
@@ -65,12 +67,22 @@ def test_parse_arguments_defaults_and_quirks(dropin_source):
     assert o.dataset == ['a/testset.txt', 'b/testset.txt'] and o.query_grid_resolution == 256 and o.sigma == 5
 
 
-@pytest.mark.skipif(not os.path.isfile('/root/reference/source/points_to_surf_eval.py'), reason='reference not present')
+PARSE_ARGS = ['--query_grid_resolution', '128', '--epsilon', '3', '--models', 'p2s_max', '--dataset', 'x.txt']
+
+
 def test_parse_arguments_identical_to_reference(dropin_source):
+    """against the reference's parse_arguments where the reference checkout is present, and always against what it
+    returned for the same command lines (tests/golden/ref_dropin_outputs.json, oracle/make_golden_dropin.py)"""
+    import json
     ev, _ = dropin_source
     from oracle import ref_shims
-    args = ['--query_grid_resolution', '128', '--epsilon', '3', '--models', 'p2s_max', '--dataset', 'x.txt']
+    args = PARSE_ARGS
     mine_default, mine = vars(ev.parse_arguments([])), vars(ev.parse_arguments(args))
+    with open(os.path.join(REPO, 'tests', 'golden', 'ref_dropin_outputs.json')) as f:
+        golden = json.load(f)['parse_arguments']
+    assert json.loads(json.dumps(mine_default)) == golden['defaults'] and json.loads(json.dumps(mine)) == golden['args']
+    if not ref_shims.reference_available():
+        return
     for k in [k for k in sys.modules if k == 'source' or k.startswith('source.')]:
         del sys.modules[k]
     sys.path.remove(DROPIN)
@@ -98,7 +110,7 @@ def test_errors_mirror_reference(dropin_source):
            'imp_surf_query_point_ms': torch.zeros(1, 3)})
 
 
-@pytest.mark.skipif(not os.path.isfile('/root/reference/source/sdf.py'), reason='reference not present')
+@pytest.mark.skipif(not os.path.isfile(os.path.join(ref_shims.REFERENCE_ROOT, 'source', 'sdf.py')), reason='reference not present')
 def test_sdf_bridge_reexports_reference_and_overrides_two_functions():
     """drop-in source.sdf: reference module re-exported, only the volume functions swapped (no GPU call here)"""
     import numpy as np

@@ -1,6 +1,7 @@
 """CPU: the report side of the drop-in's consumer stage -- PLY reader / writer, ``eval_predictions`` and the pairing
-rules + CSV of ``mesh_comparison`` -- against the reference's own functions where the reference checkout is present
-(its trimesh-dependent distance workers are replaced by the same deterministic stand-ins on both sides)."""
+rules + CSV of ``mesh_comparison`` -- against the reference's own functions where the reference checkout is present, and always against the reports
+those functions wrote for the same inputs (tests/golden/ref_dropin_outputs.json); the reference's trimesh-dependent
+distance workers are replaced by the same deterministic stand-ins on both sides."""
 import os
 import sys
 
@@ -42,30 +43,45 @@ def test_ply_round_trip_and_reference_meshes(tmp_path):
     assert va.shape == (3, 3) and fa.tolist() == [[0, 1, 2]]
 
 
+GOLDEN_REPORTS = os.path.join(REPO, 'tests', 'golden', 'ref_dropin_outputs.json')
+
+
+def reference_reports():
+    """what the reference's own functions wrote for the inputs below (oracle/make_golden_dropin.py)"""
+    import json
+    with open(GOLDEN_REPORTS) as f:
+        return json.load(f)
+
+
 @pytest.fixture()
 def both_evaluation_modules():
-    if not os.path.isfile(os.path.join(REFERENCE, 'source', 'base', 'evaluation.py')):
-        pytest.skip('reference checkout not present')
+    """the drop-in's ``source.base.evaluation`` and the reference's (None where no reference checkout is present: the
+    tests then compare with the reference's reports stored under tests/golden)"""
+    have_ref = os.path.isfile(os.path.join(REFERENCE, 'source', 'base', 'evaluation.py'))
     saved = {k: v for k, v in sys.modules.items() if k == 'source' or k.startswith('source.')}
     for k in saved:
         del sys.modules[k]
-    sys.path.insert(0, REFERENCE)
+    if have_ref:
+        sys.path.insert(0, REFERENCE)
     sys.path.insert(0, DROPIN)
     try:
         import source.base.evaluation as ours
-        ref = sys.modules.get('source.base._reference_evaluation') or ours._ref
-        assert ours.__file__.startswith(DROPIN) and ref is not None and ref.__file__.startswith(REFERENCE)
+        assert ours.__file__.startswith(DROPIN)
+        ref = None
+        if have_ref:
+            ref = sys.modules.get('source.base._reference_evaluation') or ours._ref
+            assert ref is not None and ref.__file__.startswith(REFERENCE)
         yield ours, ref
     finally:
         sys.path.remove(DROPIN)
-        sys.path.remove(REFERENCE)
+        if have_ref:
+            sys.path.remove(REFERENCE)
         for k in [k for k in sys.modules if k == 'source' or k.startswith('source.')]:
             del sys.modules[k]
         sys.modules.update(saved)
 
 
-def test_eval_predictions_writes_the_reference_report(both_evaluation_modules, tmp_path):
-    ours, ref = both_evaluation_modules
+def eval_predictions_inputs(tmp_path):
     rs = np.random.RandomState(1)
     pred, gt = str(tmp_path / 'pred'), str(tmp_path / 'gt')
     os.makedirs(pred)
@@ -73,16 +89,27 @@ def test_eval_predictions_writes_the_reference_report(both_evaluation_modules, t
     for name in ('00011084_fddd53ce45f640f3ab922328_trimesh_019', 'zz_shape', 'a_b_c_d_e_f'):
         np.save(os.path.join(pred, name + '.xyz.npy'), rs.normal(0, 0.1, 500).astype(np.float32))
         np.save(os.path.join(gt, name + '.ply.npy'), rs.normal(0, 0.1, 500).astype(np.float32))
-    for unsigned in (False, True):
-        a, b = str(tmp_path / ('ours_%d.csv' % unsigned)), str(tmp_path / ('ref_%d.csv' % unsigned))
-        ours.eval_predictions(pred, gt, a, unsigned=unsigned)
-        ref.eval_predictions(pred, gt, b, unsigned=unsigned)
-        assert open(a).read() == open(b).read()
+    return pred, gt
 
 
-def test_mesh_comparison_pairing_and_csv_equal_the_reference(both_evaluation_modules, tmp_path, monkeypatch):
+def eval_predictions_report(mod, pred, gt, path, unsigned):
+    mod.eval_predictions(pred, gt, path, unsigned=unsigned)
+    with open(path) as f:
+        return f.read()
+
+
+def test_eval_predictions_writes_the_reference_report(both_evaluation_modules, tmp_path):
     ours, ref = both_evaluation_modules
-    from points2surf_amd import metrics
+    pred, gt = eval_predictions_inputs(tmp_path)
+    golden = reference_reports()['eval_predictions']
+    for unsigned in (False, True):
+        a = eval_predictions_report(ours, pred, gt, str(tmp_path / ('ours_%d.csv' % unsigned)), unsigned)
+        assert a == golden['unsigned' if unsigned else 'signed']
+        if ref is not None:
+            assert a == eval_predictions_report(ref, pred, gt, str(tmp_path / ('ref_%d.csv' % unsigned)), unsigned)
+
+
+def mesh_comparison_inputs(tmp_path):
     new_dir, ref_dir = str(tmp_path / 'new'), str(tmp_path / 'ref')
     os.makedirs(new_dir)
     os.makedirs(ref_dir)
@@ -92,23 +119,45 @@ def test_mesh_comparison_pairing_and_csv_equal_the_reference(both_evaluation_mod
         open(os.path.join(ref_dir, n + '.ply'), 'w').write('x')
     ds = str(tmp_path / 'testset.txt')
     open(ds, 'w').write('shapeA\nshapeB\nmissing\n')
+    return new_dir, ref_dir, ds
 
-    def fake(file_in, file_ref):
-        k = float(len(os.path.basename(file_in)))
-        return 0.5 * k, 0.25 * k, 0.5 * k, 3.0 * k
-    monkeypatch.setattr(metrics, 'mesh_distances', lambda a, b, samples_per_model=10000, seed=0, device=None: fake(a, b))
-    monkeypatch.setattr(ref, '_hausdorff_distance_single_file', lambda a, b, n: (a, b) + fake(a, b)[:3])
-    monkeypatch.setattr(ref, '_chamfer_distance_single_file', lambda a, b, n: (a, b, fake(a, b)[3]))
-    a, b = str(tmp_path / 'ours.csv'), str(tmp_path / 'ref.csv')
-    ours.mesh_comparison(new_dir, ref_dir, 1, a, samples_per_model=100, dataset_file_abs=ds)
-    ref.mesh_comparison(new_meshes_dir_abs=new_dir, ref_meshes_dir_abs=ref_dir, num_processes=1, report_name=b,
+
+def fake_mesh_distances(file_in, file_ref):
+    """deterministic stand-in for the distance workers of both sides (the pairing and the CSV are under test)"""
+    k = float(len(os.path.basename(file_in)))
+    return 0.5 * k, 0.25 * k, 0.5 * k, 3.0 * k
+
+
+def patch_reference_mesh_distances(ref, monkeypatch):
+    monkeypatch.setattr(ref, '_hausdorff_distance_single_file', lambda a, b, n: (a, b) + fake_mesh_distances(a, b)[:3])
+    monkeypatch.setattr(ref, '_chamfer_distance_single_file', lambda a, b, n: (a, b, fake_mesh_distances(a, b)[3]))
+
+
+def reference_mesh_comparison_report(ref, new_dir, ref_dir, ds, path):
+    ref.mesh_comparison(new_meshes_dir_abs=new_dir, ref_meshes_dir_abs=ref_dir, num_processes=1, report_name=path,
                         samples_per_model=100, dataset_file_abs=ds)
-    assert open(a).read() == open(b).read()
+    with open(path) as f:
+        return f.read()
+
+
+def test_mesh_comparison_pairing_and_csv_equal_the_reference(both_evaluation_modules, tmp_path, monkeypatch):
+    ours, ref = both_evaluation_modules
+    from points2surf_amd import metrics
+    new_dir, ref_dir, ds = mesh_comparison_inputs(tmp_path)
+    monkeypatch.setattr(metrics, 'mesh_distances',
+                        lambda a, b, samples_per_model=10000, seed=0, device=None: fake_mesh_distances(a, b))
+    a = str(tmp_path / 'ours.csv')
+    ours.mesh_comparison(new_dir, ref_dir, 1, a, samples_per_model=100, dataset_file_abs=ds)
+    assert open(a).read().replace(str(tmp_path), '<tmp>') == reference_reports()['mesh_comparison']
+    if ref is not None:
+        patch_reference_mesh_distances(ref, monkeypatch)
+        assert open(a).read() == reference_mesh_comparison_report(ref, new_dir, ref_dir, ds, str(tmp_path / 'ref.csv'))
     assert open(a).read().count('\n') == 3 and ',-1,-1,-1,-1' in open(a).read()      # header + A + B + the missing one
     # without a dataset file the reference compares stems with full file names, finds nothing and raises: mirrored
-    for mod, kw in ((ours, {}), (ref, {})):
-        with pytest.raises(ValueError):
-            mod.mesh_comparison(new_dir, ref_dir, 1, a, samples_per_model=100, dataset_file_abs=None)
+    for mod in (ours, ref):
+        if mod is not None:
+            with pytest.raises(ValueError):
+                mod.mesh_comparison(new_dir, ref_dir, 1, a, samples_per_model=100, dataset_file_abs=None)
     with pytest.raises(ValueError):
         ours.mesh_comparison(new_dir, ref_dir, 1, a, dataset_file_abs=str(tmp_path / 'nope.txt'))
 
