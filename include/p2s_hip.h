@@ -302,6 +302,47 @@ int p2s_random_rotations(p2s_rng_t r, int64_t n, double *rot_out_dev, void *stre
  *   [n_items][points_per_item][3] (may alias), rot_dev [n_items][9] float64 */
 int p2s_rotate_points(const double *rot_dev, const float *pts_in_dev, int points_per_item, int64_t n_items,
                       float *pts_out_dev, void *stream);
+/* ------------------------------------------------------------------------------------------
+ * Workers mode: the reference's sub-sample streams under ``--workers W --batchSize B`` (W >= 1, B >= 1).
+ * torch's DataLoader hands batch b (dataset positions [b B, (b+1) B), across shapes) to worker b mod W, and every
+ * worker holds its own copies of both RandomState(seed) generators (reference source/data_loader.py:270-277): the query
+ * at dataset position g draws from worker stream (g // B) mod W, and every stream consumes its queries in increasing g.
+ *   sub[W]    the workers' twins of the sub-sample generator (rng_global_sample)
+ *   first[W]  the workers' twins of the first generator (self.rng): the patch choice of fixed-radius models and the
+ *             rotation of the GT-query pass; NULL when the call needs neither
+ *   first_position  dataset position of the call's first query (the caller's cursor over the whole sequence)
+ * All 2 W handles must be distinct.  A call neither moves nor keeps first_position: the caller advances it.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t n_streams;             /* W */
+    int32_t batch;                 /* B */
+    int64_t first_position;
+    const p2s_rng_t *sub;
+    const p2s_rng_t *first;
+} p2s_worker_streams;
+/* the stream-major permutation of the n queries at positions first_position .. + n - 1: stream 0's queries in increasing
+ * position, then stream 1's, ...  q_in_dev / q_out_dev [n][3] (both NULL: no gather; must not alias); src_out_dev [n]
+ * int64: the local index each slot came from (may be NULL); counts_host [n_streams] queries per stream (may be NULL). */
+int p2s_stream_order(int64_t first_position, int64_t n, int n_streams, int batch, const float *q_in_dev, float *q_out_dev,
+                     int64_t *src_out_dev, int64_t *counts_host, void *stream);
+/* p2s_infer_shape_ball in workers mode: the whole query grid of the shape (q_begin = 0, q_end = -1 or the grid size; a
+ * part of it is refused), positions ws->first_position onwards.  sdf_out_dev and q_out_dev in grid order; the logits
+ * capture (p2s_model_capture_logits) applies.  Refused with P2S_EINVAL before any generator moves: W > 1 with a cloud of
+ * fewer points than the sub-sample (every worker shuffles its own cached copy of shape.pts), a partial range, bad
+ * handles.  Synchronises `stream`. */
+int p2s_infer_shape_workers(p2s_model_t m, p2s_cloud_t c, const p2s_worker_streams *ws, int grid_resolution, int epsilon,
+                            int64_t q_begin, int64_t q_end, int chunk, float *sdf_out_dev, float *q_out_dev, int64_t *n_done,
+                            void *stream);
+/* p2s_infer_queries in workers mode: rotate != 0 = the GT-query pass (rotations from ws->first).  sdf_out_dev in query
+ * order.  Synchronises `stream`. */
+int p2s_infer_queries_workers(p2s_model_t m, p2s_cloud_t c, const p2s_worker_streams *ws, int rotate, const float *q_dev,
+                              int64_t n_queries, int chunk, float *sdf_out_dev, void *stream);
+/* the global sub-sample of n_queries queries in workers mode, in query order: ids_out_dev [n_queries][n] (NULL: only
+ * advance the streams), pts_out_dev [n_queries][n][3] (may be NULL).  weighted = 0: uniform (q_dev may be NULL);
+ * 1: the distance-weighted choice at q_dev [n_queries][3].  A cloud with fewer points than n is refused (P2S_EINVAL, no
+ * generator moved).  Synchronises `stream`. */
+int p2s_subsample_workers(p2s_cloud_t c, const p2s_worker_streams *ws, const float *q_dev, int64_t n_queries, int n, int weighted,
+                          int32_t *ids_out_dev, float *pts_out_dev, void *stream);
 /* One-shot capture of the decoder's raw logits: the NEXT p2s_infer_shape / p2s_infer_shape_ball / p2s_infer_queries call on
  * this model also writes logits_out_dev [processed queries][output_dim] (column output_dim - 1 = the sign logit, or the one
  * signed-distance logit of the regression model) -- what post_process (reference source/points_to_surf_eval.py:174-196)

@@ -85,10 +85,21 @@ PROTOTYPES = {
     'p2s_set_profiling': (c_int, [c_void_p, c_int]),
     'p2s_get_counters': (c_int, [c_void_p, ctypes.POINTER(Counters)]),
     'p2s_model_capture_logits': (c_int, [c_void_p, c_void_p, c_int64]),
+    'p2s_stream_order': (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'p2s_infer_shape_workers': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_void_p,
+                                        c_void_p, ctypes.POINTER(c_int64), c_void_p]),
+    'p2s_infer_queries_workers': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    'p2s_subsample_workers': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'p2s_write_txt_f32': (c_int, [ctypes.c_char_p, c_void_p, c_int64]),
     'p2s_write_query_vis_ply': (c_int, [ctypes.c_char_p, c_void_p, c_void_p, c_int64]),
     'p2s_write_coff_samples': (c_int, [ctypes.c_char_p, c_void_p, c_void_p, c_int64]),
 }
+
+
+class WorkerStreams(ctypes.Structure):
+    """mirror of ``p2s_worker_streams``"""
+    _fields_ = [('n_streams', ctypes.c_int32), ('batch', ctypes.c_int32), ('first_position', ctypes.c_int64),
+                ('sub', ctypes.POINTER(c_void_p)), ('first', ctypes.POINTER(c_void_p))]
 
 
 class P2SError(RuntimeError):

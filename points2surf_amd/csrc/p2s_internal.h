@@ -65,9 +65,32 @@ struct p2s_model_s {
                                    // stream so that it runs beside the sub-sample kernels of the auxiliary stream, not behind them
     bool overlap = true;
     PipeBuffers pipe;
-    int fault_chunk = -1;          // test hook (p2s_debug_fault_chunk): fail with P2S_EHIP before this chunk
+    int fault_chunk = -1;
+    // workers mode (p2s_streams.hip): the stream-ordered queries, their source indices and the SDF / logits produced in that
+    // order, before the scatter to the caller's buffers; grown on demand
+    struct Workers {
+        float *q = nullptr, *sdf = nullptr, *logits = nullptr;
+        int64_t *src = nullptr;
+        int64_t cap = 0;
+    } wk;          // test hook (p2s_debug_fault_chunk): fail with P2S_EHIP before this chunk
 };
 void p2s_pipe_free(p2s_model_s *m);
+
+// workers mode (p2s_streams.hip): one segment of stream-ordered queries and the generators it draws from
+struct P2sSegment {
+    p2s_rng_s *sub;
+    p2s_rng_s *first;
+    int64_t rows;
+};
+void p2s_workers_free(p2s_model_s *m);
+int p2s_workers_reserve(p2s_model_s *m, int64_t n);
+// validation of a p2s_worker_streams (need_first: the call draws from the first generators); counts: the per-stream query
+// counts of n queries at ws->first_position; segs: the non-empty streams as pipeline segments
+int p2s_workers_check(const p2s_worker_streams *ws, bool need_first, const char *who);
+int p2s_workers_segments(const p2s_worker_streams *ws, int64_t n, std::vector<P2sSegment> &segs);
+int p2s_launch_stream_order(int64_t g0, int64_t n, int W, int B, const float *q_in, float *q_out, int64_t *src, hipStream_t s);
+int p2s_launch_unpermute(const int64_t *src, int64_t n, const float *sdf_in, float *sdf_out, const float *logits_in,
+                         float *logits_out, int dim, hipStream_t s);
 // cfg.encoder_bf16: 0 fp32, 1 bf16, 2 / 3 split bf16, 4 fp16 pair (2 pieces, two accumulators)
 inline int p2s_enc_pieces(const p2s_model_cfg &c) { return c.encoder_bf16 == 4 ? 2 : c.encoder_bf16; }
 inline int p2s_enc_f16(const p2s_model_cfg &c) { return c.encoder_bf16 == 4 ? 1 : 0; }

@@ -223,8 +223,12 @@ struct LogitsCapture {
     }
 };
 
+// segs != NULL (workers mode, p2s_worker_segments): the queries are in stream-major order and consecutive segments of
+// segs[i].rows queries draw from their own generators -- segs[i].sub for the sub-sample, segs[i].first for the patch choice
+// and the rotation; r / r_rot / r_patch then only say which of them the call uses (and r_patch hosts the ball counts).
 static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s *r_rot, p2s_rng_s *r_patch, const float *q_all,
-                        int64_t q_begin, int64_t q_end, int chunk, float *sdf_out_dev, hipStream_t s, const LogitsCapture &cap) {
+                        int64_t q_begin, int64_t q_end, int chunk, float *sdf_out_dev, hipStream_t s, const LogitsCapture &cap,
+                        const P2sSegment *segs = nullptr, int nseg = 0) {
     const bool weighted = m->cfg.weighted_subsample != 0;   // p2s_vanilla: choice(p, replace=False) per query
     const double ball_r = m->cfg.patch_radius;
     const bool ball = ball_r > 0.0;                         // patch = points within a fixed radius (p2s_ball.hip)
@@ -336,20 +340,37 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
     const bool use_done = ball && sbl != s;
 
     const int64_t nchunks = (nq + C - 1) / C;
+    // the pieces of local rows [lo, lo + len) that fall into one segment each: fn(sub generator, first generator, row offset
+    // in the chunk, first local row, rows).  Without segments: one piece on the call's generators.
+    auto pieces = [&](int64_t lo, int64_t len, auto &&fn) -> int {
+        if (!segs) return fn(r, r_rot ? r_rot : r_patch, 0, lo, len);
+        int64_t at = 0;
+        for (int i = 0; i < nseg; ++i) {
+            const int64_t a = std::max(lo, at), e = std::min(lo + len, at + segs[i].rows);
+            if (a < e) {
+                const int rc2 = fn(segs[i].sub, segs[i].first, a - lo, a, e - a);
+                if (rc2) return rc2;
+            }
+            at += segs[i].rows;
+        }
+        return P2S_OK;
+    };
     auto produce = [&](int64_t ci) -> int {       // sub-sample ids of chunk ci on the aux stream
         const int bi = (int)(ci % nbuf);
         const int64_t q0 = q_begin + ci * C;
         const int cur = (int)std::min<int64_t>(C, q_end - q0);
         if (ci >= nbuf && sa != s) PIPE_HIP(hipStreamWaitEvent(sa, b.freed[bi], 0));
         const int e0 = p2s_prof_mark(m, sa);
-        int rc2;
-        if (small)
-            rc2 = p2s_subsample_shuffle_pad(r, c, cur, n, b.perm[bi], b.sub_ids[bi], sa);
-        else if (m->cfg.fixed_subsample)      // rng.seed(42) before every draw (reference source/base/utils.py:210-211)
-            rc2 = p2s_subsample_fixed(r, c, weighted ? q_all + (size_t)q0 * 3 : nullptr, cur, n, 42u, b.sub_ids[bi], nullptr, sa);
-        else
-            rc2 = weighted ? p2s_subsample_weighted(r, c, q_all + (size_t)q0 * 3, cur, n, b.sub_ids[bi], nullptr, sa)
-                           : p2s_subsample_uniform(r, c, cur, n, b.sub_ids[bi], nullptr, sa);
+        int rc2 = pieces(q0 - q_begin, cur, [&](p2s_rng_s *rs, p2s_rng_s *, int64_t off, int64_t row, int64_t cnt) -> int {
+            const float *qp = q_all + (size_t)(q_begin + row) * 3;
+            int32_t *ids = b.sub_ids[bi] + (size_t)off * n;
+            if (small)
+                return p2s_subsample_shuffle_pad(rs, c, cnt, n, b.perm[bi] + (size_t)off * n, ids, sa);
+            if (m->cfg.fixed_subsample)       // rng.seed(42) before every draw (reference source/base/utils.py:210-211)
+                return p2s_subsample_fixed(rs, c, weighted ? qp : nullptr, cnt, n, 42u, ids, nullptr, sa);
+            return weighted ? p2s_subsample_weighted(rs, c, qp, cnt, n, ids, nullptr, sa)
+                            : p2s_subsample_uniform(rs, c, cnt, n, ids, nullptr, sa);
+        });
         if (rc2) return fail(rc2);
         p2s_prof_span(m, ST_SUB, e0, p2s_prof_mark(m, sa));
         if (sa != s) PIPE_HIP(hipEventRecord(b.ready[bi], sa));
@@ -358,8 +379,11 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
             // the encoders of the chunks before; the encoders of chunk ci - nbuf read the patch buffer it fills
             if (ci >= nbuf && sbl != s) PIPE_HIP(hipStreamWaitEvent(sbl, b.done[bi], 0));
             const int eb0 = p2s_prof_mark(m, sbl);
-            rc2 = p2s_ball_patch_counted(r_patch, c, q_all + (size_t)q0 * 3, ball_cd + (q0 - q_begin), ball_ch + (q0 - q_begin), cur,
-                                         ball_r, k, r_rot ? 6 : 0, nullptr, b.patch[bi], b.radius[bi], r_rot ? b.rot[bi] : nullptr, sbl);
+            rc2 = pieces(q0 - q_begin, cur, [&](p2s_rng_s *, p2s_rng_s *rf, int64_t off, int64_t row, int64_t cnt) -> int {
+                return p2s_ball_patch_counted(rf, c, q_all + (size_t)(q_begin + row) * 3, ball_cd + row, ball_ch + row, cnt, ball_r, k,
+                                              r_rot ? 6 : 0, nullptr, b.patch[bi] + (size_t)off * k * 3, b.radius[bi] + off,
+                                              r_rot ? b.rot[bi] + (size_t)off * 9 : nullptr, sbl);
+            });
             if (rc2) return fail(rc2);
             p2s_prof_span(m, ST_KNN, eb0, p2s_prof_mark(m, sbl));
             if (sbl != s) PIPE_HIP(hipEventRecord(b.ball_ready[bi], sbl));
@@ -410,7 +434,10 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
         if ((rc = prepare(ci))) return rc;
         if (r_rot) {
             // data_loader.py:381-393: rotate sub-sample (model space), patch (patch space) and the query point
-            if (!ball && (rc = p2s_random_rotations(r_rot, cur, b.rot[bi], s))) return fail(rc);
+            if (!ball && (rc = pieces(q0 - q_begin, cur, [&](p2s_rng_s *, p2s_rng_s *rf, int64_t off, int64_t, int64_t cnt) -> int {
+                    return p2s_random_rotations(rf, cnt, b.rot[bi] + (size_t)off * 9, s);
+                })))
+                return fail(rc);
             if ((rc = p2s_rotate_points(b.rot[bi], b.sub[bi], n, cur, b.sub[bi], s))) return fail(rc);
             if ((rc = p2s_rotate_points(b.rot[bi], b.patch[bi], k, cur, b.patch[bi], s))) return fail(rc);
             if ((rc = p2s_rotate_points(b.rot[bi], qc, 1, cur, b.qrot[bi], s))) return fail(rc);
@@ -500,5 +527,100 @@ extern "C" int p2s_infer_queries(p2s_model_t m, p2s_cloud_t c, p2s_rng_t r_sub, 
     p2s_prof_collect(m);
     if ((rc = p2s_rng_check(r_sub, s))) return rc;
     if (r_rot && (rc = p2s_rng_check(r_rot, s))) return rc;
+    return P2S_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Workers mode (p2s_streams.hip): the queries in stream-major order through the pipeline, one segment per non-empty
+// stream; SDF / logits (the fp16 fallback's rows included) land in the model's stream-ordered buffers, then one scatter.
+// ---------------------------------------------------------------------------------------------------------
+static int run_workers(p2s_model_s *m, p2s_cloud_s *c, const p2s_worker_streams *ws, bool rotate, const float *q, int64_t nq,
+                       int chunk, float *sdf_out_dev, hipStream_t s, const LogitsCapture &cap) {
+    if (cap.dev && cap.room < nq) {
+        p2s_set_error("p2s pipeline: logits capture buffer holds %lld queries, the call processes %lld", (long long)cap.room, (long long)nq);
+        return P2S_ECAPACITY;
+    }
+    std::vector<P2sSegment> segs;
+    int rc = p2s_workers_segments(ws, nq, segs);
+    if (rc) return rc;
+    if ((rc = p2s_workers_reserve(m, nq))) return rc;
+    p2s_model_s::Workers &wk = m->wk;
+    if ((rc = p2s_launch_stream_order(ws->first_position, nq, ws->n_streams, ws->batch, q, wk.q, wk.src, s))) return rc;
+    LogitsCapture perm_cap(nullptr);
+    perm_cap.dev = cap.dev ? wk.logits : nullptr;
+    perm_cap.room = cap.dev ? nq : 0;
+    p2s_rng_s *f0 = segs[0].first;
+    rc = run_pipeline(m, c, segs[0].sub, rotate ? f0 : nullptr, m->cfg.patch_radius > 0.0 ? f0 : nullptr, wk.q, 0, nq, chunk, wk.sdf, s,
+                      perm_cap, segs.data(), (int)segs.size());
+    if (rc) return rc;
+    if ((rc = p2s_launch_unpermute(wk.src, nq, wk.sdf, sdf_out_dev, perm_cap.dev, cap.dev, m->cfg.output_dim, s))) return rc;
+    P2S_HIP_CHECK(hipStreamSynchronize(s));
+    for (const P2sSegment &g : segs) {
+        if ((rc = p2s_rng_check(g.sub, s))) return rc;
+        if (g.first && (rc = p2s_rng_check(g.first, s))) return rc;
+    }
+    return P2S_OK;
+}
+
+static int workers_refuse_small(p2s_model_s *m, p2s_cloud_s *c, const p2s_worker_streams *ws, const char *who) {
+    if (ws->n_streams > 1 && c->d.n < m->cfg.sub_sample_size) {
+        p2s_set_error("%s: cloud of %d points, fewer than the sub-sample of %d, with %d workers: every worker shuffles its own "
+                      "cached copy of shape.pts (and the result depends on --cache_capacity) -- not modelled", who, c->d.n,
+                      m->cfg.sub_sample_size, ws->n_streams);
+        return P2S_EINVAL;
+    }
+    return P2S_OK;
+}
+
+extern "C" int p2s_infer_shape_workers(p2s_model_t m, p2s_cloud_t c, const p2s_worker_streams *ws, int res, int eps, int64_t q_begin,
+                                       int64_t q_end, int chunk, float *sdf_out_dev, float *q_out_dev, int64_t *n_done, void *stream) {
+    const LogitsCapture cap(m);
+    if (n_done) *n_done = 0;
+    if (!m || !c || !sdf_out_dev) {
+        p2s_set_error("p2s_infer_shape_workers: null argument");
+        return P2S_EINVAL;
+    }
+    int rc = p2s_workers_check(ws, m->cfg.patch_radius > 0.0, "p2s_infer_shape_workers");
+    if (rc || (rc = workers_refuse_small(m, c, ws, "p2s_infer_shape_workers"))) return rc;
+    P2S_HIP_CHECK(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    p2s_prof_reset(m);
+    const float *q_all = nullptr;
+    long long Q = 0;
+    const int eg0 = p2s_prof_mark(m, s);
+    if ((rc = p2s_cloud_grid(c, res, eps, &q_all, &Q, s))) return rc;
+    p2s_prof_span(m, ST_GRID, eg0, p2s_prof_mark(m, s));
+    if (q_end < 0) q_end = Q;
+    if (q_begin != 0 || q_end != Q) {
+        p2s_set_error("p2s_infer_shape_workers: query range [%lld,%lld) of a grid of %lld queries: workers mode takes whole shapes "
+                      "(a part would need the stream position of every other part)", (long long)q_begin, (long long)q_end, (long long)Q);
+        return P2S_EINVAL;
+    }
+    if (Q == 0) return P2S_OK;
+    if ((rc = run_workers(m, c, ws, false, q_all, Q, chunk, sdf_out_dev, s, cap))) return rc;
+    if (q_out_dev) {
+        P2S_HIP_CHECK(hipMemcpyAsync(q_out_dev, q_all, (size_t)Q * 12, hipMemcpyDeviceToDevice, s));
+        P2S_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    p2s_prof_collect(m);
+    if (n_done) *n_done = Q;
+    return P2S_OK;
+}
+
+extern "C" int p2s_infer_queries_workers(p2s_model_t m, p2s_cloud_t c, const p2s_worker_streams *ws, int rotate, const float *q_dev,
+                                         int64_t n_queries, int chunk, float *sdf_out_dev, void *stream) {
+    const LogitsCapture cap(m);
+    if (!m || !c || n_queries < 0 || (n_queries > 0 && (!q_dev || !sdf_out_dev))) {
+        p2s_set_error("p2s_infer_queries_workers: bad argument");
+        return P2S_EINVAL;
+    }
+    int rc = p2s_workers_check(ws, rotate || m->cfg.patch_radius > 0.0, "p2s_infer_queries_workers");
+    if (rc || (rc = workers_refuse_small(m, c, ws, "p2s_infer_queries_workers"))) return rc;
+    P2S_HIP_CHECK(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    p2s_prof_reset(m);
+    if (n_queries == 0) return P2S_OK;
+    if ((rc = run_workers(m, c, ws, rotate != 0, q_dev, n_queries, chunk, sdf_out_dev, s, cap))) return rc;
+    p2s_prof_collect(m);
     return P2S_OK;
 }

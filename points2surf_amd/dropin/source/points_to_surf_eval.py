@@ -8,8 +8,13 @@ MT19937 stream reproduced on the device, one stream over all shapes in dataset o
 reference's ``--workers 0`` semantics), the encoders and the decoder.
 
 Deliberate differences (documented in INTEGRATION.md):
-  * ``--workers`` / ``--cache_capacity`` / ``--batchSize`` do not influence results (the reference's
-    results depend on the worker count through duplicated RNG streams);
+  * by default ``--workers`` / ``--cache_capacity`` / ``--batchSize`` do not influence results: the sub-sample stream is
+    the reference's ``--workers 0`` one.  ``P2S_RNG_MODE=workers`` reproduces ``--workers W --batchSize B`` instead (the
+    command line of every eval script the reference ships): every DataLoader worker holds its own copies of both
+    RandomState(seed) generators, so the query at dataset position g draws from worker (g // B) mod W, W =
+    max(--workers, 1), B = --batchSize or the training batch size when it is 0 (reference :324-327).  Reconstruction
+    and GT-query passes, fixed-radius models and ``sequential_shapes_random_patches`` (position = index in the sampler's
+    sequence); refused with ``P2S_SHARD=queries`` and, with W > 1, for clouds smaller than the sub-sample;
   * ``--gpu_idx < 0`` raises: the reference's CPU branch does not run as written either
     (:167,362 call .cuda() unconditionally) and this engine has no CPU fallback;
   * the debug visualisations ``<out>/vis/*.ply`` and ``rec/query_pts_ms_vis/*.ply`` (sdf.visualize_query_points,
@@ -71,8 +76,10 @@ def parse_arguments(args=None):
     parser.add_argument('--query_points_per_patch', type=int, default=1, help='number of query points per patch')
     parser.add_argument('--sub_sample_size', type=int, default=500, help='overridden by the training parameters')
     parser.add_argument('--seed', type=int, default=40938661, help='manual seed')
-    parser.add_argument('--batchSize', type=int, default=0, help='accepted and ignored (the engine chooses its chunk size)')
-    parser.add_argument('--workers', type=int, default=0, help='ignored by the device data path')
+    parser.add_argument('--batchSize', type=int, default=0,
+                        help='the engine chooses its chunk size; P2S_RNG_MODE=workers: the DataLoader batch of the stream model')
+    parser.add_argument('--workers', type=int, default=0,
+                        help='ignored by the device data path, except P2S_RNG_MODE=workers (one stream set per worker)')
     parser.add_argument('--cache_capacity', type=int, default=100, help='ignored by the device data path')
 
     opt = parser.parse_args(args=args)
@@ -296,14 +303,29 @@ def points_to_surf_eval(eval_opt):
         os.makedirs(model_out_dir, exist_ok=True)
         print('getting information for {} shapes'.format(len(shape_names)))
 
-        # one RNG stream over all shapes in dataset order (--workers 0 semantics of the reference)
-        rng_dev = _engine.Rng(eval_opt.seed, device=device)
-        # the dataset's FIRST RandomState (data_loader.py:272): rand(3) per query -> rotation, GT-query pass only
-        # -- and, for fixed-radius models, the patch choice of every query in both passes (:336)
         ball = cfg['patch_radius'] > 0.0
-        rng_rot = None if (reconstruction and not ball) else _engine.Rng(eval_opt.seed, device=device)
+        rng_mode = os.environ.get('P2S_RNG_MODE', 'dataset')
+        if rng_mode not in ('dataset', 'per_shape', 'workers'):
+            raise ValueError('P2S_RNG_MODE=%s: expected dataset, per_shape or workers' % rng_mode)
+        per_shape_rng = rng_mode == 'per_shape'
+        streams = None
+        if rng_mode == 'workers':
+            if world > 1 and os.environ.get('P2S_SHARD', 'shapes') == 'queries':
+                raise ValueError('P2S_RNG_MODE=workers with P2S_SHARD=queries is not built: a part of a shape would need the '
+                                 'stream position of every other part (shard whole shapes instead)')
+            # --workers W --batchSize B of the reference: W stream sets (a fresh one per call, as the reference makes a fresh
+            # dataset), the query at dataset position g on worker (g // B) mod W (reference :324-327 for B)
+            batch = int(eval_opt.batchSize) if int(eval_opt.batchSize) != 0 else int(train_opt.batchSize)
+            streams = _engine.WorkerStreams(eval_opt.seed, max(int(eval_opt.workers), 1), batch, device=device,
+                                            first=ball or not reconstruction)
+            rng_dev, rng_rot = streams, (None if reconstruction else True)
+        else:
+            # one RNG stream over all shapes in dataset order (--workers 0 semantics of the reference)
+            rng_dev = _engine.Rng(eval_opt.seed, device=device)
+            # the dataset's FIRST RandomState (data_loader.py:272): rand(3) per query -> rotation, GT-query pass only
+            # -- and, for fixed-radius models, the patch choice of every query in both passes (:336)
+            rng_rot = None if (reconstruction and not ball) else _engine.Rng(eval_opt.seed, device=device)
         mine = set(range(len(shape_names)))
-        per_shape_rng = os.environ.get('P2S_RNG_MODE', 'dataset') == 'per_shape'
         # P2S_SHARD=queries: every rank takes a contiguous query range of EVERY shape (few, large shapes; 512^3 grids)
         # instead of whole shapes; the RNG stream is advanced past the other ranks' queries, results stay identical
         shard_queries = world > 1 and os.environ.get('P2S_SHARD', 'shapes') == 'queries' and not per_shape_rng \
@@ -326,6 +348,7 @@ def points_to_surf_eval(eval_opt):
                     counts.append(c.count_queries(eval_opt.query_grid_resolution, eval_opt.epsilon))
                     c.close()
             parts, owner = _sharding.assign_shapes(counts, world)
+            shape_start = [0] + list(np.cumsum(counts))        # workers mode: the dataset position of every shape
             mine = set(parts[rank])
             if handoff is not None:
                 handoff.owner = list(owner)
@@ -412,8 +435,12 @@ def points_to_surf_eval(eval_opt):
                 # dataset-wide stream exact on every rank by consuming this shape's draws without inference
                 cloud = _engine.Cloud(_load_points(eval_opt.indir, shape_name), device=device)
                 try:
-                    _sharding.skip_shape_stream(cloud, rng_dev, cfg, eval_opt.query_grid_resolution,
-                                                eval_opt.epsilon, model.sub_sample_size, rng_patch=rng_rot)
+                    if streams is not None:
+                        streams.skip_shape(cloud, cfg, cloud.query_grid(eval_opt.query_grid_resolution, eval_opt.epsilon),
+                                           model.sub_sample_size)
+                    else:
+                        _sharding.skip_shape_stream(cloud, rng_dev, cfg, eval_opt.query_grid_resolution,
+                                                    eval_opt.epsilon, model.sub_sample_size, rng_patch=rng_rot)
                 finally:
                     cloud.close()
                 continue
@@ -421,7 +448,7 @@ def points_to_surf_eval(eval_opt):
             with guard:                    # an exception here leaves a 'failed' record: waiting ranks raise, not hang
                 pts_np = _load_points(eval_opt.indir, shape_name)      # (inside the guard: a missing / corrupt file too)
                 if handoff is not None:
-                    rngs = [rng_dev] + ([rng_rot] if rng_rot is not None else [])
+                    rngs = streams.generators() if streams is not None else [rng_dev] + ([rng_rot] if rng_rot is not None else [])
                     handoff.begin(shape_ind, rngs)         # waits until the owner of the shape before has published
                     if handoff.must_publish(shape_ind):
                         def _advance(k):
@@ -429,11 +456,18 @@ def points_to_surf_eval(eval_opt):
                             c2 = _engine.Cloud(pts_np if k == shape_ind else _load_points(eval_opt.indir, shape_names[k]),
                                                device=device)
                             try:
-                                _sharding.skip_shape_stream(c2, rng_dev, cfg, eval_opt.query_grid_resolution,
-                                                            eval_opt.epsilon, model.sub_sample_size, rng_patch=rng_rot)
+                                if streams is not None:
+                                    streams.position = int(shape_start[k])
+                                    streams.skip_shape(c2, cfg, c2.query_grid(eval_opt.query_grid_resolution, eval_opt.epsilon),
+                                                       model.sub_sample_size)
+                                else:
+                                    _sharding.skip_shape_stream(c2, rng_dev, cfg, eval_opt.query_grid_resolution,
+                                                                eval_opt.epsilon, model.sub_sample_size, rng_patch=rng_rot)
                             finally:
                                 c2.close()
                         handoff.publish_after(shape_ind, rngs, _advance)
+                    if streams is not None:
+                        streams.position = int(shape_start[shape_ind])
                 cloud = _engine.Cloud(pts_np, device=device)
                 res_ = _infer_one_shape(model, cloud, rng_dev, eval_opt.query_grid_resolution, eval_opt.epsilon, chunk,
                                         rng_patch=rng_rot, want_logits=tie_file is not None)

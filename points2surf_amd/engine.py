@@ -353,6 +353,109 @@ class Rng:
         return ids, pts
 
 
+class WorkerStreams:
+    """The reference's sub-sample streams under ``--workers W --batchSize B`` (points2surf_amd/streams.py): every
+    DataLoader worker holds its own copies of both ``RandomState(seed)`` generators, and the query at dataset position g
+    draws from worker ``(g // B) mod W``.  Owns the W device twins of the sub-sample generator, optionally (``first``) the W
+    twins of the first generator (patch choice of fixed-radius models, rotation of the GT-query pass), and the dataset
+    cursor ``position`` (advanced by every call that consumes queries).  Pass it where ``infer_shape`` /
+    ``infer_queries`` take an ``Rng``."""
+
+    def __init__(self, seed, workers, batch_size, device=None, first=False):
+        W, B = int(workers), int(batch_size)
+        if W < 1 or B < 1:
+            raise ValueError('workers and batch size must be >= 1 (got %d, %d)' % (W, B))
+        self.lib = _lib.load()
+        self.seed, self.workers, self.batch_size = int(seed), W, B
+        self.sub = [Rng(seed, device=device) for _ in range(W)]
+        self.first = [Rng(seed, device=device) for _ in range(W)] if first else None
+        self.device = self.sub[0].device
+        self.position = 0
+
+    def generators(self):
+        """every generator, sub-sample twins first (the list a StreamHandoff carries)"""
+        return self.sub + (self.first or [])
+
+    def close(self):
+        for r in self.generators():
+            r.close()
+
+    def get_state(self):
+        return {'position': int(self.position), 'states': [r.get_state() for r in self.generators()]}
+
+    def set_state(self, state):
+        gens = self.generators()
+        if len(state['states']) != len(gens):
+            raise ValueError('state of %d generators, this stream set has %d' % (len(state['states']), len(gens)))
+        for r, (mt, pos) in zip(gens, state['states']):
+            r.set_state(mt, pos)
+        self.position = int(state['position'])
+
+    def struct(self, need_first=False):
+        """the ``p2s_worker_streams`` of the current cursor (kept alive on the object until the next call)"""
+        if need_first and self.first is None:
+            raise ValueError('this call draws from the first generator: WorkerStreams(..., first=True)')
+        W = self.workers
+        self._sub_arr = (ctypes.c_void_p * W)(*[r.handle.value for r in self.sub])
+        self._first_arr = (ctypes.c_void_p * W)(*[r.handle.value for r in self.first]) if self.first else None
+        self._ws = _lib.WorkerStreams(W, self.batch_size, int(self.position),
+                                      ctypes.cast(self._sub_arr, ctypes.POINTER(ctypes.c_void_p)),
+                                      ctypes.cast(self._first_arr, ctypes.POINTER(ctypes.c_void_p)) if self._first_arr else None)
+        return ctypes.byref(self._ws)
+
+    def stream_order(self, n, queries=None):
+        """p2s_stream_order at the cursor: (queries in stream-major order [n,3] or None, source index [n] int64, counts [W])
+        device tensors / numpy array; the cursor does not move"""
+        n = int(n)
+        src = torch.empty((max(n, 1),), dtype=torch.int64, device=self.device)
+        counts = np.zeros(self.workers, dtype=np.int64)
+        q = _f32c(queries, self.device).reshape(-1, 3) if queries is not None else None
+        qo = torch.empty((max(n, 1), 3), dtype=torch.float32, device=self.device) if q is not None else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.p2s_stream_order(int(self.position), n, self.workers, self.batch_size, _ptr(q), _ptr(qo),
+                                                 _ptr(src), counts.ctypes.data_as(ctypes.c_void_p), _stream_ptr(self.device)))
+        return (qo[:n] if qo is not None else None), src[:n], counts
+
+    def subsample(self, cloud, n, query_ms=None, n_queries=None, want_pts=True):
+        """the global sub-sample of the next queries in query order (p2s_subsample_workers): uniform (``n_queries``) or
+        distance-weighted at ``query_ms``; ids [Q,n] int32 (+ points [Q,n,3]).  Advances the cursor."""
+        q = None if query_ms is None else _f32c(query_ms, self.device).reshape(-1, 3)
+        nq = int(q.shape[0]) if q is not None else int(n_queries)
+        ids = torch.empty((max(nq, 1), n), dtype=torch.int32, device=self.device)
+        pts = torch.empty((max(nq, 1), n, 3), dtype=torch.float32, device=self.device) if want_pts else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.p2s_subsample_workers(cloud.handle, self.struct(), _ptr(q), nq, int(n), int(q is not None),
+                                                      _ptr(ids), _ptr(pts), _stream_ptr(self.device)))
+        self.position += nq
+        return ids[:nq], (pts[:nq] if pts is not None else None)
+
+    def skip_shape(self, cloud, cfg, queries, sub_sample_size):
+        """advance every stream past the queries of one shape ([m,3] device tensor, in dataset order) without inference:
+        the stream order at the cursor, then ``Rng.skip`` (and, fixed-radius models, the patch choices) on each stream's
+        slice (sharding.skip_queries).  Advances the cursor; returns the number of queries."""
+        from . import sharding
+        ball = float(cfg.get('patch_radius', 0.0) or 0.0) > 0.0
+        if ball and self.first is None:
+            raise ValueError('fixed-radius model: the stream set needs the first generators (first=True)')
+        if self.workers > 1 and cloud.n < sub_sample_size:
+            raise ValueError('workers mode: a cloud with fewer points (%d) than the sub-sample (%d) is not supported with %d '
+                             'workers' % (cloud.n, sub_sample_size, self.workers))
+        m = int(queries.shape[0])
+        q_perm, _, counts = self.stream_order(m, queries)
+        at = 0
+        for w, cnt in enumerate(counts):
+            cnt = int(cnt)
+            if cnt:
+                sharding.skip_queries(cloud, self.sub[w], cfg, q_perm[at:at + cnt], sub_sample_size,
+                                      rng_patch=self.first[w] if ball else None)
+            at += cnt
+        torch.cuda.synchronize(self.device)
+        for r in self.generators():
+            r.check()
+        self.position += m
+        return m
+
+
 def query_inputs(model, cloud, rng, queries, index):
     """Diagnostic: the network inputs of query ``index`` of a shape whose queries (in order) are ``queries``, with
     ``rng`` positioned at the shape's first draw -- the stream is advanced past the queries before it (NULL-ids path),
@@ -437,9 +540,14 @@ def infer_shape(model, cloud, rng, grid_resolution, epsilon, q_begin=0, q_end=-1
     """Fused per-shape pipeline (p2s_infer_shape).  Returns (sdf [n] device tensor, q [n,3] or None).
     ``n_queries``: the size of the query grid if the caller already asked for it (Cloud.count_queries).
     ``rng_patch``: fixed-radius models -- the data set's first generator (patch choice).
-    ``want_logits``: also return the decoder's raw logits [n, output_dim] as a third value (p2s_model_capture_logits)."""
+    ``want_logits``: also return the decoder's raw logits [n, output_dim] as a third value (p2s_model_capture_logits).
+    ``rng`` may be a WorkerStreams (workers mode, p2s_infer_shape_workers): whole shapes only, ``rng_patch`` unused (the
+    stream set's first generators), and the set's cursor advances by the shape's queries."""
     dev = model.device
     lib = model.lib
+    workers = isinstance(rng, WorkerStreams)
+    if workers and rng_patch is not None:
+        raise ValueError('workers mode: the patch choice draws from the WorkerStreams\' own first generators')
     with torch.cuda.device(dev):
         Q = cloud.count_queries(grid_resolution, epsilon) if n_queries is None else int(n_queries)
         qe = Q if q_end < 0 else q_end
@@ -451,10 +559,16 @@ def infer_shape(model, cloud, rng, grid_resolution, epsilon, q_begin=0, q_end=-1
         if want_logits:
             logits = torch.empty((max(nq, 1), model.output_dim), dtype=torch.float32, device=dev)
             _lib.check(lib.p2s_model_capture_logits(model.handle, _ptr(logits), nq))
-        _lib.check(lib.p2s_infer_shape_ball(model.handle, cloud.handle, rng.handle,
-                                            rng_patch.handle if rng_patch is not None else None, int(grid_resolution),
-                                            int(epsilon), int(q_begin), int(qe), int(chunk), _ptr(sdf), _ptr(q),
-                                            ctypes.byref(done), _stream_ptr(dev)))
+        if workers:
+            _lib.check(lib.p2s_infer_shape_workers(model.handle, cloud.handle, rng.struct(need_first=model.cfg.get('patch_radius', 0.0) > 0.0),
+                                                   int(grid_resolution), int(epsilon), int(q_begin), int(qe), int(chunk), _ptr(sdf),
+                                                   _ptr(q), ctypes.byref(done), _stream_ptr(dev)))
+            rng.position += nq
+        else:
+            _lib.check(lib.p2s_infer_shape_ball(model.handle, cloud.handle, rng.handle,
+                                                rng_patch.handle if rng_patch is not None else None, int(grid_resolution),
+                                                int(epsilon), int(q_begin), int(qe), int(chunk), _ptr(sdf), _ptr(q),
+                                                ctypes.byref(done), _stream_ptr(dev)))
     if want_logits:
         return sdf[:nq], (q[:nq] if q is not None else None), logits[:nq]
     return sdf[:nq], (q[:nq] if q is not None else None)
@@ -476,19 +590,32 @@ def rotate_points(rot, pts):
     return out
 
 
-def infer_queries(model, cloud, rng_sub, rng_rot, queries, chunk=0):
+def infer_queries(model, cloud, rng_sub, rng_rot, queries, chunk=0, want_logits=False):
     """GT-query evaluation pass for one shape (p2s_infer_queries): SDF at the given query points, with the
     reference's per-query random rotation when ``rng_rot`` is given (reference source/data_loader.py:365-393).
-    Returns sdf [n] device tensor."""
+    ``rng_sub`` may be a WorkerStreams (workers mode, p2s_infer_queries_workers): ``rng_rot`` is then a flag -- the
+    rotations (and a fixed-radius model's patch choices) come from the set's first generators -- and the cursor advances
+    by the queries.  Returns sdf [n] device tensor (+ logits [n, output_dim] with ``want_logits``)."""
     dev = model.device
     q = _f32c(queries, dev).reshape(-1, 3)
     nq = int(q.shape[0])
     sdf = torch.empty((max(nq, 1),), dtype=torch.float32, device=dev)
+    logits = None
     with torch.cuda.device(dev):
+        if want_logits:
+            logits = torch.empty((max(nq, 1), model.output_dim), dtype=torch.float32, device=dev)
+            _lib.check(model.lib.p2s_model_capture_logits(model.handle, _ptr(logits), nq))
+        if isinstance(rng_sub, WorkerStreams):
+            rotate = bool(rng_rot)
+            ws = rng_sub.struct(need_first=rotate or model.cfg.get('patch_radius', 0.0) > 0.0)
+            _lib.check(model.lib.p2s_infer_queries_workers(model.handle, cloud.handle, ws, int(rotate), _ptr(q), nq, int(chunk),
+                                                           _ptr(sdf), _stream_ptr(dev)))
+            rng_sub.position += nq
+            return (sdf[:nq], logits[:nq]) if want_logits else sdf[:nq]
         _lib.check(model.lib.p2s_infer_queries(model.handle, cloud.handle, rng_sub.handle,
                                                rng_rot.handle if rng_rot is not None else None, _ptr(q), nq,
                                                int(chunk), _ptr(sdf), _stream_ptr(dev)))
-    return sdf[:nq]
+    return (sdf[:nq], logits[:nq]) if want_logits else sdf[:nq]
 
 
 def sdf_volume(query_pts_ms, query_dist_ms, grid_resolution, sigma, certainty_threshold, clamp=True):
