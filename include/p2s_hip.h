@@ -343,8 +343,9 @@ int p2s_infer_queries_workers(p2s_model_t m, p2s_cloud_t c, const p2s_worker_str
  * generator moved).  Synchronises `stream`. */
 int p2s_subsample_workers(p2s_cloud_t c, const p2s_worker_streams *ws, const float *q_dev, int64_t n_queries, int n, int weighted,
                           int32_t *ids_out_dev, float *pts_out_dev, void *stream);
-/* One-shot capture of the decoder's raw logits: the NEXT p2s_infer_shape / p2s_infer_shape_ball / p2s_infer_queries call on
- * this model also writes logits_out_dev [processed queries][output_dim] (column output_dim - 1 = the sign logit, or the one
+/* One-shot capture of the decoder's raw logits: the NEXT p2s_infer_shape / p2s_infer_shape_ball / p2s_infer_queries /
+ * p2s_infer_shape_workers / p2s_infer_queries_workers call on this model (p2s_encode_* leave the capture in place) also
+ * writes logits_out_dev [processed queries][output_dim] (column output_dim - 1 = the sign logit, or the one
  * signed-distance logit of the regression model) -- what post_process (reference source/points_to_surf_eval.py:174-196)
  * starts from.  The drop-in's tie report (P2S_TIE_REPORT) lists the queries whose sign logit lies within fp32 noise of the
  * reference's decision ``logit >= 0`` (source/sdf_nn.py:16-21).  capacity_queries < the queries of that call: the call

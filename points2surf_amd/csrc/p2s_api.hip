@@ -565,14 +565,14 @@ int p2s_run_chunk(p2s_model_s *m, const float *patch, const float *sub, const fl
     return P2S_OK;
 }
 
-int p2s_model_fallback_finish(p2s_model_s *m, float *logits_out, float *sdf_out, hipStream_t s) {
+// fp16 pair mode (ModelCall::finish): the collected queries through the fp32 kernels, their results scattered over the outputs
+static int fallback_finish(p2s_model_s *m, float *logits_out, float *sdf_out, hipStream_t s) {
     p2s_model_s::Fallback &fb = m->fb;
     if (!fb.count) return P2S_OK;
     int h = 0;
     P2S_HIP_CHECK(hipMemcpyAsync(&h, fb.count, 4, hipMemcpyDeviceToHost, s));
     P2S_HIP_CHECK(hipStreamSynchronize(s));
     if (!h) return P2S_OK;
-    P2S_HIP_CHECK(hipMemsetAsync(fb.count, 0, 4, s));
     if (h > fb.cap || (!logits_out && !sdf_out)) {
         p2s_set_error("fp16 pair encoder (encoder_bf16 = 4): %d queries of this call have activations beyond the half range (> 6e4)%s "
                       "-- use encoder_bf16 = 3 or 0 for this model", h,
@@ -618,13 +618,13 @@ void p2s_prof_span(p2s_model_s *m, int stage, int a, int b) {
     if (a >= 0 && b >= 0) m->spans.push_back({stage, a, b});
 }
 
-void p2s_prof_reset(p2s_model_s *m) {
+static void prof_reset(p2s_model_s *m) {
     m->ev_used = 0;
     m->spans.clear();
     memset(&m->counters, 0, sizeof(m->counters));
 }
 
-void p2s_prof_collect(p2s_model_s *m) {
+static void prof_collect(p2s_model_s *m) {           // synchronises the last event
     if (!m->profiling || m->ev_used == 0) return;
     (void)hipEventSynchronize(m->evpool[m->ev_used - 1]);
     for (const auto &sp : m->spans) {
@@ -650,35 +650,65 @@ void p2s_prof_collect(p2s_model_s *m) {
     m->spans.clear();
 }
 
+ModelCall::ModelCall(p2s_model_s *m_, hipStream_t s_, bool pipeline_) : m(m_), s(s_), pipeline(pipeline_) {
+    if (!m) return;
+    if (pipeline) {
+        logits = m->logits_capture;
+        logits_room = m->logits_capacity;
+        m->logits_capture = nullptr;
+        m->logits_capacity = 0;
+    }
+    rc = [&]() -> int {
+        P2S_HIP_CHECK(hipSetDevice(m->device));
+        prof_reset(m);
+        if (m->fb.count) {
+            P2S_HIP_CHECK(hipMemsetAsync(m->fb.count, 0, 4, s));
+            P2S_HIP_CHECK(hipMemsetAsync(m->fb.flags, 0, (size_t)m->max_chunk * 4, s));
+        }
+        return P2S_OK;
+    }();
+}
+
+int ModelCall::fail(int code) {
+    if (!m) return code;
+    (void)hipStreamSynchronize(s);          // (an error here is a real fault and stays pending)
+    if (pipeline && m->aux) (void)hipStreamSynchronize(m->aux);
+    if (pipeline && m->ball) (void)hipStreamSynchronize(m->ball);
+    return code;
+}
+
+int ModelCall::finish(float *logits_out, float *sdf_out, int64_t nq) {
+    m->counters.queries += nq;
+    const int rc2 = fallback_finish(m, logits_out, sdf_out, s);
+    if (rc2) return fail(rc2);
+    prof_collect(m);
+    return P2S_OK;
+}
+
 static int run_batched(p2s_model_s *m, const float *patch, const float *sub, const float *query, const float *radius,
                        int B, float *logits, float *sdf, float *fl, float *fg, hipStream_t s) {
+    ModelCall call(m, s, false);
     if (!m || B < 0 || !patch || !sub || !query) {
         p2s_set_error("encode: null argument");
-        return P2S_EINVAL;
+        return call.fail(P2S_EINVAL);
     }
     if (sdf && !radius) {
         p2s_set_error("encode: sdf_out requested without radius");
-        return P2S_EINVAL;
+        return call.fail(P2S_EINVAL);
     }
-    P2S_HIP_CHECK(hipSetDevice(m->device));
     const int chunk = std::min(B, m->max_chunk);
-    int rc = p2s_model_reserve(m, chunk);
-    if (rc) return rc;
+    int rc = call.rc ? call.rc : p2s_model_reserve(m, chunk);
+    if (rc) return call.fail(rc);
     const int PL = m->cfg.points_per_patch, PG = m->cfg.sub_sample_size;
-    p2s_prof_reset(m);
     for (int q0 = 0; q0 < B; q0 += chunk) {
         const int C = std::min(chunk, B - q0);
         rc = p2s_run_chunk(m, patch + (size_t)q0 * PL * 3, sub + (size_t)q0 * PG * 3, query + (size_t)q0 * 3,
                            radius ? radius + q0 : nullptr, C, logits ? logits + (size_t)q0 * m->cfg.output_dim : nullptr,
                            sdf ? sdf + q0 : nullptr, fl ? fl + (size_t)q0 * 1024 : nullptr,
                            fg ? fg + (size_t)q0 * 1024 : nullptr, s, q0);
-        if (rc) return rc;
+        if (rc) return call.fail(rc);
     }
-    p2s_prof_collect(m);
-    m->counters.queries += B;
-    // fp16 pair encoder: queries with activations beyond the half range are repaired by the fp32 kernels now (this
-    // synchronises `s` in that mode only)
-    return p2s_model_fallback_finish(m, logits, sdf, s);
+    return call.finish(logits, sdf, B);
 }
 
 extern "C" {

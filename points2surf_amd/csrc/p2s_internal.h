@@ -36,10 +36,10 @@ struct p2s_model_s {
     size_t h_sf1[2] = {}, h_sf2[2] = {}, h_sf3[2] = {}, h_qf1 = 0, h_qf2 = 0;
     bool heads_f16 = false;
     // fp16 pair mode: queries with an activation beyond the half range are flagged by the 16-bit kernels, collected per
-    // chunk (inputs copied aside) and re-run through the fp32 kernels at the end of the same call (p2s_model_fallback_finish)
+    // chunk (inputs copied aside) and re-run through the fp32 kernels at the end of the same call (ModelCall::finish)
     struct Fallback {
         int *flags = nullptr;              // [max_chunk] per query of the chunk in flight
-        int *count = nullptr;              // queries collected since the last finish (may run past cap: overflow)
+        int *count = nullptr;              // queries collected by the call (may run past cap: overflow)
         float *patch = nullptr, *sub = nullptr, *query = nullptr, *radius = nullptr;   // [cap] inputs of the collected queries
         long long *index = nullptr;        // [cap] position in the call's output arrays
         float *sdf = nullptr, *logits = nullptr;                                       // [cap] results of the fp32 run
@@ -65,18 +65,19 @@ struct p2s_model_s {
                                    // stream so that it runs beside the sub-sample kernels of the auxiliary stream, not behind them
     bool overlap = true;
     PipeBuffers pipe;
-    int fault_chunk = -1;
+    int fault_chunk = -1;          // test hook (p2s_debug_fault_chunk): fail with P2S_EHIP before this chunk
     // workers mode (p2s_streams.hip): the stream-ordered queries, their source indices and the SDF / logits produced in that
     // order, before the scatter to the caller's buffers; grown on demand
     struct Workers {
         float *q = nullptr, *sdf = nullptr, *logits = nullptr;
         int64_t *src = nullptr;
         int64_t cap = 0;
-    } wk;          // test hook (p2s_debug_fault_chunk): fail with P2S_EHIP before this chunk
+    } wk;
 };
 void p2s_pipe_free(p2s_model_s *m);
 
-// workers mode (p2s_streams.hip): one segment of stream-ordered queries and the generators it draws from
+// consecutive pipeline queries and their generators (first: patch choice / rotation, NULL if unused): dataset mode is one
+// segment, workers mode (p2s_streams.hip) one per non-empty stream
 struct P2sSegment {
     p2s_rng_s *sub;
     p2s_rng_s *first;
@@ -94,20 +95,32 @@ int p2s_launch_unpermute(const int64_t *src, int64_t n, const float *sdf_in, flo
 // cfg.encoder_bf16: 0 fp32, 1 bf16, 2 / 3 split bf16, 4 fp16 pair (2 pieces, two accumulators)
 inline int p2s_enc_pieces(const p2s_model_cfg &c) { return c.encoder_bf16 == 4 ? 2 : c.encoder_bf16; }
 inline int p2s_enc_f16(const p2s_model_cfg &c) { return c.encoder_bf16 == 4 ? 1 : 0; }
-// fp16 pair mode, at the end of every call: the queries the 16-bit kernels flagged (an activation beyond the half range) run
-// through the fp32 kernels and their results replace the poisoned ones in logits_out [.][output_dim] / sdf_out (either
-// may be null).  Synchronises `s` in that mode.  More flagged queries than the side buffers hold (16384 per call), or a
-// call without either output (p2s_encode_features): P2S_EINVAL.
-int p2s_model_fallback_finish(p2s_model_s *m, float *logits_out, float *sdf_out, hipStream_t s);
+
+// One call of a model entry point (p2s_encode_*, the pipeline calls), constructed first.  Construction (m == NULL: nothing)
+// takes the one-shot logits capture off the model (pipeline calls, whatever the outcome), sets the device, resets the profile
+// and clears the fp16-pair fallback state on `s`: nothing an earlier call left there is re-run or scattered by this one.
+struct ModelCall {
+    p2s_model_s *const m;
+    const hipStream_t s;
+    const bool pipeline;
+    float *logits = nullptr;      // pipeline calls: the capture buffer [logits_room][output_dim] (p2s_model_capture_logits)
+    int64_t logits_room = 0;
+    int rc = P2S_OK;              // outcome of the set-up
+    ModelCall(p2s_model_s *m, hipStream_t s, bool pipeline);
+    // every error exit: drains `s` (pipeline calls: the model's own streams too), so the next call's reset is ordered; -> code
+    int fail(int code);
+    // the success exit: counters.queries += nq; fp16 pair mode: the flagged queries (an activation beyond the half range) re-run
+    // in fp32 into logits_out [.][output_dim] / sdf_out (either may be NULL; synchronises `s`; more than the 16384 the side
+    // buffers hold, or neither output: P2S_EINVAL); the profile is collected
+    int finish(float *logits_out, float *sdf_out, int64_t nq);
+};
 
 enum P2SStage { ST_CHAIN_STN = 0, ST_HEAD, ST_CHAIN_MAIN, ST_DECODER, ST_KNN, ST_SUB, ST_GRID, ST_CHAIN_QSTN };
 int p2s_prof_mark(p2s_model_s *m, hipStream_t s);                 // event index or -1
 void p2s_prof_span(p2s_model_s *m, int stage, int a, int b);
-void p2s_prof_reset(p2s_model_s *m);
-void p2s_prof_collect(p2s_model_s *m);                            // synchronises the last event
 
 int p2s_model_reserve(p2s_model_s *m, int chunk);
-// index0: position of the chunk's first query in the CALL's output arrays (what the fp32 fallback scatters to)
+// index0: position of the chunk's first query in the output arrays of the call's finish() (what the fp32 fallback scatters to)
 int p2s_run_chunk(p2s_model_s *m, const float *patch, const float *sub, const float *query, const float *radius,
                   int C, float *logits_out, float *sdf_out, float *feat_local_out, float *feat_global_out,
                   hipStream_t s, long long index0 = 0);

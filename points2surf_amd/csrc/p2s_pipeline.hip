@@ -208,27 +208,11 @@ extern "C" int p2s_debug_fault_chunk(p2s_model_t m, int chunk_index) {
     return P2S_OK;
 }
 
-// queries q_all[q_begin, q_end) through the double-buffered pipeline.  r_rot != NULL: GT-query pass (rotation).
-// r_patch: fixed-radius models only (the generator of the patch choice; in the GT-query pass the same handle as r_rot).
-// one-shot logits capture (p2s_model_capture_logits): taken off the model at the top of the call that consumes it, whatever
-// the call's outcome
-struct LogitsCapture {
-    float *dev;
-    int64_t room;
-    explicit LogitsCapture(p2s_model_s *m) : dev(m ? m->logits_capture : nullptr), room(m ? m->logits_capacity : 0) {
-        if (m) {
-            m->logits_capture = nullptr;
-            m->logits_capacity = 0;
-        }
-    }
-};
-
-// segs != NULL (workers mode, p2s_worker_segments): the queries are in stream-major order and consecutive segments of
-// segs[i].rows queries draw from their own generators -- segs[i].sub for the sub-sample, segs[i].first for the patch choice
-// and the rotation; r / r_rot / r_patch then only say which of them the call uses (and r_patch hosts the ball counts).
-static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s *r_rot, p2s_rng_s *r_patch, const float *q_all,
-                        int64_t q_begin, int64_t q_end, int chunk, float *sdf_out_dev, hipStream_t s, const LogitsCapture &cap,
-                        const P2sSegment *segs = nullptr, int nseg = 0) {
+// queries q [nq][3] (nq > 0) through the double-buffered pipeline, consecutive segments segs[i].rows of them on their own
+// generators.  rotate: GT-query pass.  sdf_out [nq], logits_out [nq][output_dim] (may be NULL).  Drains every stream it used
+// before it returns, on success too.
+static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, const P2sSegment *segs, int nseg, bool rotate, const float *q, int64_t nq,
+                        int chunk, float *sdf_out_dev, float *logits_out, hipStream_t s) {
     const bool weighted = m->cfg.weighted_subsample != 0;   // p2s_vanilla: choice(p, replace=False) per query
     const double ball_r = m->cfg.patch_radius;
     const bool ball = ball_r > 0.0;                         // patch = points within a fixed radius (p2s_ball.hip)
@@ -263,14 +247,6 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
     // function on every exit (fail(), and the guard below as a backstop): a cloud handle must not keep, let alone
     // synchronise, a stream of a model that may be destroyed before it
     p2s_cloud_note_stream(c, s);
-    const int64_t nq = q_end - q_begin;
-    float *const logits_cap = cap.dev;
-    const int64_t logits_room = cap.room;
-    if (logits_cap && logits_room < nq) {
-        p2s_set_error("p2s pipeline: logits capture buffer holds %lld queries, the call processes %lld", (long long)logits_room, (long long)nq);
-        return P2S_ECAPACITY;
-    }
-    if (nq <= 0) return P2S_OK;
     struct QuietGuard {
         p2s_cloud_s *c;
         p2s_model_s *m;
@@ -288,7 +264,7 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
     // clouds with fewer points than the sub-sample: shuffle + pad, and shape.pts permuted under the kd-tree
     // (reference source/base/utils.py:221-226; p2s_subsample_shuffle_pad)
     const bool small = c->d.n < n;
-    if (ball && (small || !r_patch || (r_rot && r_rot != r_patch))) {
+    if (ball && (small || std::any_of(segs, segs + nseg, [](const P2sSegment &g) { return !g.first; }))) {
         p2s_set_error("p2s pipeline: a fixed-radius model needs the generator of the patch choice (the rotation generator of the "
                       "GT-query pass) and a cloud with at least sub_sample_size points");
         return P2S_EINVAL;
@@ -334,16 +310,15 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
     const int32_t *ball_ch = nullptr;
     if (ball) {
         const int eb0 = p2s_prof_mark(m, s);
-        if ((rc = p2s_ball_counts_to_host(r_patch, c, q_all + (size_t)q_begin * 3, nq, ball_r, &ball_cd, &ball_ch, s))) return fail(rc);
+        if ((rc = p2s_ball_counts_to_host(segs[0].first, c, q, nq, ball_r, &ball_cd, &ball_ch, s))) return fail(rc);
         p2s_prof_span(m, ST_KNN, eb0, p2s_prof_mark(m, s));
     }
     const bool use_done = ball && sbl != s;
 
     const int64_t nchunks = (nq + C - 1) / C;
-    // the pieces of local rows [lo, lo + len) that fall into one segment each: fn(sub generator, first generator, row offset
-    // in the chunk, first local row, rows).  Without segments: one piece on the call's generators.
+    // the pieces of rows [lo, lo + len) that fall into one segment each: fn(sub generator, first generator, row offset in the
+    // chunk, first row, rows)
     auto pieces = [&](int64_t lo, int64_t len, auto &&fn) -> int {
-        if (!segs) return fn(r, r_rot ? r_rot : r_patch, 0, lo, len);
         int64_t at = 0;
         for (int i = 0; i < nseg; ++i) {
             const int64_t a = std::max(lo, at), e = std::min(lo + len, at + segs[i].rows);
@@ -357,12 +332,12 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
     };
     auto produce = [&](int64_t ci) -> int {       // sub-sample ids of chunk ci on the aux stream
         const int bi = (int)(ci % nbuf);
-        const int64_t q0 = q_begin + ci * C;
-        const int cur = (int)std::min<int64_t>(C, q_end - q0);
+        const int64_t q0 = ci * C;
+        const int cur = (int)std::min<int64_t>(C, nq - q0);
         if (ci >= nbuf && sa != s) PIPE_HIP(hipStreamWaitEvent(sa, b.freed[bi], 0));
         const int e0 = p2s_prof_mark(m, sa);
-        int rc2 = pieces(q0 - q_begin, cur, [&](p2s_rng_s *rs, p2s_rng_s *, int64_t off, int64_t row, int64_t cnt) -> int {
-            const float *qp = q_all + (size_t)(q_begin + row) * 3;
+        int rc2 = pieces(q0, cur, [&](p2s_rng_s *rs, p2s_rng_s *, int64_t off, int64_t row, int64_t cnt) -> int {
+            const float *qp = q + (size_t)row * 3;
             int32_t *ids = b.sub_ids[bi] + (size_t)off * n;
             if (small)
                 return p2s_subsample_shuffle_pad(rs, c, cnt, n, b.perm[bi] + (size_t)off * n, ids, sa);
@@ -379,10 +354,10 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
             // the encoders of the chunks before; the encoders of chunk ci - nbuf read the patch buffer it fills
             if (ci >= nbuf && sbl != s) PIPE_HIP(hipStreamWaitEvent(sbl, b.done[bi], 0));
             const int eb0 = p2s_prof_mark(m, sbl);
-            rc2 = pieces(q0 - q_begin, cur, [&](p2s_rng_s *, p2s_rng_s *rf, int64_t off, int64_t row, int64_t cnt) -> int {
-                return p2s_ball_patch_counted(rf, c, q_all + (size_t)(q_begin + row) * 3, ball_cd + row, ball_ch + row, cnt, ball_r, k,
-                                              r_rot ? 6 : 0, nullptr, b.patch[bi] + (size_t)off * k * 3, b.radius[bi] + off,
-                                              r_rot ? b.rot[bi] + (size_t)off * 9 : nullptr, sbl);
+            rc2 = pieces(q0, cur, [&](p2s_rng_s *, p2s_rng_s *rf, int64_t off, int64_t row, int64_t cnt) -> int {
+                return p2s_ball_patch_counted(rf, c, q + (size_t)row * 3, ball_cd + row, ball_ch + row, cnt, ball_r, k,
+                                              rotate ? 6 : 0, nullptr, b.patch[bi] + (size_t)off * k * 3, b.radius[bi] + off,
+                                              rotate ? b.rot[bi] + (size_t)off * 9 : nullptr, sbl);
             });
             if (rc2) return fail(rc2);
             p2s_prof_span(m, ST_KNN, eb0, p2s_prof_mark(m, sbl));
@@ -394,9 +369,9 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
     // kNN patch + radius and the gathered sub-sample of chunk ci into buffer ci % nbuf (compute stream)
     auto prepare = [&](int64_t ci) -> int {
         const int bi = (int)(ci % nbuf);
-        const int64_t q0 = q_begin + ci * C;
-        const int cur = (int)std::min<int64_t>(C, q_end - q0);
-        const float *qc = q_all + (size_t)q0 * 3;
+        const int64_t q0 = ci * C;
+        const int cur = (int)std::min<int64_t>(C, nq - q0);
+        const float *qc = q + (size_t)q0 * 3;
         const int ek0 = p2s_prof_mark(m, s);
         int rc2 = P2S_OK;
         if (!ball) {
@@ -423,18 +398,18 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
         if ((rc = produce(ci))) return rc;
     for (int64_t ci = 0; ci < nchunks; ++ci) {
         const int bi = (int)(ci % nbuf);
-        const int64_t q0 = q_begin + ci * C;
-        const int cur = (int)std::min<int64_t>(C, q_end - q0);
-        const float *qc = q_all + (size_t)q0 * 3;
+        const int64_t q0 = ci * C;
+        const int cur = (int)std::min<int64_t>(C, nq - q0);
+        const float *qc = q + (size_t)q0 * 3;
         if (m->fault_chunk == (int)ci) {
             m->fault_chunk = -1;
             p2s_set_error("p2s pipeline: injected fault before chunk %lld (p2s_debug_fault_chunk)", (long long)ci);
             return fail(P2S_EHIP);
         }
         if ((rc = prepare(ci))) return rc;
-        if (r_rot) {
+        if (rotate) {
             // data_loader.py:381-393: rotate sub-sample (model space), patch (patch space) and the query point
-            if (!ball && (rc = pieces(q0 - q_begin, cur, [&](p2s_rng_s *, p2s_rng_s *rf, int64_t off, int64_t, int64_t cnt) -> int {
+            if (!ball && (rc = pieces(q0, cur, [&](p2s_rng_s *, p2s_rng_s *rf, int64_t off, int64_t, int64_t cnt) -> int {
                     return p2s_random_rotations(rf, cnt, b.rot[bi] + (size_t)off * 9, s);
                 })))
                 return fail(rc);
@@ -444,8 +419,8 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
             qc = b.qrot[bi];
         }
         rc = p2s_run_chunk(m, b.patch[bi], b.sub[bi], qc, b.radius[bi], cur,
-                           logits_cap ? logits_cap + (size_t)(q0 - q_begin) * m->cfg.output_dim : nullptr,
-                           sdf_out_dev + (q0 - q_begin), nullptr, nullptr, s, q0 - q_begin);
+                           logits_out ? logits_out + (size_t)q0 * m->cfg.output_dim : nullptr, sdf_out_dev + q0, nullptr, nullptr,
+                           s, q0);
         if (rc) return fail(rc);
         if (use_done) PIPE_HIP(hipEventRecord(b.done[bi], s));
         if (ci + nbuf < nchunks) {
@@ -453,10 +428,95 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, p2s_rng_s *r, p2s_rng_s 
         }
     }
 #undef PIPE_HIP
-    m->counters.queries += nq;
-    if ((rc = fail(P2S_OK))) return rc;
-    // fp16 pair encoder: the queries it flagged (activations beyond the half range) through the fp32 kernels, now
-    return p2s_model_fallback_finish(m, logits_cap, sdf_out_dev, s);
+    return fail(P2S_OK);
+}
+
+static int hip_status(hipError_t e, const char *what) {
+    if (e != hipSuccess) p2s_set_error("p2s pipeline: %s failed: %s", what, hipGetErrorString(e));
+    return e == hipSuccess ? P2S_OK : P2S_EHIP;
+}
+
+// Every pipeline call after its argument checks: the queries q [nq][3] through the pipeline, finish() and the check of every
+// generator drawn from.  ws == NULL: dataset mode, the queries are ONE segment on `one`'s generators.  Workers mode
+// (p2s_streams.hip): the queries in stream-major order, one segment per non-empty stream; SDF / logits (the fp16 fallback's
+// rows included) land in the model's stream-ordered buffers, then one scatter puts them back in query order.
+static int run_call(ModelCall &call, p2s_cloud_s *c, const p2s_worker_streams *ws, P2sSegment one, bool rotate, const float *q,
+                    int64_t nq, int chunk, float *sdf_out) {
+    p2s_model_s *m = call.m;
+    const hipStream_t s = call.s;
+    if (call.logits && call.logits_room < nq) {
+        p2s_set_error("p2s pipeline: logits capture buffer holds %lld queries, the call processes %lld", (long long)call.logits_room,
+                      (long long)nq);
+        return call.fail(P2S_ECAPACITY);
+    }
+    if (nq == 0) return call.finish(nullptr, nullptr, 0);
+    one.rows = nq;
+    std::vector<P2sSegment> segs{one};
+    float *sdf = sdf_out, *logits = call.logits;
+    int rc;
+    if (ws) {
+        p2s_workers_segments(ws, nq, segs);
+        if ((rc = p2s_workers_reserve(m, nq)) ||
+            (rc = p2s_launch_stream_order(ws->first_position, nq, ws->n_streams, ws->batch, q, m->wk.q, m->wk.src, s)))
+            return call.fail(rc);
+        q = m->wk.q;
+        sdf = m->wk.sdf;
+        logits = logits ? m->wk.logits : nullptr;
+    }
+    if ((rc = run_pipeline(m, c, segs.data(), (int)segs.size(), rotate, q, nq, chunk, sdf, logits, s))) return call.fail(rc);
+    if ((rc = call.finish(logits, sdf, nq))) return rc;
+    if (ws && ((rc = p2s_launch_unpermute(m->wk.src, nq, sdf, sdf_out, logits, call.logits, m->cfg.output_dim, s)) ||
+               (rc = hip_status(hipStreamSynchronize(s), "hipStreamSynchronize"))))
+        return call.fail(rc);
+    for (const P2sSegment &g : segs) {
+        if ((rc = p2s_rng_check(g.sub, s)) || (g.first && (rc = p2s_rng_check(g.first, s)))) return call.fail(rc);
+    }
+    return P2S_OK;
+}
+
+// the shape entries: queries [q_begin, q_end) of the grid of (res, eps) -- workers mode: the whole grid -- to q_out and
+// through run_call
+static int run_grid(ModelCall &call, p2s_cloud_s *c, const p2s_worker_streams *ws, P2sSegment one, int res, int eps, int64_t q_begin,
+                    int64_t q_end, int chunk, float *sdf_out, float *q_out, int64_t *n_done, const char *who) {
+    if (n_done) *n_done = 0;
+    p2s_model_s *m = call.m;
+    const hipStream_t s = call.s;
+    const float *q_all = nullptr;
+    long long Q = 0;
+    const int eg0 = p2s_prof_mark(m, s);
+    int rc = p2s_cloud_grid(c, res, eps, &q_all, &Q, s);
+    if (rc) return call.fail(rc);
+    p2s_prof_span(m, ST_GRID, eg0, p2s_prof_mark(m, s));
+    if (q_end < 0) q_end = Q;
+    if (ws && (q_begin != 0 || q_end != Q)) {
+        p2s_set_error("%s: query range [%lld,%lld) of a grid of %lld queries: workers mode takes whole shapes (a part would need the "
+                      "stream position of every other part)", who, (long long)q_begin, (long long)q_end, (long long)Q);
+        return call.fail(P2S_EINVAL);
+    }
+    if (q_begin < 0 || q_begin > q_end || q_end > Q) {
+        p2s_set_error("%s: query range [%lld,%lld) outside [0,%lld]", who, (long long)q_begin, (long long)q_end, (long long)Q);
+        return call.fail(P2S_EINVAL);
+    }
+    const int64_t nq = q_end - q_begin;
+    const float *q = q_all + (size_t)q_begin * 3;
+    if (q_out && nq > 0 && (rc = hip_status(hipMemcpyAsync(q_out, q, (size_t)nq * 12, hipMemcpyDeviceToDevice, s), "copy of the queries")))
+        return call.fail(rc);
+    if ((rc = run_call(call, c, ws, one, false, q, nq, chunk, sdf_out))) return rc;
+    if (n_done) *n_done = nq;
+    return P2S_OK;
+}
+
+// workers mode: the stream set, and a refusal of W > 1 streams over a cloud smaller than the sub-sample
+static int workers_refuse(p2s_model_s *m, p2s_cloud_s *c, const p2s_worker_streams *ws, bool need_first, const char *who) {
+    const int rc = p2s_workers_check(ws, need_first, who);
+    if (rc) return rc;
+    if (ws->n_streams > 1 && c->d.n < m->cfg.sub_sample_size) {
+        p2s_set_error("%s: cloud of %d points, fewer than the sub-sample of %d, with %d workers: every worker shuffles its own "
+                      "cached copy of shape.pts (and the result depends on --cache_capacity) -- not modelled", who, c->d.n,
+                      m->cfg.sub_sample_size, ws->n_streams);
+        return P2S_EINVAL;
+    }
+    return P2S_OK;
 }
 
 extern "C" int p2s_infer_shape(p2s_model_t m, p2s_cloud_t c, p2s_rng_t r, int res, int eps, int64_t q_begin,
@@ -473,154 +533,47 @@ extern "C" int p2s_infer_shape(p2s_model_t m, p2s_cloud_t c, p2s_rng_t r, int re
 extern "C" int p2s_infer_shape_ball(p2s_model_t m, p2s_cloud_t c, p2s_rng_t r, p2s_rng_t r_patch, int res, int eps,
                                     int64_t q_begin, int64_t q_end, int chunk, float *sdf_out_dev, float *q_out_dev,
                                     int64_t *n_done, void *stream) {
-    const LogitsCapture cap(m);
+    ModelCall call(m, (hipStream_t)stream, true);
     if (!m || !c || !r || !sdf_out_dev || r_patch == r) {
         p2s_set_error("p2s_infer_shape: null argument (or one generator handle passed twice)");
-        return P2S_EINVAL;
+        return call.fail(P2S_EINVAL);
     }
-    if (m->cfg.patch_radius <= 0.0) r_patch = nullptr;
-    P2S_HIP_CHECK(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
-    p2s_prof_reset(m);
-    const float *q_all = nullptr;
-    long long Q = 0;
-    const int eg0 = p2s_prof_mark(m, s);
-    int rc = p2s_cloud_grid(c, res, eps, &q_all, &Q, s);
-    if (rc) return rc;
-    p2s_prof_span(m, ST_GRID, eg0, p2s_prof_mark(m, s));
-    if (q_end < 0) q_end = Q;
-    if (q_begin < 0 || q_begin > q_end || q_end > Q) {
-        p2s_set_error("p2s_infer_shape: query range [%lld,%lld) outside [0,%lld]", (long long)q_begin,
-                      (long long)q_end, (long long)Q);
-        return P2S_EINVAL;
-    }
-    if (n_done) *n_done = 0;
-    const int64_t nq = q_end - q_begin;
-    if (nq == 0) return P2S_OK;
-    rc = run_pipeline(m, c, r, nullptr, r_patch, q_all, q_begin, q_end, chunk, sdf_out_dev, s, cap);
-    if (rc) return rc;
-    if (q_out_dev) {
-        P2S_HIP_CHECK(hipMemcpyAsync(q_out_dev, q_all + (size_t)q_begin * 3, (size_t)nq * 12, hipMemcpyDeviceToDevice, s));
-        P2S_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    p2s_prof_collect(m);
-    rc = p2s_rng_check(r, s);
-    if (rc) return rc;
-    if (r_patch && (rc = p2s_rng_check(r_patch, s))) return rc;
-    if (n_done) *n_done = nq;
-    return P2S_OK;
+    if (call.rc) return call.fail(call.rc);
+    const P2sSegment one = {r, m->cfg.patch_radius > 0.0 ? r_patch : nullptr, 0};
+    return run_grid(call, c, nullptr, one, res, eps, q_begin, q_end, chunk, sdf_out_dev, q_out_dev, n_done, "p2s_infer_shape");
 }
 
 extern "C" int p2s_infer_queries(p2s_model_t m, p2s_cloud_t c, p2s_rng_t r_sub, p2s_rng_t r_rot, const float *q_dev,
                                  int64_t n_queries, int chunk, float *sdf_out_dev, void *stream) {
-    const LogitsCapture cap(m);
+    ModelCall call(m, (hipStream_t)stream, true);
     if (!m || !c || !r_sub || (n_queries > 0 && (!q_dev || !sdf_out_dev)) || n_queries < 0 || r_rot == r_sub) {
         p2s_set_error("p2s_infer_queries: bad argument (the rotation generator must be a second handle)");
-        return P2S_EINVAL;
+        return call.fail(P2S_EINVAL);
     }
-    P2S_HIP_CHECK(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
-    p2s_prof_reset(m);
-    if (n_queries == 0) return P2S_OK;
-    int rc = run_pipeline(m, c, r_sub, r_rot, m->cfg.patch_radius > 0.0 ? r_rot : nullptr, q_dev, 0, n_queries, chunk, sdf_out_dev, s, cap);
-    if (rc) return rc;
-    p2s_prof_collect(m);
-    if ((rc = p2s_rng_check(r_sub, s))) return rc;
-    if (r_rot && (rc = p2s_rng_check(r_rot, s))) return rc;
-    return P2S_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Workers mode (p2s_streams.hip): the queries in stream-major order through the pipeline, one segment per non-empty
-// stream; SDF / logits (the fp16 fallback's rows included) land in the model's stream-ordered buffers, then one scatter.
-// ---------------------------------------------------------------------------------------------------------
-static int run_workers(p2s_model_s *m, p2s_cloud_s *c, const p2s_worker_streams *ws, bool rotate, const float *q, int64_t nq,
-                       int chunk, float *sdf_out_dev, hipStream_t s, const LogitsCapture &cap) {
-    if (cap.dev && cap.room < nq) {
-        p2s_set_error("p2s pipeline: logits capture buffer holds %lld queries, the call processes %lld", (long long)cap.room, (long long)nq);
-        return P2S_ECAPACITY;
-    }
-    std::vector<P2sSegment> segs;
-    int rc = p2s_workers_segments(ws, nq, segs);
-    if (rc) return rc;
-    if ((rc = p2s_workers_reserve(m, nq))) return rc;
-    p2s_model_s::Workers &wk = m->wk;
-    if ((rc = p2s_launch_stream_order(ws->first_position, nq, ws->n_streams, ws->batch, q, wk.q, wk.src, s))) return rc;
-    LogitsCapture perm_cap(nullptr);
-    perm_cap.dev = cap.dev ? wk.logits : nullptr;
-    perm_cap.room = cap.dev ? nq : 0;
-    p2s_rng_s *f0 = segs[0].first;
-    rc = run_pipeline(m, c, segs[0].sub, rotate ? f0 : nullptr, m->cfg.patch_radius > 0.0 ? f0 : nullptr, wk.q, 0, nq, chunk, wk.sdf, s,
-                      perm_cap, segs.data(), (int)segs.size());
-    if (rc) return rc;
-    if ((rc = p2s_launch_unpermute(wk.src, nq, wk.sdf, sdf_out_dev, perm_cap.dev, cap.dev, m->cfg.output_dim, s))) return rc;
-    P2S_HIP_CHECK(hipStreamSynchronize(s));
-    for (const P2sSegment &g : segs) {
-        if ((rc = p2s_rng_check(g.sub, s))) return rc;
-        if (g.first && (rc = p2s_rng_check(g.first, s))) return rc;
-    }
-    return P2S_OK;
-}
-
-static int workers_refuse_small(p2s_model_s *m, p2s_cloud_s *c, const p2s_worker_streams *ws, const char *who) {
-    if (ws->n_streams > 1 && c->d.n < m->cfg.sub_sample_size) {
-        p2s_set_error("%s: cloud of %d points, fewer than the sub-sample of %d, with %d workers: every worker shuffles its own "
-                      "cached copy of shape.pts (and the result depends on --cache_capacity) -- not modelled", who, c->d.n,
-                      m->cfg.sub_sample_size, ws->n_streams);
-        return P2S_EINVAL;
-    }
-    return P2S_OK;
+    if (call.rc) return call.fail(call.rc);
+    return run_call(call, c, nullptr, {r_sub, r_rot, 0}, r_rot != nullptr, q_dev, n_queries, chunk, sdf_out_dev);
 }
 
 extern "C" int p2s_infer_shape_workers(p2s_model_t m, p2s_cloud_t c, const p2s_worker_streams *ws, int res, int eps, int64_t q_begin,
                                        int64_t q_end, int chunk, float *sdf_out_dev, float *q_out_dev, int64_t *n_done, void *stream) {
-    const LogitsCapture cap(m);
-    if (n_done) *n_done = 0;
+    ModelCall call(m, (hipStream_t)stream, true);
     if (!m || !c || !sdf_out_dev) {
         p2s_set_error("p2s_infer_shape_workers: null argument");
-        return P2S_EINVAL;
+        return call.fail(P2S_EINVAL);
     }
-    int rc = p2s_workers_check(ws, m->cfg.patch_radius > 0.0, "p2s_infer_shape_workers");
-    if (rc || (rc = workers_refuse_small(m, c, ws, "p2s_infer_shape_workers"))) return rc;
-    P2S_HIP_CHECK(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
-    p2s_prof_reset(m);
-    const float *q_all = nullptr;
-    long long Q = 0;
-    const int eg0 = p2s_prof_mark(m, s);
-    if ((rc = p2s_cloud_grid(c, res, eps, &q_all, &Q, s))) return rc;
-    p2s_prof_span(m, ST_GRID, eg0, p2s_prof_mark(m, s));
-    if (q_end < 0) q_end = Q;
-    if (q_begin != 0 || q_end != Q) {
-        p2s_set_error("p2s_infer_shape_workers: query range [%lld,%lld) of a grid of %lld queries: workers mode takes whole shapes "
-                      "(a part would need the stream position of every other part)", (long long)q_begin, (long long)q_end, (long long)Q);
-        return P2S_EINVAL;
-    }
-    if (Q == 0) return P2S_OK;
-    if ((rc = run_workers(m, c, ws, false, q_all, Q, chunk, sdf_out_dev, s, cap))) return rc;
-    if (q_out_dev) {
-        P2S_HIP_CHECK(hipMemcpyAsync(q_out_dev, q_all, (size_t)Q * 12, hipMemcpyDeviceToDevice, s));
-        P2S_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    p2s_prof_collect(m);
-    if (n_done) *n_done = Q;
-    return P2S_OK;
+    int rc = workers_refuse(m, c, ws, m->cfg.patch_radius > 0.0, "p2s_infer_shape_workers");
+    if (rc || (rc = call.rc)) return call.fail(rc);
+    return run_grid(call, c, ws, {}, res, eps, q_begin, q_end, chunk, sdf_out_dev, q_out_dev, n_done, "p2s_infer_shape_workers");
 }
 
 extern "C" int p2s_infer_queries_workers(p2s_model_t m, p2s_cloud_t c, const p2s_worker_streams *ws, int rotate, const float *q_dev,
                                          int64_t n_queries, int chunk, float *sdf_out_dev, void *stream) {
-    const LogitsCapture cap(m);
+    ModelCall call(m, (hipStream_t)stream, true);
     if (!m || !c || n_queries < 0 || (n_queries > 0 && (!q_dev || !sdf_out_dev))) {
         p2s_set_error("p2s_infer_queries_workers: bad argument");
-        return P2S_EINVAL;
+        return call.fail(P2S_EINVAL);
     }
-    int rc = p2s_workers_check(ws, rotate || m->cfg.patch_radius > 0.0, "p2s_infer_queries_workers");
-    if (rc || (rc = workers_refuse_small(m, c, ws, "p2s_infer_queries_workers"))) return rc;
-    P2S_HIP_CHECK(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
-    p2s_prof_reset(m);
-    if (n_queries == 0) return P2S_OK;
-    if ((rc = run_workers(m, c, ws, rotate != 0, q_dev, n_queries, chunk, sdf_out_dev, s, cap))) return rc;
-    p2s_prof_collect(m);
-    return P2S_OK;
+    int rc = workers_refuse(m, c, ws, rotate || m->cfg.patch_radius > 0.0, "p2s_infer_queries_workers");
+    if (rc || (rc = call.rc)) return call.fail(rc);
+    return run_call(call, c, ws, {}, rotate != 0, q_dev, n_queries, chunk, sdf_out_dev);
 }

@@ -1,7 +1,7 @@
 """GPU: the fp16-pair encoder (cfg.encoder_bf16 = 4, BASELINE configs[3]'s fast mode) is safe for an ARBITRARY checkpoint --
 VERDICT r5 item 3.  fp16 ends at 65504; r05 poisoned a query whose activation passed 6e4 and failed the whole call.  Now
 the 16-bit kernels flag such queries, their inputs are put aside per chunk, and at the end of the same call they run
-through the fp32 kernels (p2s_api.hip: p2s_model_fallback_finish); ``counters()['fallback_queries']`` says how many.
+through the fp32 kernels (p2s_api.hip: ModelCall::finish); ``counters()['fallback_queries']`` says how many.
 
 The checkpoints here compute the SAME function as the synthetic p2s_max / p2s_vanilla weights -- one BatchNorm channel is
 scaled by 2^k and the next layer's weights for that channel by 2^-k (ReLU and max-pool are positively homogeneous, powers
@@ -130,6 +130,32 @@ def test_fallback_through_the_model_forward_boundary_and_its_capacity(fixture_cl
     assert torch.equal(lg, lg32[:8])
     m16.close()
     m32.close()
+
+
+def test_a_failed_call_leaves_no_flagged_query_to_the_next(fixture_cloud):
+    """the fallback state belongs to one call: a call that fails after chunks with flagged queries were put aside must not
+    hand them to the next call, which would re-run them and scatter their results to the failed call's positions"""
+    import torch
+    from points2surf_amd import engine, synth, _lib
+    w, cfg = synth.make_weights('p2s_max')
+    w2 = w
+    for c in range(8):                                     # first-layer channels times 2^24: every query leaves the half range
+        w2 = _rescaled(w2, 'first', c, float(2 ** 24))
+    cloud = engine.Cloud(fixture_cloud)
+    fresh, n_fresh = _run(engine, w2, cfg, cloud, 4, chunk=512)
+    assert n_fresh == fresh.shape[0] > 3 * 512
+    m = engine.Model(w2, dict(cfg, encoder_bf16=4))
+    rng = engine.Rng(SEED)
+    mt0, pos0 = rng.get_state()
+    m.debug_fault_chunk(2)                                 # chunks 0 and 1 are collected, then the call fails
+    with pytest.raises(_lib.P2SError, match='injected fault'):
+        engine.infer_shape(m, cloud, rng, 32, 3, chunk=512)
+    rng.set_state(mt0, pos0)
+    sdf, _ = engine.infer_shape(m, cloud, rng, 32, 3, chunk=512)
+    torch.cuda.synchronize()
+    assert int(m.counters()['fallback_queries']) == n_fresh
+    assert np.array_equal(sdf.cpu().numpy(), fresh)
+    m.close()
 
 
 def test_logits_capture_of_the_pipeline(fixture_cloud):
