@@ -354,54 +354,62 @@ _BN_EPS = np.float32(1e-5)
 
 
 def _bn(x, w, prefix, channel_axis):
-    """torch BatchNorm1d in eval mode: (x - mean) / sqrt(var + eps) * gamma + beta."""
+    """torch BatchNorm1d in eval mode: (x - mean) / sqrt(var + eps) * gamma + beta (eps in the dtype of x)."""
     shape = [1] * x.ndim
     shape[channel_axis] = -1
     mean = w[prefix + '.running_mean'].reshape(shape)
     var = w[prefix + '.running_var'].reshape(shape)
     gamma = w[prefix + '.weight'].reshape(shape)
     beta = w[prefix + '.bias'].reshape(shape)
-    return (x - mean) / np.sqrt(var + _BN_EPS) * gamma + beta
+    return (x - mean) / np.sqrt(var + (_BN_EPS if x.dtype == np.float32 else x.dtype.type(1e-5))) * gamma + beta
 
 
-def _conv(x, w, prefix):
+def _mm(x, Wt, rev=False):
+    """x [..., K] @ Wt [K, N]; ``rev``: the K terms in reversed order (another summation order of the same products)"""
+    if rev:
+        return np.ascontiguousarray(x[..., ::-1]) @ np.ascontiguousarray(Wt[::-1])
+    return x @ Wt
+
+
+def _conv(x, w, prefix, rev=False):
     """Conv1d(kernel 1) on x [B, P, Cin] (points-major layout of the reference's [B,Cin,P])."""
     W = w[prefix + '.weight'][:, :, 0]              # [Cout, Cin]
-    return x @ W.T + w[prefix + '.bias']
+    return _mm(x, W.T, rev) + w[prefix + '.bias']
 
 
-def _fc(x, w, prefix):
-    return x @ w[prefix + '.weight'].T + w[prefix + '.bias']
+def _fc(x, w, prefix, rev=False):
+    return _mm(x, w[prefix + '.weight'].T, rev) + w[prefix + '.bias']
 
 
 def _relu(x):
     return np.maximum(x, np.float32(0))
 
 
-def _stn_trunk(x, w, pre):
+def _stn_trunk(x, w, pre, rev=False):
     """shared trunk of STN/QSTN: source/points_to_surf_model.py:41-63 / :100-123."""
-    x = _relu(_bn(_conv(x, w, pre + '.conv1'), w, pre + '.bn1', 2))
-    x = _relu(_bn(_conv(x, w, pre + '.conv2'), w, pre + '.bn2', 2))
-    x = _relu(_bn(_conv(x, w, pre + '.conv3'), w, pre + '.bn3', 2))
+    x = _relu(_bn(_conv(x, w, pre + '.conv1', rev), w, pre + '.bn1', 2))
+    x = _relu(_bn(_conv(x, w, pre + '.conv2', rev), w, pre + '.bn2', 2))
+    x = _relu(_bn(_conv(x, w, pre + '.conv3', rev), w, pre + '.bn3', 2))
     x = x.max(axis=1)                               # MaxPool1d over all points
-    x = _relu(_bn(_fc(x, w, pre + '.fc1'), w, pre + '.bn4', 1))
-    x = _relu(_bn(_fc(x, w, pre + '.fc2'), w, pre + '.bn5', 1))
-    return _fc(x, w, pre + '.fc3')
+    x = _relu(_bn(_fc(x, w, pre + '.fc1', rev), w, pre + '.bn4', 1))
+    x = _relu(_bn(_fc(x, w, pre + '.fc2', rev), w, pre + '.bn5', 1))
+    return _fc(x, w, pre + '.fc3', rev)
 
 
-def stn_forward(x, w, pre, dim):
+def stn_forward(x, w, pre, dim, rev=False):
     """source/points_to_surf_model.py:41-69: returns trans [B, dim, dim]."""
-    t = _stn_trunk(x, w, pre)
+    t = _stn_trunk(x, w, pre, rev)
     t = t + np.eye(dim, dtype=np.float32).reshape(1, dim * dim)
     return t.reshape(-1, dim, dim)
 
 
 def quat_to_rotmat(q):
-    """source/base/utils.py:13-46 ``batch_quat_to_rotmat`` (same index pattern)."""
-    q = q.astype(np.float32)
-    s = np.float32(2) / np.sum(q * q, axis=1)
+    """source/base/utils.py:13-46 ``batch_quat_to_rotmat`` (same index pattern; float32, or float64 for float64 q)."""
+    dt = np.float64 if q.dtype == np.float64 else np.float32
+    q = q.astype(dt)
+    s = dt(2) / np.sum(q * q, axis=1)
     h = q[:, :, None] * q[:, None, :]
-    out = np.empty((q.shape[0], 3, 3), dtype=np.float32)
+    out = np.empty((q.shape[0], 3, 3), dtype=dt)
     out[:, 0, 0] = 1 - (h[:, 2, 2] + h[:, 3, 3]) * s
     out[:, 0, 1] = (h[:, 1, 2] - h[:, 3, 0]) * s
     out[:, 0, 2] = (h[:, 1, 3] + h[:, 2, 0]) * s
@@ -414,45 +422,49 @@ def quat_to_rotmat(q):
     return out
 
 
-def qstn_forward(x, w, pre):
+def qstn_forward(x, w, pre, rev=False):
     """source/points_to_surf_model.py:100-131: returns (R [B,3,3], quat [B,4])."""
-    quat = _stn_trunk(x, w, pre) + np.array([1, 0, 0, 0], dtype=np.float32)
+    quat = _stn_trunk(x, w, pre, rev) + np.array([1, 0, 0, 0], dtype=np.float32)
     return quat_to_rotmat(quat), quat
 
 
-def pointnetfeat_forward(x, w, pre, use_point_stn, use_feat_stn=True, return_aux=False, sym_op='max'):
+def pointnetfeat_forward(x, w, pre, use_point_stn, use_feat_stn=True, return_aux=False, sym_op='max', rev=False):
     """source/points_to_surf_model.py:177-234 (num_scales=1; sym_op 'max' or 'sum', :211-214 -- the STN / QSTN inside
     keep their max-pool whatever sym_op says, :47, :106).
     x: [B, P, 3] (points-major).  Returns feature [B, net_size] (+ trans)."""
     trans = None
     if use_point_stn:
-        trans, _ = qstn_forward(x, w, pre + '.stn1')
+        trans, _ = qstn_forward(x, w, pre + '.stn1', rev)
         x = np.einsum('bij,bpj->bpi', trans, x)      # bmm(trans, x[:, :3, :])
-    x = _relu(_bn(_conv(x, w, pre + '.conv0a'), w, pre + '.bn0a', 2))
-    x = _relu(_bn(_conv(x, w, pre + '.conv0b'), w, pre + '.bn0b', 2))
+    x = _relu(_bn(_conv(x, w, pre + '.conv0a', rev), w, pre + '.bn0a', 2))
+    x = _relu(_bn(_conv(x, w, pre + '.conv0b', rev), w, pre + '.bn0b', 2))
     aux = {}
     if use_feat_stn:
-        trans2 = stn_forward(x, w, pre + '.stn2', 64)
+        trans2 = stn_forward(x, w, pre + '.stn2', 64, rev)
         if return_aux:
             aux['trans2'] = trans2
         x = np.einsum('bij,bpj->bpi', trans2, x)     # bmm(trans2, x)
-    x = _relu(_bn(_conv(x, w, pre + '.conv1'), w, pre + '.bn1', 2))
-    x = _relu(_bn(_conv(x, w, pre + '.conv2'), w, pre + '.bn2', 2))
-    x = _bn(_conv(x, w, pre + '.conv3'), w, pre + '.bn3', 2)     # no ReLU before the pool
-    x = x.max(axis=1) if sym_op == 'max' else x.sum(axis=1, dtype=np.float32)      # torch.sum(x, 2, keepdim=True)
+    x = _relu(_bn(_conv(x, w, pre + '.conv1', rev), w, pre + '.bn1', 2))
+    x = _relu(_bn(_conv(x, w, pre + '.conv2', rev), w, pre + '.bn2', 2))
+    x = _bn(_conv(x, w, pre + '.conv3', rev), w, pre + '.bn3', 2)     # no ReLU before the pool
+    x = x.max(axis=1) if sym_op == 'max' else x.sum(axis=1, dtype=x.dtype)      # torch.sum(x, 2, keepdim=True)
     if return_aux:
         return x, trans, aux
     return x, trans
 
 
-def model_forward(w, cfg, patch_pts_ps, pts_sub_sample_ms, query_ms, chunk=32, return_feats=False):
+def model_forward(w, cfg, patch_pts_ps, pts_sub_sample_ms, query_ms, chunk=32, return_feats=False, dtype=np.float32,
+                  rev=False):
     """source/points_to_surf_model.py:296-352 ``PointsToSurfModel.forward`` (eval mode).
 
     w:   dict name -> float32 ndarray (state_dict without the ``module.`` prefix)
     cfg: dict with use_point_stn, shared_transformer (and use_feat_stn, default True)
     Returns logits [B, output_dim] float32.  Inputs are not modified (the reference
-    translates pts_sub_sample_ms in place, :303)."""
-    w = {k: np.asarray(v, dtype=np.float32) for k, v in w.items()}
+    translates pts_sub_sample_ms in place, :303).
+    dtype: np.float64 runs every operation (weights and inputs rounded to float32 first, as the reference's are) in
+    float64 -- the high-precision oracle of the parity tests.  rev: every matrix product sums its terms in reversed
+    order (another fp32 evaluation of the same function, for the spread of fp32 noise, points2surf_amd/parity.py)."""
+    w = {k: np.asarray(v, dtype=np.float32).astype(dtype) for k, v in w.items()}
     B = patch_pts_ps.shape[0]
     use_point_stn = bool(cfg.get('use_point_stn', False))
     shared = bool(cfg.get('shared_transformer', False))
@@ -462,54 +474,54 @@ def model_forward(w, cfg, patch_pts_ps, pts_sub_sample_ms, query_ms, chunk=32, r
     out = []
     feats = []
     for s in range(0, B, chunk):
-        patch = np.asarray(patch_pts_ps[s:s + chunk], dtype=np.float32)
-        shape = np.asarray(pts_sub_sample_ms[s:s + chunk], dtype=np.float32) \
-            - np.asarray(query_ms[s:s + chunk], dtype=np.float32)[:, None, :]      # :303
+        patch = np.asarray(patch_pts_ps[s:s + chunk], dtype=np.float32).astype(dtype)
+        shape = (np.asarray(pts_sub_sample_ms[s:s + chunk], dtype=np.float32)
+                 - np.asarray(query_ms[s:s + chunk], dtype=np.float32)[:, None, :]).astype(dtype)      # :303
         if single:                                                                # :320-323
             lg, _ = pointnetfeat_forward(np.concatenate([patch, shape], axis=1), w, 'feat_local_global',
-                                         use_point_stn, use_feat_stn, sym_op=sym_op)
-            f = _relu(_bn(_fc(lg, w, 'fc1_local_global'), w, 'bn1_local_global', 1))
-            f = _relu(_bn(_fc(f, w, 'fc2'), w, 'bn2', 1))
-            f = _relu(_bn(_fc(f, w, 'fc3'), w, 'bn3', 1))
-            out.append(_fc(f, w, 'fc4'))
+                                         use_point_stn, use_feat_stn, sym_op=sym_op, rev=rev)
+            f = _relu(_bn(_fc(lg, w, 'fc1_local_global', rev), w, 'bn1_local_global', 1))
+            f = _relu(_bn(_fc(f, w, 'fc2', rev), w, 'bn2', 1))
+            f = _relu(_bn(_fc(f, w, 'fc3', rev), w, 'bn3', 1))
+            out.append(_fc(f, w, 'fc4', rev))
             if return_feats:
                 feats.append((lg, lg))
             continue
         if use_point_stn and shared:                                              # :325-331
             both = np.concatenate([patch, shape], axis=1)
-            trans, _ = qstn_forward(both, w, 'point_stn')
+            trans, _ = qstn_forward(both, w, 'point_stn', rev)
             shape = np.einsum('bij,bpj->bpi', trans, shape)
             patch = np.einsum('bij,bpj->bpi', trans, patch)
         g, trans_g = pointnetfeat_forward(shape, w, 'feat_global',
-                                          use_point_stn and not shared, use_feat_stn, sym_op=sym_op)   # :333
-        gfc = _relu(_bn(_fc(g, w, 'fc1_global'), w, 'bn1_global', 1))                   # :335
+                                          use_point_stn and not shared, use_feat_stn, sym_op=sym_op, rev=rev)   # :333
+        gfc = _relu(_bn(_fc(g, w, 'fc1_global', rev), w, 'bn1_global', 1))              # :335
         if use_point_stn and not shared:                                                # :337-339
             patch = np.einsum('bij,bpj->bpi', trans_g, patch)
-        l, _ = pointnetfeat_forward(patch, w, 'feat_local', False, use_feat_stn, sym_op=sym_op)        # :341
-        lfc = _relu(_bn(_fc(l, w, 'fc1_local'), w, 'bn1_local', 1))                     # :343
+        l, _ = pointnetfeat_forward(patch, w, 'feat_local', False, use_feat_stn, sym_op=sym_op, rev=rev)        # :341
+        lfc = _relu(_bn(_fc(l, w, 'fc1_local', rev), w, 'bn1_local', 1))                # :343
         f = np.concatenate([lfc, gfc], axis=1)                                          # :346
-        f = _relu(_bn(_fc(f, w, 'fc2'), w, 'bn2', 1))
-        f = _relu(_bn(_fc(f, w, 'fc3'), w, 'bn3', 1))
-        out.append(_fc(f, w, 'fc4'))
+        f = _relu(_bn(_fc(f, w, 'fc2', rev), w, 'bn2', 1))
+        f = _relu(_bn(_fc(f, w, 'fc3', rev), w, 'bn3', 1))
+        out.append(_fc(f, w, 'fc4', rev))
         if return_feats:
             feats.append((l, g))
-    logits = np.concatenate(out, axis=0).astype(np.float32)
+    logits = np.concatenate(out, axis=0).astype(dtype)
     if return_feats:
         return logits, np.concatenate([f[0] for f in feats]), np.concatenate([f[1] for f in feats])
     return logits
 
 
-def post_process(logits, patch_radius):
+def post_process(logits, patch_radius, dtype=np.float32):
     """source/points_to_surf_eval.py:184-196 + source/sdf_nn.py:11-21 + :263-273,205-207:
-    sdf = tanh(l0)^2 * r * (l1 >= 0 ? +1 : -1); NaN -> 1.0."""
-    logits = np.asarray(logits, dtype=np.float32)
+    sdf = tanh(l0)^2 * r * (l1 >= 0 ? +1 : -1); NaN -> 1.0.  dtype np.float64: the same in float64."""
+    logits = np.asarray(logits, dtype=dtype)
     if logits.shape[1] == 1:      # outputs = ['imp_surf']: sdf_nn.post_process_distance (sdf_nn.py:6-8), * radius (:176-183)
-        sdf = (np.tanh(logits[:, 0]) ** 2 * np.sign(logits[:, 0]) * np.asarray(patch_radius, dtype=np.float32)).astype(np.float32)
+        sdf = (np.tanh(logits[:, 0]) ** 2 * np.sign(logits[:, 0]) * np.asarray(patch_radius, dtype=dtype)).astype(dtype)
         sdf[np.isnan(sdf)] = 1.0
         return sdf
-    mag = np.tanh(logits[:, 0]) ** 2 * np.asarray(patch_radius, dtype=np.float32)
-    sign = np.where(logits[:, 1] >= 0, np.float32(1), np.float32(-1))
-    sdf = (mag * sign).astype(np.float32)
+    mag = np.tanh(logits[:, 0]) ** 2 * np.asarray(patch_radius, dtype=dtype)
+    sign = np.where(logits[:, 1] >= 0, dtype(1), dtype(-1))
+    sdf = (mag * sign).astype(dtype)
     sdf[np.isnan(sdf)] = 1.0
     return sdf
 

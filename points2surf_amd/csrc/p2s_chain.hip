@@ -421,7 +421,7 @@ __global__ __launch_bounds__(256) void p2s_fold_kernel(FoldArgs args) {
             unsigned short *dst = outh + ((ot * 4 + (kg >> 1)) * 64 + (kg & 1) * 32 + (lane & 31)) * 8 + 4 * kk;
             float x[4] = {acc[4 * g + 0], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
             if (args.f16 && args.bad_items &&
-                !(fabsf(x[0]) <= 6.0e4f && fabsf(x[1]) <= 6.0e4f && fabsf(x[2]) <= 6.0e4f && fabsf(x[3]) <= 6.0e4f))
+                (p2s_f16_out_of_range(x[0]) || p2s_f16_out_of_range(x[1]) || p2s_f16_out_of_range(x[2]) || p2s_f16_out_of_range(x[3])))
                 args.bad_items[item] = 1;          // this item's folded weights leave the half range: its query re-runs in fp32
             for (int q = 0; q < args.ns; ++q) {
                 unsigned short h[4];

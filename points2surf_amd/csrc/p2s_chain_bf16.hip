@@ -20,14 +20,20 @@
 // at 1/16 of the fp32 MFMA cost per piece product.  Arithmetic model + measured deviation: DESIGN.md "bf16 modes".
 //
 // fp16 pair mode (template parameter F16; cfg.encoder_bf16 = 4, "fp16x2"): every operand as TWO fp16 numbers,
-//   x = h0 + h1 * 2^-11,   h0 = fp16(x),   h1 = fp16((x - h0) * 2^11)     (22 mantissa bits; the residual is scaled so
-// that it never goes subnormal), and a product = h0 h0' into one fp32 accumulator, (h0 h1' + h1 h0') into a second one
-// that enters with the factor 2^-11 at the end -- THREE v_mfma_f32_32x32x16_f16 per product instead of the six bf16
-// ones of the three-piece mode, for the same deviation from fp32 (relative feature error 5e-7 vs 4e-7 in the CPU model;
-// two bf16 pieces: 1.3e-5).  fp16 ends at 65504: an activation beyond 6e4 poisons its item (NaN) AND flags the item's
-// query (ChainArgs.bad_items); flagged queries are collected per chunk and re-run through the fp32 kernels at the end of
-// the same call (p2s_api.hip: fallback) -- an arbitrary checkpoint cannot turn this mode into wrong values or an error
-// (the reference's activations stay below 20 with the weights at hand: nothing is ever flagged there).
+//   x = h0 + h1 * 2^-11,   h0 = fp16(x),   h1 = fp16((x - h0) * 2^11)     (22 mantissa bits while |x| >= 2^-14, fp16's
+// normal range; below it h0 and then h1 go subnormal and the pair keeps an ABSOLUTE error of ~2^-36 instead), and a
+// product = h0 h0' into one fp32 accumulator, (h0 h1' + h1 h0') into a second one that enters with the factor 2^-11 at the
+// end -- THREE v_mfma_f32_32x32x16_f16 per product instead of the six bf16 ones of the three-piece mode, for the same
+// deviation from fp32 (relative feature error 5e-7 vs 4e-7 in the CPU model; two bf16 pieces: 1.3e-5).
+// Both ends of the fp16 range are guarded.  High end (65504): an activation beyond 6e4 poisons its item (NaN) AND flags the
+// item's query (ChainArgs.bad_items); flagged queries are collected per chunk and re-run through the fp32 kernels at the end
+// of the same call (p2s_api.hip: fallback); a folded WEIGHT beyond 6e4 refuses the mode at model creation.  NaN / inf are
+// not flagged (p2s_f16_out_of_range): they poison the item as in the fp32 mode.  Low end: a channel whose producer weights
+// are tiny next to its consumer weights (a BN that shrinks a channel that the next layer grows again) would carry its
+// activations in the subnormal range; the weight blob of this mode is rebalanced by exact powers of two at model creation
+// (points2surf_amd/weights.py: _balance), which puts such channels back in the normal range without changing the function.
+// What that does not reach -- single tiny weights next to large ones of the same column, the pooled conv3 features of the
+// main trunk, conv0b's output -- keeps the absolute error floor (DESIGN.md "bf16 modes").
 #include "p2s_common.h"
 #include <cmath>
 
@@ -117,7 +123,7 @@ __device__ __forceinline__ void split_pair(float a, float b, unsigned (&out)[NS]
     }
 }
 
-constexpr float F16_LIMIT = 6.0e4f;       // |activation| beyond this does not fit fp16 (max 65504)
+constexpr float F16_LIMIT = 6.0e4f;       // |weight| beyond this does not fit fp16 (max 65504); activations: p2s_f16_out_of_range
 constexpr float F16_SCALE = 1.0f / 2048.0f;
 
 // Small layers run TRANSPOSED: D = W^T X^T, the weight fragment is the MFMA's first operand and the activation fragment the
@@ -140,7 +146,7 @@ __device__ __forceinline__ void store_tile(const f32x16 (&acc)[F16 ? 2 : 1], uns
             v[t] = acc[0][4 * g + t];
             if (F16) v[t] = fmaf(acc[F16 ? 1 : 0][4 * g + t], F16_SCALE, v[t]);
             v[t] = fmaxf(v[t] + b[t], 0.0f);
-            if (F16) range_bad = range_bad || !(v[t] <= F16_LIMIT);       // (NaN too: an operand beyond the range made inf * 0)
+            if (F16) range_bad = range_bad || p2s_f16_out_of_range(v[t]);
         }
         unsigned lo[NS], hi[NS];
         split_pair<NS, F16>(v[0], v[1], lo);
@@ -253,7 +259,7 @@ __global__ __launch_bounds__(256, F16 ? P2S_F16_WG : ((MT == 64 && NS == 1) ? (S
                     v = fmaf(w0a[128 + o], x2, v);
                     sv[u] = fmaxf(v, 0.0f);
                 }
-                if (F16) range_bad = range_bad || !(sv[0] <= F16_LIMIT) || !(sv[1] <= F16_LIMIT);
+                if (F16) range_bad = range_bad || p2s_f16_out_of_range(sv[0]) || p2s_f16_out_of_range(sv[1]);
                 unsigned u[NS];
                 split_pair<NS, F16>(sv[0], sv[1], u);
 #pragma unroll

@@ -9,6 +9,14 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// fp16 pair mode (cfg.encoder_bf16 = 4): a FINITE value beyond the half range flags its query for the fp32 re-run.  NaN and
+// inf are not flagged: they are non-finite in fp32 as well, so they take the poison path of every other mode (NaN -> SDF 1)
+// instead of filling the fallback's side buffers with queries the fp32 kernels cannot repair.
+__device__ __forceinline__ bool p2s_f16_out_of_range(float v) {
+    const float a = fabsf(v);
+    return a > 6.0e4f && a <= 3.4028235e38f;
+}
+
 void p2s_set_error(const char *fmt, ...);
 // Process-wide grow-only scratch buffer per device (volume / iso-surface stages: ~0.5 ms of hipMalloc + hipFree per
 // call otherwise).  A caller holds the lock for its whole call -- host threads serialise per device -- and synchronises

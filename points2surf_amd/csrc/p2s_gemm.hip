@@ -174,7 +174,8 @@ __global__ __launch_bounds__(256) void p2s_gemm_f16_kernel(GemmArgs g) {
             const int r = (tid >> 5) + 8 * i;
             const f32x4 v = stage[i];
             // a row with an activation beyond the half range: its query goes through the fp32 kernels again (fallback)
-            if (g.bad_rows && !(fabsf(v[0]) <= 6.0e4f && fabsf(v[1]) <= 6.0e4f && fabsf(v[2]) <= 6.0e4f && fabsf(v[3]) <= 6.0e4f))
+            if (g.bad_rows && (p2s_f16_out_of_range(v[0]) || p2s_f16_out_of_range(v[1]) || p2s_f16_out_of_range(v[2]) ||
+                               p2s_f16_out_of_range(v[3])))
                 g.bad_rows[min(m0 + r, g.M - 1)] = 1;
             uint2 h0, h1;
             h0.x = pack_h2(v[0], v[1]);

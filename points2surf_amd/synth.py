@@ -30,8 +30,65 @@ _FC4_BIAS_SHIFT = {'p2s_max': (6.289174, 2.416443), 'p2s_vanilla': (2.6854432, 4
 _SIGN_BIAS_EXTRA = {'p2s_vanilla_mixed': ('p2s_vanilla', 1.30)}
 
 
+# Adversarial derived sets (parity tests of the regimes the default sets never reach): the weights of the base set with
+#  * every BatchNorm: gamma of both signs (40 % negative), 5 % of the channels with |gamma| in [1e-6, 1e-3], two channels
+#    with gamma exactly 0; running_var log-uniform in [1e-6, 10] and |gamma| = g * sqrt(var + eps), g in U(0.5, 1.5), for
+#    the others, so that the folded scale gamma / sqrt(var + eps) stays O(1) and activations do not grow layer by layer;
+#  * the STN / QSTN fc3 redrawn without the near-identity scaling (||trans2 - I|| of order 10, quaternions far from
+#    [1,0,0,0]); the QSTN fc3 bias moved by ``qstn_shift`` so that some queries of the test shape have sum(q^2) in
+#    [0.05, 0.3] (the normalisation s = 2 / sum(q^2) of batch_quat_to_rotmat, reference source/base/utils.py:13-46);
+#  * two all-zero rows in every per-point conv of the encoders;
+#  * fc4 scaled by ``fc4_scale`` and its bias moved by ``fc4_shift`` (measured on the abc_minimal test shape with
+#    oracle/p2s_oracle.py) so that both logits take both signs and tanh^2 is not saturated for most queries.
+# name -> (base set, seed of the perturbation, qstn_shift, fc4_scale, fc4_shift); statistics: tests/golden/meta_stress.json
+_STRESS = {'p2s_max_stress': ('p2s_max', 9001, None, 0.1, (-6.151, -6.783)),
+           'p2s_vanilla_stress': ('p2s_vanilla', 9002, (-1.3, 0.35, -1.14, 1.42), 0.1, (-1.045, -1.576))}
+STRESS_MODELS = tuple(sorted(_STRESS))
+
+
+def _stress(w, seed, qstn_shift, fc4_scale, fc4_shift):
+    rng = np.random.default_rng(seed)
+    w = {k: v.copy() for k, v in w.items()}
+    eps = 1e-5
+    for name in sorted(w):
+        pre, leaf = name.rsplit('.', 1)
+        if not (pre.rsplit('.', 1)[-1].startswith('bn') and leaf == 'weight'):
+            continue
+        c = w[name].shape[0]
+        var = 10.0 ** rng.uniform(-6.0, 1.0, c)
+        g = rng.uniform(0.5, 1.5, c) * np.sqrt(var + eps)
+        tiny = rng.random(c) < 0.05
+        g[tiny] = 10.0 ** rng.uniform(-6.0, -3.0, int(tiny.sum()))
+        g *= np.where(rng.random(c) < 0.4, -1.0, 1.0)
+        g[rng.choice(c, 2, replace=False)] = 0.0
+        w[name] = g.astype(np.float32)
+        w[pre + '.running_var'] = var.astype(np.float32)
+    for name in sorted(w):
+        pre, leaf = name.rsplit('.', 1)
+        layer = pre.rsplit('.', 1)[-1]
+        if pre.endswith('stn2.fc3') or pre.endswith('stn1.fc3') or pre.startswith('point_stn.fc3'):
+            a = np.sqrt(6.0 / w[pre + '.weight'].shape[1])
+            w[name] = rng.uniform(-a if leaf == 'weight' else -0.1, a if leaf == 'weight' else 0.1,
+                                  w[name].shape).astype(np.float32)
+        elif leaf == 'weight' and layer in ('conv1', 'conv2', 'conv3') and '.stn' not in pre and pre.startswith('feat_'):
+            W = w[name].copy()
+            W[rng.choice(W.shape[0], 2, replace=False)] = 0.0
+            w[name] = W
+    if qstn_shift is not None:
+        for name in sorted(w):
+            if name.endswith('stn1.fc3.bias') or name == 'point_stn.fc3.bias':
+                w[name] = (w[name] + np.asarray(qstn_shift, dtype=np.float32)).astype(np.float32)
+    w['fc4.weight'] = (w['fc4.weight'] * np.float32(fc4_scale)).astype(np.float32)
+    w['fc4.bias'] = (w['fc4.bias'] + np.asarray(fc4_shift, dtype=np.float32)).astype(np.float32)
+    return w
+
+
 def make_weights(model='p2s_max', seed=1234, net_size_max=1024, output_dim=None):
     """Returns ({name: float32 ndarray} without ``module.`` prefix, cfg dict)."""
+    if isinstance(model, str) and model in _STRESS:
+        base, sseed, qshift, fscale, fshift = _STRESS[model]
+        w, cfg_out = make_weights(base, seed=seed, net_size_max=net_size_max, output_dim=output_dim)
+        return _stress(w, sseed, qshift, fscale, fshift), cfg_out
     if isinstance(model, str) and model in _SIGN_BIAS_EXTRA:
         base, extra = _SIGN_BIAS_EXTRA[model]
         w, cfg_out = make_weights(base, seed=seed, net_size_max=net_size_max, output_dim=output_dim)

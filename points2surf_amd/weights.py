@@ -9,6 +9,9 @@
   k-permutation the kernels use:  packed[n/32][k/8][lane][t] = W[k = 8*(k/8) + 4*(lane>>5) + t][n = 32*(n/32) + (lane&31)]
 * the STN identity (``x + eye(64)``, :66-67) and the QSTN identity quaternion (:125-126) are
   folded into the fc3 bias.
+* fp16 pair encoder (cfg encoder_bf16 = 4) only: exact power-of-two rebalancing of every ReLU boundary inside the
+  encoders (``_balance``), so that no channel whose producer weights are tiny next to its consumer weights sinks below
+  fp16's normal range.
 """
 import ctypes
 
@@ -106,19 +109,68 @@ class _Blob:
         return np.concatenate(self.parts) if self.parts else np.zeros(0, np.float32)
 
 
-def _add_gemm(blob, w, lin, bn, extra_bias=None):
-    W, b = fold_affine(w, lin, bn)
+def _add_gemm(blob, w, lin, bn, extra_bias=None, folded=None):
+    W, b = folded[lin] if folded is not None and lin in folded else fold_affine(w, lin, bn)
     if extra_bias is not None:
         b = b + extra_bias
     return blob.add(pack_b(W.T)), blob.add(b)
 
 
-def _add_plain(blob, w, lin, bn, extra_bias=None):
+def _add_plain(blob, w, lin, bn, extra_bias=None, folded=None):
     """small layers kept as plain [K][N] (first K=3 conv, fc4, QSTN fc3)."""
-    W, b = fold_affine(w, lin, bn)
+    W, b = folded[lin] if folded is not None and lin in folded else fold_affine(w, lin, bn)
     if extra_bias is not None:
         b = b + extra_bias
     return blob.add(W.T), blob.add(b)
+
+
+# Chains of (layer, its BN) inside a PointNetfeat / STN / QSTN trunk with a ReLU between neighbours whose channels may be
+# rescaled: relu(s * y) = s * relu(y) and max(s * y) = s * max(y) for s > 0, so producer row c and bias c times 2^e with
+# consumer column c times 2^-e compute the same function.  Not across conv0b -> conv1 (conv0b's output also meets trans2 in
+# W1' = W1 . trans2) and not past the pooled conv3 feature of the main trunk (no ReLU; it is an output of the encoder).
+_TRUNK_CHAINS = ((('conv1', 'bn1'), ('conv2', 'bn2'), ('conv3', 'bn3'), ('fc1', 'bn4'), ('fc2', 'bn5'), ('fc3', None)),)
+_FEAT_CHAINS = ((('conv0a', 'bn0a'), ('conv0b', 'bn0b')), (('conv1', 'bn1'), ('conv2', 'bn2'), ('conv3', 'bn3')))
+
+
+BALANCE_MIN_EXP = 4
+BALANCE_BELOW = 2.0 ** -6
+
+
+def _balance(Wp, bp, Wc):
+    """Exact power-of-two rebalancing of one ReLU boundary for the fp16 pair encoder (fp16 is normal from 2^-14 on; below,
+    an fp16 pair x = h0 + h1 2^-11 keeps an absolute error of ~2^-36 instead of 22 bits): producer rows Wp [C, K] + bias
+    bp [C], consumer columns Wc [N, C] (float64, in place).  A channel whose consumer column is larger than its producer row
+    (max |.|) gets 2^e with e = round(log2(consumer / producer) / 2) on the producer side, 2^-e on the consumer side, where
+    e >= BALANCE_MIN_EXP, i.e. consumer / producer >= 2^7 (channels closer to balance keep their weights -- in the default
+    synthetic sets: all of them), and only where the producer row itself is small (max |.| < BALANCE_BELOW): a producer
+    of normal size next to a consumer column that is large through ONE entry (a consumer row that is itself huge) would
+    otherwise push the column's other entries toward the subnormal range:
+    a checkpoint whose BN shrinks a channel by 2^-k and whose next layer grows it by 2^k (the same function) gets its
+    balance back.  Never the other way round: a channel that is large on the producer side stays as large (activations
+    beyond the half range are the fp32 fallback's, p2s_api.hip).  Powers of two are exact: the fp32 kernels compute the
+    same values from the rebalanced weights."""
+    mp = np.maximum(np.abs(Wp).max(axis=1), np.abs(bp))
+    mc = np.abs(Wc).max(axis=0)
+    e = np.zeros(mp.shape, np.float64)
+    ok = (mp > 0) & (mp < BALANCE_BELOW) & (mc > 0)
+    e[ok] = np.clip(np.floor(0.5 * np.log2(mc[ok] / mp[ok]) + 0.5), 0, 60)
+    e[e < BALANCE_MIN_EXP] = 0
+    s = np.exp2(e)
+    Wp *= s[:, None]
+    bp *= s
+    Wc /= s[None, :]
+
+
+def _fold_balanced(w, pre, chains):
+    """{layer name: (W, b)} of the layers of ``chains`` under ``pre``, folded and rebalanced (fp16 pair encoder)"""
+    out = {}
+    for chain in chains:
+        for lin, bn in chain:
+            out[pre + '.' + lin] = fold_affine(w, pre + '.' + lin, pre + '.' + bn if bn else None)
+        for (lp, _), (lc, _) in zip(chain, chain[1:]):
+            Wp, bp = out[pre + '.' + lp]
+            _balance(Wp, bp, out[pre + '.' + lc][0])
+    return out
 
 
 def build_blob(state_dict, cfg):
@@ -152,46 +204,62 @@ def build_blob(state_dict, cfg):
     if sym_op not in ('max', 'sum'):
         raise ValueError("Unsupported symmetric operation: %s" % sym_op)        # reference points_to_surf_model.py:175
 
+    encoders = ('feat_local_global',) if single else ('feat_local', 'feat_global')
+    qstn = 'feat_local_global.stn1' if single else ('point_stn' if shared else 'feat_global.stn1')
+    folded = {}
+    if int(cfg.get('encoder_bf16', 0) or 0) == 4:
+        for pre in encoders:
+            folded.update(_fold_balanced(w, pre, _FEAT_CHAINS))
+            folded.update(_fold_balanced(w, pre + '.stn2', _TRUNK_CHAINS))
+        if use_point_stn:
+            folded.update(_fold_balanced(w, qstn, _TRUNK_CHAINS))
+
+    def gemm(*a, **k):
+        return _add_gemm(*a, folded=folded, **k)
+
+    def plain(*a, **k):
+        return _add_plain(*a, folded=folded, **k)
+
     blob = _Blob()
     offs = WeightOffsets()
     # single_transformer: ONE encoder over cat(patch, sub-sample); the engine runs it as its usual two branches
     # (patch points / sub-sample points) with the same weights and takes the max of the two pools
     for e, pre in enumerate(('feat_local_global', 'feat_local_global') if single else ('feat_local', 'feat_global')):
         o = offs.enc[e]
-        o.w0a, o.b0a = _add_plain(blob, w, pre + '.conv0a', pre + '.bn0a')
-        o.w0b, o.b0b = _add_gemm(blob, w, pre + '.conv0b', pre + '.bn0b')
+        o.w0a, o.b0a = plain(blob, w, pre + '.conv0a', pre + '.bn0a')
+        o.w0b, o.b0b = gemm(blob, w, pre + '.conv0b', pre + '.bn0b')
         s = pre + '.stn2'
-        o.s1, o.sb1 = _add_gemm(blob, w, s + '.conv1', s + '.bn1')
-        o.s2, o.sb2 = _add_gemm(blob, w, s + '.conv2', s + '.bn2')
-        o.s3, o.sb3 = _add_gemm(blob, w, s + '.conv3', s + '.bn3')
-        o.sf1, o.sfb1 = _add_gemm(blob, w, s + '.fc1', s + '.bn4')
-        o.sf2, o.sfb2 = _add_gemm(blob, w, s + '.fc2', s + '.bn5')
-        o.sf3, o.sfb3 = _add_gemm(blob, w, s + '.fc3', None, extra_bias=np.eye(64).reshape(-1))
-        o.m1t, o.mb1 = _add_gemm(blob, w, pre + '.conv1', pre + '.bn1')
-        o.m2, o.mb2 = _add_gemm(blob, w, pre + '.conv2', pre + '.bn2')
-        o.m3, o.mb3 = _add_gemm(blob, w, pre + '.conv3', pre + '.bn3')
+        o.s1, o.sb1 = gemm(blob, w, s + '.conv1', s + '.bn1')
+        o.s2, o.sb2 = gemm(blob, w, s + '.conv2', s + '.bn2')
+        o.s3, o.sb3 = gemm(blob, w, s + '.conv3', s + '.bn3')
+        o.sf1, o.sfb1 = gemm(blob, w, s + '.fc1', s + '.bn4')
+        o.sf2, o.sfb2 = gemm(blob, w, s + '.fc2', s + '.bn5')
+        o.sf3, o.sfb3 = gemm(blob, w, s + '.fc3', None, extra_bias=np.eye(64).reshape(-1))
+        o.m1t, o.mb1 = gemm(blob, w, pre + '.conv1', pre + '.bn1')
+        o.m2, o.mb2 = gemm(blob, w, pre + '.conv2', pre + '.bn2')
+        o.m3, o.mb3 = gemm(blob, w, pre + '.conv3', pre + '.bn3')
     if use_point_stn:
         q = offs.qstn
         # shared: one QSTN over cat(patch, sub-sample) (model.point_stn); otherwise the QSTN of feat_global, which
         # sees the sub-sample only (reference source/points_to_surf_model.py:267-269, :283-284)
-        s = 'feat_local_global.stn1' if single else ('point_stn' if shared else 'feat_global.stn1')
-        q.c1, q.cb1 = _add_plain(blob, w, s + '.conv1', s + '.bn1')
-        q.c2, q.cb2 = _add_gemm(blob, w, s + '.conv2', s + '.bn2')
-        q.c3, q.cb3 = _add_gemm(blob, w, s + '.conv3', s + '.bn3')
-        q.f1, q.fb1 = _add_gemm(blob, w, s + '.fc1', s + '.bn4')
-        q.f2, q.fb2 = _add_gemm(blob, w, s + '.fc2', s + '.bn5')
-        q.f3, q.fb3 = _add_plain(blob, w, s + '.fc3', None, extra_bias=np.array([1.0, 0, 0, 0]))
+        s = qstn
+        q.c1, q.cb1 = plain(blob, w, s + '.conv1', s + '.bn1')
+        q.c2, q.cb2 = gemm(blob, w, s + '.conv2', s + '.bn2')
+        q.c3, q.cb3 = gemm(blob, w, s + '.conv3', s + '.bn3')
+        q.f1, q.fb1 = gemm(blob, w, s + '.fc1', s + '.bn4')
+        q.f2, q.fb2 = gemm(blob, w, s + '.fc2', s + '.bn5')
+        q.f3, q.fb3 = plain(blob, w, s + '.fc3', None, extra_bias=np.array([1.0, 0, 0, 0]))
     if single:
         # fc1_local_global 1024 -> 1024 as two 512-column halves: the decoder's two fc1 GEMMs read the same feature
         W1, b1 = fold_affine(w, 'fc1_local_global', 'bn1_local_global')
         offs.d1l, offs.db1l = blob.add(pack_b(W1[:512].T)), blob.add(b1[:512])
         offs.d1g, offs.db1g = blob.add(pack_b(W1[512:].T)), blob.add(b1[512:])
     else:
-        offs.d1l, offs.db1l = _add_gemm(blob, w, 'fc1_local', 'bn1_local')
-        offs.d1g, offs.db1g = _add_gemm(blob, w, 'fc1_global', 'bn1_global')
-    offs.d2, offs.db2 = _add_gemm(blob, w, 'fc2', 'bn2')
-    offs.d3, offs.db3 = _add_gemm(blob, w, 'fc3', 'bn3')
-    offs.d4, offs.db4 = _add_plain(blob, w, 'fc4', None)
+        offs.d1l, offs.db1l = gemm(blob, w, 'fc1_local', 'bn1_local')
+        offs.d1g, offs.db1g = gemm(blob, w, 'fc1_global', 'bn1_global')
+    offs.d2, offs.db2 = gemm(blob, w, 'fc2', 'bn2')
+    offs.d3, offs.db3 = gemm(blob, w, 'fc3', 'bn3')
+    offs.d4, offs.db4 = plain(blob, w, 'fc4', None)
 
     mc = ModelCfg()
     mc.net_size = n

@@ -205,3 +205,92 @@ def test_fallback_in_the_gt_query_pass_with_rotations(fixture_cloud):
     assert out[0][1] == 0 and out[4][1] > 100
     same = int((out[4][0] == out[0][0]).sum())
     assert same >= out[4][1] and float(np.abs(out[4][0] - out[0][0]).max()) < 1e-4
+
+
+_LOW = {}
+
+
+def _low_base(engine, model, cloud):
+    """mode 0 and mode 4 on the unscaled weights: SDF + logits of the grid-32 queries"""
+    if model not in _LOW:
+        from points2surf_amd import synth
+        w, cfg = synth.make_weights(model)
+        out = {}
+        for enc in (0, 4):
+            m = engine.Model(w, dict(cfg, encoder_bf16=enc))
+            sdf, _, lg = engine.infer_shape(m, cloud, engine.Rng(SEED), 32, 3, want_logits=True)
+            out[enc] = (sdf.cpu().numpy(), lg.cpu().numpy())
+            m.close()
+        _LOW[model] = (w, cfg, out)
+    return _LOW[model]
+
+
+@pytest.mark.parametrize('k', [8, 16, 24])
+@pytest.mark.parametrize('model,site', [('p2s_max', 'chain'), ('p2s_max', 'first'), ('p2s_max', 'heads'),
+                                        ('p2s_vanilla', 'chain')])
+def test_channels_scaled_below_the_normal_range(model, site, k, fixture_cloud, golden_dir):
+    """the fp16-pair low end: one channel times 2^-k, the next layer's weights for it times 2^k -- the SAME function as the
+    unscaled weights, but without the rebalancing of the fp16 pair mode's weights (points2surf_amd/weights.py: _balance)
+    that channel's activations or weights sit below fp16's normal range (2^-14), where an fp16 pair keeps only an absolute
+    error of ~2^-36.  Mode 4 must hold what it holds on the unscaled weights: SDF within 1e-4 of mode 0 and the golden,
+    flips only as ties, and a logit deviation from mode 0 at most twice that of the unscaled checkpoint."""
+    import torch
+    from points2surf_amd import engine, parity
+    cloud = engine.Cloud(fixture_cloud)
+    w, cfg, base = _low_base(engine, model, cloud)
+    sdf0, lg0 = base[0]
+    d_base = float(np.abs(base[4][1] - lg0).max())
+    m = engine.Model(_rescaled(w, site, 0, float(2.0 ** -k)), dict(cfg, encoder_bf16=4))
+    sdf, _, lg = engine.infer_shape(m, cloud, engine.Rng(SEED), 32, 3, want_logits=True)
+    torch.cuda.synchronize()
+    sdf, lg = sdf.cpu().numpy(), lg.cpu().numpy()
+    n_fb = int(m.counters()['fallback_queries'])
+    m.close()
+    d = float(np.abs(lg - lg0).max())
+    c0 = parity.compare_sdf(sdf, sdf0)
+    g = np.load(os.path.join(golden_dir, 'ref_%s_grid32.npz' % model))['sdf_full']
+    cg = parity.compare_sdf(sdf, g)
+    print('%s / %s x 2^-%d: max|dlogit| vs mode 0 %.3g (unscaled %.3g), max|dSDF| vs mode 0 %.3g, vs golden %.3g, flips %d / %d, '
+          'fallback_queries %d' % (model, site, k, d, d_base, c0['max_abs_dsdf'], cg['max_abs_dsdf'], c0['flipped'].size,
+                                   cg['flipped'].size, n_fb))
+    assert n_fb == 0
+    assert d <= 2.0 * d_base
+    assert c0['max_abs_dsdf'] < 1e-4 and cg['max_abs_dsdf'] < 1e-4
+    for i in np.concatenate([c0['flipped'], cg['flipped']]):
+        assert parity.is_tie(lg[i, 1], lg0[i, 1], encoder_bf16=4), (int(i), lg[i], lg0[i])
+
+
+def test_non_finite_queries_poison_like_the_fp32_mode(fixture_cloud):
+    """NaN / inf query points in the fp16 pair mode take the poison path of the other modes (SDF 1.0 for NaN logits, no
+    error); they are not flagged for the fp32 re-run -- also past the 16384 queries the re-run takes per call (through
+    Model.forward, the stage-wise boundary: the inputs of the finite queries come from the device's kNN / sub-sample)"""
+    import torch
+    from points2surf_amd import engine, synth
+    w, cfg = synth.make_weights('p2s_max')
+    cloud = engine.Cloud(fixture_cloud)
+    q = cloud.query_grid(32, 3)[:300].contiguous()
+    _, sub = engine.Rng(SEED).subsample_uniform(cloud, 300, 1000)
+    _, patch, rad = cloud.knn_patch(q, 300, want_ids=False)
+    nb = 17000
+    idx = torch.arange(nb, device='cuda') % 300
+    bad = torch.full((nb, 3), float('nan'), device='cuda')
+    bad[::7, 1] = float('inf')
+    bad[1::7, 1] = -float('inf')
+    qs = torch.cat([q, bad])
+    ps = torch.cat([patch, patch[idx]]).contiguous()
+    ss = torch.cat([sub, sub[idx]]).contiguous()
+    rs = torch.cat([rad, rad[idx]]).contiguous()
+    out = {}
+    for enc in (0, 3, 4):
+        m = engine.Model(w, dict(cfg, encoder_bf16=enc))
+        lg, sdf = m.forward(ps, ss, qs, rs, want_sdf=True)
+        torch.cuda.synchronize()
+        out[enc] = (lg.cpu().numpy(), sdf.cpu().numpy(), int(m.counters()['fallback_queries']))
+        m.close()
+    for enc in (0, 3, 4):
+        lg, sdf, n_fb = out[enc]
+        print('mode %d: non-finite queries -> SDF %s, fallback_queries %d' % (enc, np.unique(sdf[300:]), n_fb))
+        assert n_fb == 0
+        assert np.all(sdf[300:] == 1.0) and np.array_equal(sdf[300:], out[0][1][300:])
+        assert np.array_equal(np.isnan(lg[300:]), np.isnan(out[0][0][300:]))
+        assert float(np.abs(sdf[:300] - out[0][1][:300]).max()) < 1e-4
