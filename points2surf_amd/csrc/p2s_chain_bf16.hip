@@ -27,7 +27,7 @@
 // deviation from fp32 (relative feature error 5e-7 vs 4e-7 in the CPU model; two bf16 pieces: 1.3e-5).
 // Both ends of the fp16 range are guarded.  High end (65504): an activation beyond 6e4 poisons its item (NaN) AND flags the
 // item's query (ChainArgs.bad_items); flagged queries are collected per chunk and re-run through the fp32 kernels at the end
-// of the same call (p2s_api.hip: fallback); a folded WEIGHT beyond 6e4 refuses the mode at model creation.  NaN / inf are
+// of the same call (p2s_forward.hip: fallback); a folded WEIGHT beyond 6e4 refuses the mode at model creation.  NaN / inf are
 // not flagged (p2s_f16_out_of_range): they poison the item as in the fp32 mode.  Low end: a channel whose producer weights
 // are tiny next to its consumer weights (a BN that shrinks a channel that the next layer grows again) would carry its
 // activations in the subnormal range; the weight blob of this mode is rebalanced by exact powers of two at model creation

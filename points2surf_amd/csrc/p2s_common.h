@@ -83,7 +83,7 @@ struct ChainArgs {
     long long piece_stride, w1_piece_stride;
     int f16;                 // 1: the pieces are an fp16 pair (h0, h1 * 2^11) with two accumulators (ns = 2)
     int *bad_items;          // fp16 pair mode: [items per branch] flag of every item (= query of the chunk) an activation of
-                             // which left the half range -- the query is re-run through the fp32 kernels (p2s_api.hip: fallback)
+                             // which left the half range -- the query is re-run through the fp32 kernels (p2s_forward.hip: fallback)
 };
 int p2s_launch_chain(const ChainArgs &args, hipStream_t stream);
 // bf16 variant (p2s_chain_bf16.hip): w0b / w1 / w2 / w3 point to bf16 fragment arrays, w1_item_stride counts halfs

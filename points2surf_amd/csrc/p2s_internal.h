@@ -2,6 +2,7 @@
 #pragma once
 #include "p2s_common.h"
 #include <vector>
+#include <cstddef>
 
 // per-shape pipeline buffers (p2s_pipeline.hip): owned by the model handle, grown on demand, reused across
 // shapes, released by p2s_model_destroy -- no allocation and no leak on the per-shape path
@@ -22,19 +23,63 @@ struct PipeBuffers {
     int cap_chunk = 0, cap_k = 0, cap_n = 0, cap_small = 0;
 };
 
+// Precision of one run of the network.  cfg.encoder_bf16: 0 fp32, 1 bf16, 2 / 3 split bf16, 4 fp16 pair (2 pieces, two
+// accumulators; the encoder-side head layers on 16-bit fragments too, queries beyond the half range flagged and collected)
+struct Precision {
+    int pieces;              // 16-bit pieces per operand of the per-point layers; 0: the fp32 kernels
+    bool f16;                // the pieces are an fp16 pair
+};
+constexpr Precision P2S_FP32 = {0, false};
+inline Precision p2s_precision(const p2s_model_cfg &c) { return {c.encoder_bf16 == 4 ? 2 : c.encoder_bf16, c.encoder_bf16 == 4}; }
+
+// The FC / per-point layers whose weights are packed MFMA B fragments, each named once: where p2s_weight_offsets holds the
+// offsets of its fp32 fragments and of its bias (slice 1 -- the second encoder, fc1_global -- `slice` bytes further), its
+// shape, and when it has 16-bit fragments in blob_h as well.  The kinds are the groups of blob_h, in its order.
+enum P2sLayerKind {
+    LK_ENC,                  // per-point layers of both encoders: any 16-bit precision, encoder by encoder
+    LK_QSTN,                 // per-point layers of the QSTN: any 16-bit precision, models with use_point_stn
+    LK_ENC_HEAD,             // STN fc1..fc3 of both encoders: fp16 pair, encoder by encoder
+    LK_QSTN_HEAD,            // QSTN fc1 / fc2: fp16 pair, models with use_point_stn
+    LK_FP32                  // decoder: fp32 only
+};
+enum P2sLayer { L_W0B, L_S1, L_S2, L_S3, L_M2, L_M3, L_QC2, L_QC3, L_SF1, L_SF2, L_SF3, L_QF1, L_QF2, L_D1, L_D2, L_D3, P2S_LAYERS };
+struct P2sLayerDesc { P2sLayerKind kind; size_t w, b, slice; int K, N; };
+#define P2S_AT(w, b) offsetof(p2s_weight_offsets, w), offsetof(p2s_weight_offsets, b)
+constexpr size_t P2S_PER_ENC = sizeof(p2s_encoder_offsets);
+inline constexpr P2sLayerDesc p2s_layers[P2S_LAYERS] = {
+    {LK_ENC, P2S_AT(enc[0].w0b, enc[0].b0b), P2S_PER_ENC, 64, 64},         {LK_ENC, P2S_AT(enc[0].s1, enc[0].sb1), P2S_PER_ENC, 64, 64},
+    {LK_ENC, P2S_AT(enc[0].s2, enc[0].sb2), P2S_PER_ENC, 64, 128},         {LK_ENC, P2S_AT(enc[0].s3, enc[0].sb3), P2S_PER_ENC, 128, 1024},
+    {LK_ENC, P2S_AT(enc[0].m2, enc[0].mb2), P2S_PER_ENC, 64, 128},         {LK_ENC, P2S_AT(enc[0].m3, enc[0].mb3), P2S_PER_ENC, 128, 1024},
+    {LK_QSTN, P2S_AT(qstn.c2, qstn.cb2), 0, 64, 128},                      {LK_QSTN, P2S_AT(qstn.c3, qstn.cb3), 0, 128, 1024},
+    {LK_ENC_HEAD, P2S_AT(enc[0].sf1, enc[0].sfb1), P2S_PER_ENC, 1024, 512}, {LK_ENC_HEAD, P2S_AT(enc[0].sf2, enc[0].sfb2), P2S_PER_ENC, 512, 256},
+    {LK_ENC_HEAD, P2S_AT(enc[0].sf3, enc[0].sfb3), P2S_PER_ENC, 256, 4096},
+    {LK_QSTN_HEAD, P2S_AT(qstn.f1, qstn.fb1), 0, 1024, 512},               {LK_QSTN_HEAD, P2S_AT(qstn.f2, qstn.fb2), 0, 512, 256},
+    {LK_FP32, P2S_AT(d1l, db1l), offsetof(p2s_weight_offsets, d1g) - offsetof(p2s_weight_offsets, d1l), 1024, 512},
+    {LK_FP32, P2S_AT(d2, db2), 0, 1024, 256},                              {LK_FP32, P2S_AT(d3, db3), 0, 256, 128},
+};
+#undef P2S_AT
+// does a model of this configuration hold 16-bit fragments of the layers of `kind`?
+inline bool p2s_kind_packed(P2sLayerKind kind, const p2s_model_cfg &c) {
+    const Precision p = p2s_precision(c);
+    const bool head = kind == LK_ENC_HEAD || kind == LK_QSTN_HEAD, qstn = kind == LK_QSTN || kind == LK_QSTN_HEAD;
+    return kind != LK_FP32 && (head ? p.f16 : p.pieces != 0) && (!qstn || c.use_point_stn);
+}
+
 struct p2s_model_s {
-    p2s_model_cfg cfg;
-    p2s_weight_offsets offs;
-    int device = 0;
+    const p2s_model_cfg cfg;
+    const p2s_weight_offsets offs;
+    const int device;
     float *blob = nullptr;
-    size_t n_floats = 0;
-    // bf16 encoder (cfg.encoder_bf16): bf16 B fragments of the per-point layers, converted once at creation
-    unsigned short *blob_h = nullptr;      // [pieces][h_total] (cfg.encoder_bf16 = number of bf16 pieces per operand)
+    // 16-bit encoder modes: 16-bit B fragments of the layers p2s_kind_packed() names, converted once at creation
+    unsigned short *blob_h = nullptr;      // [pieces][h_total]
     size_t h_total = 0;
-    size_t h_w0b[2] = {}, h_s1[2] = {}, h_s2[2] = {}, h_s3[2] = {}, h_m2[2] = {}, h_m3[2] = {}, h_qc2 = 0, h_qc3 = 0;
-    // fp16 pair mode: the STN / QSTN head layers as 16-bit fragments too (p2s_gemm_f16_kernel); the decoder stays fp32
-    size_t h_sf1[2] = {}, h_sf2[2] = {}, h_sf3[2] = {}, h_qf1 = 0, h_qf2 = 0;
-    bool heads_f16 = false;
+    size_t h_off[P2S_LAYERS][2] = {};      // of slice 0 / 1 of a layer within a piece (a layer without slices: the same twice)
+    p2s_model_s(const p2s_model_cfg &c, const p2s_weight_offsets &o, int dev) : cfg(c), offs(o), device(dev) {}
+    // the operands of `layer`, slice z: fp32 fragments / bias in blob, piece 0 of the 16-bit fragments in blob_h
+    const float *w32(P2sLayer layer, int z) const { return blob + offset(p2s_layers[layer].w + z * p2s_layers[layer].slice); }
+    const float *bias(P2sLayer layer, int z) const { return blob + offset(p2s_layers[layer].b + z * p2s_layers[layer].slice); }
+    const unsigned short *w16(P2sLayer layer, int z) const { return blob_h + h_off[layer][z]; }
+    uint64_t offset(size_t member) const { return *reinterpret_cast<const uint64_t *>(reinterpret_cast<const char *>(&offs) + member); }
     // fp16 pair mode: queries with an activation beyond the half range are flagged by the 16-bit kernels, collected per
     // chunk (inputs copied aside) and re-run through the fp32 kernels at the end of the same call (ModelCall::finish)
     struct Fallback {
@@ -92,9 +137,6 @@ int p2s_workers_segments(const p2s_worker_streams *ws, int64_t n, std::vector<P2
 int p2s_launch_stream_order(int64_t g0, int64_t n, int W, int B, const float *q_in, float *q_out, int64_t *src, hipStream_t s);
 int p2s_launch_unpermute(const int64_t *src, int64_t n, const float *sdf_in, float *sdf_out, const float *logits_in,
                          float *logits_out, int dim, hipStream_t s);
-// cfg.encoder_bf16: 0 fp32, 1 bf16, 2 / 3 split bf16, 4 fp16 pair (2 pieces, two accumulators)
-inline int p2s_enc_pieces(const p2s_model_cfg &c) { return c.encoder_bf16 == 4 ? 2 : c.encoder_bf16; }
-inline int p2s_enc_f16(const p2s_model_cfg &c) { return c.encoder_bf16 == 4 ? 1 : 0; }
 
 // One call of a model entry point (p2s_encode_*, the pipeline calls), constructed first.  Construction (m == NULL: nothing)
 // takes the one-shot logits capture off the model (pipeline calls, whatever the outcome), sets the device, resets the profile
@@ -119,11 +161,15 @@ enum P2SStage { ST_CHAIN_STN = 0, ST_HEAD, ST_CHAIN_MAIN, ST_DECODER, ST_KNN, ST
 int p2s_prof_mark(p2s_model_s *m, hipStream_t s);                 // event index or -1
 void p2s_prof_span(p2s_model_s *m, int stage, int a, int b);
 
+// the forward pass (p2s_forward.hip)
 int p2s_model_reserve(p2s_model_s *m, int chunk);
+// One chunk (C <= ws_chunk queries) at `prec`: the model's own, or P2S_FP32 (the fp32 fragments are resident in any mode).
 // index0: position of the chunk's first query in the output arrays of the call's finish() (what the fp32 fallback scatters to)
-int p2s_run_chunk(p2s_model_s *m, const float *patch, const float *sub, const float *query, const float *radius,
+int p2s_run_chunk(p2s_model_s *m, Precision prec, const float *patch, const float *sub, const float *query, const float *radius,
                   int C, float *logits_out, float *sdf_out, float *feat_local_out, float *feat_global_out,
                   hipStream_t s, long long index0 = 0);
+// fp16 pair mode (ModelCall::finish): the collected queries through the fp32 kernels, their results scattered over the outputs
+int p2s_fallback_finish(p2s_model_s *m, float *logits_out, float *sdf_out, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // cloud / rng handles (p2s_cloud.hip, p2s_rng.hip)

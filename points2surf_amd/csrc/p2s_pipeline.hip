@@ -418,7 +418,7 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, const P2sSegment *segs, 
             if ((rc = p2s_rotate_points(b.rot[bi], qc, 1, cur, b.qrot[bi], s))) return fail(rc);
             qc = b.qrot[bi];
         }
-        rc = p2s_run_chunk(m, b.patch[bi], b.sub[bi], qc, b.radius[bi], cur,
+        rc = p2s_run_chunk(m, p2s_precision(m->cfg), b.patch[bi], b.sub[bi], qc, b.radius[bi], cur,
                            logits_out ? logits_out + (size_t)q0 * m->cfg.output_dim : nullptr, sdf_out_dev + q0, nullptr, nullptr,
                            s, q0);
         if (rc) return fail(rc);

@@ -1,7 +1,7 @@
 """GPU: the fp16-pair encoder (cfg.encoder_bf16 = 4, BASELINE configs[3]'s fast mode) is safe for an ARBITRARY checkpoint --
 VERDICT r5 item 3.  fp16 ends at 65504; r05 poisoned a query whose activation passed 6e4 and failed the whole call.  Now
 the 16-bit kernels flag such queries, their inputs are put aside per chunk, and at the end of the same call they run
-through the fp32 kernels (p2s_api.hip: ModelCall::finish); ``counters()['fallback_queries']`` says how many.
+through the fp32 kernels (p2s_forward.hip: p2s_fallback_finish); ``counters()['fallback_queries']`` says how many.
 
 The checkpoints here compute the SAME function as the synthetic p2s_max / p2s_vanilla weights -- one BatchNorm channel is
 scaled by 2^k and the next layer's weights for that channel by 2^-k (ReLU and max-pool are positively homogeneous, powers
