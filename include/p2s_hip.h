@@ -38,6 +38,7 @@ extern "C" {
 typedef struct p2s_model_s *p2s_model_t;
 typedef struct p2s_cloud_s *p2s_cloud_t;
 typedef struct p2s_rng_s   *p2s_rng_t;
+typedef struct p2s_trimesh_s *p2s_trimesh_t;
 
 int         p2s_abi_version(void);
 const char *p2s_last_error(void);
@@ -411,6 +412,42 @@ int p2s_points_remove_close(const float *pts_dev, int64_t m, double radius, int6
  * Hausdorff distance, *sum_host = the Chamfer term; dist_out_dev [n] float64 may be NULL.  Synchronises. */
 int p2s_nn_distance_stats(p2s_cloud_t target, const float *query_dev, int64_t n, double *dist_out_dev, double *max_host,
                           double *sum_host, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * "next" row: ground-truth signed distance to a triangle mesh -- what the reference obtains from
+ * trimesh.proximity.signed_distance in batches of 1000 queries (source/sdf.py:318-348, get_signed_distance) for the
+ * GT file 05_query_dist/<shape>.npy of make_dataset.py:447-474.  Exact: nearest triangle in float64 (ties: smallest
+ * face id), sign from the pseudonormal of the closest feature (face / edge / vertex), queries whose sign is within
+ * rounding of zero re-decided by the generalised winding number.  Positive inside (trimesh), negative outside, a query
+ * with d <= 1e-8 (trimesh tol.merge) keeps its unsigned d; a non-finite query, or one so far away that d^2 overflows
+ * float64 (coordinates beyond ~1e154), yields NaN and face -1.  A handle serves ONE p2s_mesh_distance call at a time
+ * (info[5] is per handle); different handles are independent.
+ * ------------------------------------------------------------------------------------------ */
+/* replaces trimesh.load / trimesh.Trimesh(vertices, faces) (make_dataset.py:457) + the proximity structures
+ * signed_distance builds per call: verts_dev [n_verts][3] float32, faces_dev [n_faces][3] int32 (both read during the
+ * call only).  Indices out of range or a non-finite vertex: P2S_EINVAL, before anything dereferences them.  Holds the
+ * float64 triangles, face / edge / angle-weighted vertex pseudonormals and the cell + octree index of the triangles' AABBs;
+ * an inward-oriented closed mesh is stored flipped (trimesh.repair.fix_inversion).  Build scratch (the edge table, ~150
+ * bytes per face) returns to the device's block cache before the call ends.  Synchronises `stream`. */
+int p2s_trimesh_create(const float *verts_dev, int64_t n_verts, const int32_t *faces_dev, int64_t n_faces, int device,
+                       void *stream, p2s_trimesh_t *out);
+int p2s_trimesh_destroy(p2s_trimesh_t m);
+/* trimesh's mesh.is_watertight / is_winding_consistent / the sign of mesh.volume.  info_host[8]: [0] n_faces,
+ * [1] closed (every undirected edge traversed exactly once in each direction), [2] inverted (closed and signed volume
+ * < 0: stored flipped), [3] number of open or non-manifold edges, [4] cells per axis of the index, [5] point-triangle
+ * tests of the last indexed p2s_mesh_distance call on this handle, [6] connected components (closed meshes; 0
+ * otherwise), [7] 0.  The components of a closed mesh may overlap (a union of solids): with 2..16 components the sign is
+ * the sum of the per-component pseudonormal signs (one nearest-triangle pass per component); with more, every signed
+ * query is decided by the winding number (O(n_faces) per query). */
+int p2s_trimesh_info(p2s_trimesh_t m, int64_t *info_host);
+/* trimesh.proximity.signed_distance(mesh, query) (source/sdf.py:329; signed_ = 0: the unsigned closest-point distance of
+ * trimesh.proximity.closest_point).  query_dev [n][3] float32 in any order; dist_out_dev [n] float64; face_out_dev [n]
+ * (nearest face) and closest_out_dev [n][3] float64 may be NULL.  signed_ != 0 on a mesh that is not closed:
+ * P2S_EINVAL, nothing written.  method 0 = index, 1 = exhaustive (every query against every triangle: the yardstick of
+ * the index; identical results).  *n_winding_host (may be NULL) = queries decided by the winding number.
+ * Synchronises `stream`. */
+int p2s_mesh_distance(p2s_trimesh_t m, const float *query_dev, int64_t n, int signed_, int method, double *dist_out_dev,
+                      int32_t *face_out_dev, double *closest_out_dev, int64_t *n_winding_host, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * "next" row: the per-shape text / debug files of save_evaluation and implicit_surface_to_mesh, written

@@ -82,6 +82,11 @@ PROTOTYPES = {
                                         c_void_p]),
     'p2s_nn_distance_stats': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, ctypes.POINTER(ctypes.c_double),
                                       ctypes.POINTER(ctypes.c_double), c_void_p]),
+    'p2s_trimesh_create': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, ctypes.POINTER(c_void_p)]),
+    'p2s_trimesh_destroy': (c_int, [c_void_p]),
+    'p2s_trimesh_info': (c_int, [c_void_p, ctypes.POINTER(c_int64)]),
+    'p2s_mesh_distance': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                  ctypes.POINTER(c_int64), c_void_p]),
     'p2s_set_profiling': (c_int, [c_void_p, c_int]),
     'p2s_get_counters': (c_int, [c_void_p, ctypes.POINTER(Counters)]),
     'p2s_model_capture_logits': (c_int, [c_void_p, c_void_p, c_int64]),

@@ -25,6 +25,7 @@ import time
 import numpy as np
 
 import source as _pkg
+from points2surf_amd.file_utils import call_necessary as _call_necessary
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _IMPORT_PID = os.getpid()
@@ -140,16 +141,6 @@ def implicit_surface_to_mesh_file(query_dist_ms_file, query_pts_ms_file, volume_
                              grid_res, sigma, certainty_threshold)
 
 
-def _call_necessary(files_in, files_out):
-    """file_utils.call_necessary (source/base/file_utils.py:194-240): inputs exist and an output is missing or older"""
-    if any(not os.path.isfile(f) for f in files_in):
-        print('WARNING: Input file are missing: {}'.format([f for f in files_in if not os.path.isfile(f)]))
-        return False
-    if any(not os.path.isfile(f) or os.path.getsize(f) == 0 for f in files_out):
-        return True
-    return max(os.path.getmtime(f) for f in files_in) >= min(os.path.getmtime(f) for f in files_out)
-
-
 def implicit_surface_to_mesh_directory(imp_surf_dist_ms_dir, query_pts_ms_dir, vol_out_dir, mesh_out_dir,
                                        grid_res, sigma, certainty_threshold, num_processes=1):
     """reference :240-266.  The reference forks ``num_processes`` workers (source/base/utils_mp.py:33-35), each running
@@ -190,8 +181,36 @@ def implicit_surface_to_mesh_directory(imp_surf_dist_ms_dir, query_pts_ms_dir, v
         sharding.barrier()               # the metrics stage that follows reads every rank's meshes
 
 
+def get_signed_distance(in_mesh, query_pts_ms, signed_distance_batch_size=1000):
+    """reference :318-348 with trimesh.proximity.signed_distance on the device (p2s_mesh_distance): ``in_mesh`` is anything
+    with ``.vertices`` and ``.faces``; float64 [n], positive inside.  ``signed_distance_batch_size`` is accepted and ignored
+    (the reference batches because trimesh needs ~8 GB per 3k queries).  A mesh that is not closed raises ValueError
+    (declared in INTEGRATION.md: trimesh would return a ray-parity sign of no defined meaning there).  The query points are
+    rounded to float32 before they are measured (the C ABI takes float32 queries, the stored form of 05_query_pts); the
+    reference measures the float64 points -- up to 8e-6 on the fixtures, also declared there."""
+    _check_process()
+    from points2surf_amd import gt_sdf
+    query_pts_ms = np.asarray(query_pts_ms)
+    mesh = gt_sdf.TriMesh(np.asarray(in_mesh.vertices, dtype=np.float32), np.asarray(in_mesh.faces))
+    try:
+        info = mesh.info()
+        if not info['closed']:
+            raise ValueError('get_signed_distance: the mesh is not closed ({} open or non-manifold edges)'.format(
+                info['bad_edges']))
+        dists_ms = mesh.distance(query_pts_ms.astype(np.float32), signed=True).cpu().numpy()
+    finally:
+        mesh.close()
+    num_nans = np.isnan(dists_ms).sum()
+    num_infs = np.isinf(dists_ms).sum()
+    if num_nans > 0 or num_infs > 0:
+        print('Error: Encountered {} NaN and {} Inf values in signed distance of {}.'.format(
+            num_nans, num_infs, query_pts_ms))
+    return dists_ms
+
+
 if _ref is not None:
     # code of the reference module that resolves these names in ITS globals gets the device versions too
     _ref.add_samples_to_volume = add_samples_to_volume
     _ref.propagate_sign = propagate_sign
     _ref.visualize_query_points = visualize_query_points
+    _ref.get_signed_distance = get_signed_distance

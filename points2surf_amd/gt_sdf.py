@@ -1,0 +1,147 @@
+"""Ground-truth signed distance to a triangle mesh on the device: what the reference computes with
+``trimesh.proximity.signed_distance`` (source/sdf.py:318-348) for the GT file ``05_query_dist/<shape>.npy``
+(make_dataset.py:447-474), through libp2s_hip.so (p2s_trimesh_create, p2s_mesh_distance).  Exact point-to-mesh distance
+in float64, positive inside like trimesh.  Torch tensors are containers only; no CPU fallback.
+
+``python -m points2surf_amd.gt_sdf --indir DATASET`` writes ``DATASET/05_query_dist`` from ``03_meshes`` and
+``05_query_pts``.
+"""
+import argparse
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import engine as _engine
+from . import ply as _ply
+from .file_utils import call_necessary as _call_necessary
+
+METHODS = {'index': 0, 'exhaustive': 1}
+
+
+class TriMesh:
+    """Device-resident triangle mesh with its distance index (replaces ``trimesh.load`` + the proximity structures of
+    ``trimesh.proximity.signed_distance``).  ``verts`` [V, 3], ``faces`` [F, 3]: numpy arrays or tensors."""
+
+    def __init__(self, verts, faces, device=None):
+        if not torch.cuda.is_available():
+            raise RuntimeError('points2surf_amd needs a ROCm GPU (gfx950); no CPU fallback exists')
+        self.lib = _lib.load()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        if isinstance(verts, np.ndarray):
+            verts = torch.from_numpy(np.ascontiguousarray(verts, dtype=np.float32))
+        if isinstance(faces, np.ndarray):
+            faces = torch.from_numpy(np.ascontiguousarray(faces).astype(np.int32))
+        v = verts.to(self.device, torch.float32).contiguous()
+        f = faces.to(self.device, torch.int32).contiguous()
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError('verts must be [V, 3] and faces [F, 3] (got %s, %s)' % (tuple(v.shape), tuple(f.shape)))
+        self.handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.p2s_trimesh_create(_engine._ptr(v), int(v.shape[0]), _engine._ptr(f), int(f.shape[0]),
+                                                   self.device.index, _engine._stream_ptr(self.device),
+                                                   ctypes.byref(self.handle)))
+        self.n_winding = 0
+
+    def info(self):
+        """dict: n_faces, closed, inverted, bad_edges (open or non-manifold), grid (cells per axis), tests (point-triangle
+        tests of the last indexed distance call), components (of a closed mesh)"""
+        a = (ctypes.c_int64 * 8)()
+        _lib.check(self.lib.p2s_trimesh_info(self.handle, a))
+        return dict(n_faces=int(a[0]), closed=bool(a[1]), inverted=bool(a[2]), bad_edges=int(a[3]), grid=int(a[4]),
+                    tests=int(a[5]), components=int(a[6]))
+
+    @property
+    def closed(self):
+        return self.info()['closed']
+
+    def distance(self, queries, signed=True, method='index', want_face=False, want_closest=False):
+        """float64 device tensor [n]: the (signed: positive inside) distance of every query; with ``want_face`` /
+        ``want_closest`` also the nearest face [n] int32 / the closest point [n, 3] float64.  ``self.n_winding`` = queries
+        of this call whose sign the winding number decided."""
+        if self.handle is None:
+            raise RuntimeError('TriMesh is closed')
+        if isinstance(queries, np.ndarray):
+            queries = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32))
+        q = queries.to(self.device, torch.float32).contiguous()
+        if q.ndim != 2 or q.shape[1] != 3:
+            raise ValueError('queries must be [n, 3] (got %s)' % (tuple(q.shape),))
+        n = int(q.shape[0])
+        dist = torch.empty((n,), dtype=torch.float64, device=self.device)
+        face = torch.empty((n,), dtype=torch.int32, device=self.device) if want_face else None
+        closest = torch.empty((n, 3), dtype=torch.float64, device=self.device) if want_closest else None
+        nw = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.p2s_mesh_distance(self.handle, _engine._ptr(q), n, int(bool(signed)), METHODS[method],
+                                                  _engine._ptr(dist), _engine._ptr(face), _engine._ptr(closest),
+                                                  ctypes.byref(nw), _engine._stream_ptr(self.device)))
+        self.n_winding = int(nw.value)
+        out = (dist,) + ((face,) if want_face else ()) + ((closest,) if want_closest else ())
+        return out[0] if len(out) == 1 else out
+
+    def close(self):
+        if getattr(self, 'handle', None) is not None and self.handle:
+            self.lib.p2s_trimesh_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def query_dist(mesh, query_pts):
+    """make_dataset.py:464-474: the signed distances of ``query_pts`` with NaN -> 0, inf -> 1, clamped to [-1, 1], as a
+    float32 numpy array (the content of 05_query_dist/<shape>.npy)"""
+    d = mesh.distance(query_pts, signed=True)
+    d = torch.nan_to_num(d, nan=0.0, posinf=1.0, neginf=1.0).clamp_(-1.0, 1.0)
+    return d.to(torch.float32).cpu().numpy()
+
+
+def load_mesh(path, device=None):
+    v, f = _ply.read_ply(path)
+    return TriMesh(np.asarray(v, dtype=np.float32), np.asarray(f), device=device)
+
+
+def write_query_dist_dir(mesh_dir, query_pts_dir, out_dir, device=None):
+    """05_query_dist/<mesh>.npy for every 03_meshes/<mesh> that has 05_query_pts/<mesh>.npy (get_query_pts_dist_ms of
+    make_dataset.py:481-530 without the query-point generation); files that are up to date are skipped.  Returns the
+    list of files written."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for name in sorted(os.listdir(mesh_dir)):
+        f_mesh = os.path.join(mesh_dir, name)
+        f_pts = os.path.join(query_pts_dir, name + '.npy')
+        f_out = os.path.join(out_dir, name + '.npy')
+        if not os.path.isfile(f_mesh) or not os.path.isfile(f_pts):
+            continue
+        if not _call_necessary([f_mesh, f_pts], [f_out]):
+            continue
+        mesh = load_mesh(f_mesh, device=device)
+        try:
+            if not mesh.closed:
+                raise ValueError('%s is not closed (%d open or non-manifold edges): no signed distance'
+                                 % (f_mesh, mesh.info()['bad_edges']))
+            np.save(f_out, query_dist(mesh, np.load(f_pts).astype(np.float32)))
+        finally:
+            mesh.close()
+        written.append(f_out)
+    return written
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description='write DATASET/05_query_dist from 03_meshes and 05_query_pts')
+    ap.add_argument('--indir', required=True)
+    opt = ap.parse_args(argv)
+    for f in write_query_dist_dir(os.path.join(opt.indir, '03_meshes'), os.path.join(opt.indir, '05_query_pts'),
+                                  os.path.join(opt.indir, '05_query_dist')):
+        print(f)
+
+
+if __name__ == '__main__':
+    main()

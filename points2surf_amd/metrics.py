@@ -154,3 +154,44 @@ def mesh_comparison(new_meshes_dir_abs, ref_meshes_dir_abs, num_processes, repor
     with open(report_name, 'w') as text_file:
         text_file.write('\n'.join(csv_lines))
     return results
+
+
+def sdf_error(rec_dir, ref_meshes_dir, report_name, device=None):
+    """How far the predicted SDF lies from the truth, over the WHOLE query grid (eval_predictions of the reference looks at
+    the 2,000 GT queries only): for every ``rec_dir/dist_ms/<s>.xyz.npy`` + ``rec_dir/query_pts_ms/<s>.xyz.npy`` with a GT
+    mesh ``ref_meshes_dir/<s>.*`` the exact signed distance of every query to the mesh (p2s_mesh_distance, clamped to
+    [-1, 1] like the GT files) and, against the prediction, the MSE, the mean and max of |d_pred - d_gt| and the share of
+    wrong signs.  One CSV in the style of mesh_comparison; returns its rows."""
+    from . import gt_sdf as _gt
+    dev = _dev(device)
+    dist_dir, pts_dir = os.path.join(rec_dir, 'dist_ms'), os.path.join(rec_dir, 'query_pts_ms')
+    ref_files = sorted(f for f in os.listdir(ref_meshes_dir) if os.path.isfile(os.path.join(ref_meshes_dir, f)))
+    results = []
+    for name in sorted(f for f in os.listdir(dist_dir) if f.endswith('.xyz.npy')):
+        f_pts = os.path.join(pts_dir, name)
+        match = [f for f in ref_files if f.split('.')[0] == name.split('.')[0]]
+        if not os.path.isfile(f_pts) or not match:
+            continue
+        f_ref = os.path.join(ref_meshes_dir, match[0])
+        mesh = _gt.load_mesh(f_ref, device=dev)
+        try:
+            if not mesh.closed:
+                results.append((os.path.join(dist_dir, name), f_ref, '0', '-1', '-1', '-1', '-1'))
+                continue
+            pred = torch.from_numpy(np.load(os.path.join(dist_dir, name)).astype(np.float64).reshape(-1)).to(dev)
+            gt = mesh.distance(np.load(f_pts).astype(np.float32), signed=True).clamp_(-1.0, 1.0)
+        finally:
+            mesh.close()
+        err = (pred - gt).abs()
+        wrong = ((pred > 0) != (gt > 0)).double().mean()
+        results.append((os.path.join(dist_dir, name), f_ref, str(int(gt.shape[0])), repr(float((err * err).mean())),
+                        repr(float(err.mean())), repr(float(err.max())), repr(float(wrong))))
+    if len(results) == 0:
+        raise ValueError('Results are empty!')
+    if os.path.dirname(report_name):
+        os.makedirs(os.path.dirname(report_name), exist_ok=True)
+    csv_lines = ['dist file,ref mesh,queries,MSE,mean abs error,max abs error,wrong sign share(-1: mesh not closed)']
+    csv_lines += [','.join(item) for item in results]
+    with open(report_name, 'w') as text_file:
+        text_file.write('\n'.join(csv_lines))
+    return results

@@ -1,0 +1,70 @@
+"""Timing of the GT-distance path (points2surf_amd/gt_sdf.py): handle build, 2,000 queries and the full 256^3 query grid of
+the test shape against each fixture mesh and against the engine's own 256^3 mesh, indexed next to exhaustive.  HIP events,
+one warm-up, median of three; one JSON line per case.    python tools/gt_sdf_bench.py [--skip-large] [--no-exhaustive-large]"""
+import argparse
+import glob
+import json
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+FIX = os.path.join(REPO, 'tests', 'golden', 'abc_minimal')
+
+
+def timed(fn, reps=3):
+    import torch
+    fn()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return float(np.median(ms))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--skip-large', action='store_true')
+    ap.add_argument('--no-exhaustive-large', action='store_true', help='skip grid x 0.92 M faces exhaustively (~3e11 tests)')
+    args = ap.parse_args()
+    import torch
+    from points2surf_amd import engine, gt_sdf, ply, synth
+    pts = np.load(os.path.join(FIX, '04_pts', '00994122_57d9d4755722f9d2d7436f0a_trimesh_000.xyz.npy'))
+    cloud = engine.Cloud(pts)
+    grid = cloud.query_grid(256, 3).contiguous()
+    few = torch.from_numpy(np.load(glob.glob(os.path.join(FIX, '05_query_pts', '00994122*'))[0]).astype(np.float32)).cuda()
+    meshes = [(os.path.basename(f)[:8],) + tuple(ply.read_ply(f)) for f in sorted(glob.glob(os.path.join(FIX, '03_meshes', '*.ply')))]
+    if not args.skip_large:
+        w, cfg = synth.make_weights('p2s_max')
+        sdf, q = engine.infer_shape(engine.Model(w, cfg), cloud, engine.Rng(40938661), 256, 3)
+        vol, _ = engine.sdf_volume(q, sdf, 256, 5, 13.0, clamp=True)
+        v, f, _ = engine.marching_cubes(vol, model_space=True, fix_inversion=True)
+        meshes.append(('engine256',) + ply.merge_vertices(v.cpu().numpy(), f.cpu().numpy()))
+    for name, v, f in meshes:
+        vt = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).cuda()
+        ft = torch.from_numpy(np.ascontiguousarray(f).astype(np.int32)).cuda()
+        build_ms = timed(lambda: gt_sdf.TriMesh(vt, ft).close())
+        mesh = gt_sdf.TriMesh(vt, ft)
+        info = mesh.info()
+        for label, q in (('2000', few), ('grid256', grid)):
+            for signed in (False, True) if info['closed'] else (False,):
+                row = dict(mesh=name, faces=info['n_faces'], grid=info['grid'], components=info['components'], build_ms=build_ms,
+                           queries=int(q.shape[0]), set=label, signed=signed)
+                row['index_ms'] = timed(lambda: mesh.distance(q, signed=signed, method='index'))
+                row['tests_per_query'] = mesh.info()['tests'] / q.shape[0]
+                row['n_winding'] = mesh.n_winding
+                if not (name == 'engine256' and label == 'grid256' and args.no_exhaustive_large):
+                    row['exhaustive_ms'] = timed(lambda: mesh.distance(q, signed=signed, method='exhaustive'),
+                                                 reps=1 if name == 'engine256' and label == 'grid256' else 3)
+                print(json.dumps(row), flush=True)
+        mesh.close()
+
+
+if __name__ == '__main__':
+    main()
