@@ -450,6 +450,46 @@ int p2s_mesh_distance(p2s_trimesh_t m, const float *query_dev, int64_t n, int si
                       int32_t *face_out_dev, double *closest_out_dev, int64_t *n_winding_host, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * "next" row: scanning a mesh into a point cloud and drawing the GT query points -- what the reference's
+ * make_dataset.py does by starting one BlenSor process per mesh (:242-380: 5..30 time-of-flight scans of 176 x 144 rays)
+ * and with trimesh (source/sdf.py:288-315).  First-hit ray casting on the p2s_trimesh_t handle, float64.
+ * Rules: the smallest t in (0, t_max] wins, ties go to the smallest face id; both sides of a face are hit; a ray in a
+ * face's plane misses it; a degenerate face (|ab x ac|^2 <= 2^-90 |ab|^2 |ac|^2) is never hit; a hit whose computed
+ * point lies more than 2^-24 max(|mesh|, |origin|) outside the face's bounding box is discarded (rounding at
+ * conditioning beyond 2^-28 only); a direction component below 2^-1022 in magnitude is taken as 0; a ray with a non-finite component (|x| > 1e300) or a zero direction misses.  A miss
+ * is face -1, t = +inf; no NaN is ever written.
+ * ------------------------------------------------------------------------------------------ */
+/* rays_dev [n][6] float64 (origin, direction; the direction need not be normalised: t is in units of it); t_out_dev [n]
+ * float64, face_out_dev [n].  method 0 = index (octree descent), 1 = exhaustive (every ray against every triangle: the
+ * yardstick; identical results).  *tests_host (may be NULL) = ray-triangle tests performed.  Synchronises `stream`. */
+int p2s_mesh_raycast(p2s_trimesh_t m, const double *rays_dev, int64_t n, double t_max, int method, double *t_out_dev,
+                     int32_t *face_out_dev, int64_t *tests_host, void *stream);
+/* the time-of-flight sensor: width x height pixels, tan(angle / 2) of the horizontal and the vertical opening angle
+ * (computed by the caller), the largest distance that returns a hit */
+typedef struct {
+    int32_t width, height;
+    double  tan_half_w, tan_half_h, max_distance;
+} p2s_tof_sensor;
+/* n_scans scans of the mesh.  Sensor frame: camera at the origin looking along +y, x right, z up; the object is placed
+ * at R(q) p + location.  poses_host [n_scans][7]: location[3], UNIT quaternion (w, x, y, z); ||q|^2 - 1| > 2^-49: P2S_EINVAL.  Pixel (i, j) looks along
+ * normalise(((i + 1/2 - W/2) 2 tan_half_w / W, 1, (j + 1/2 - H/2) 2 tan_half_h / H)); the ray is cast in model space
+ * (origin R^T (-location), direction R^T dir), so t is the sensor distance.  noise_dev [n_scans * H * W] float64
+ * standard-normal deviates, one per ray in the order (scan, row j, column i).  The hits are written in that order
+ * (stable): noisy_out_dev [hits][3] = o + (t + sigma g) d, clean_out_dev [hits][3] = o + t d, face_out_dev [hits],
+ * normal_out_dev [hits][3] = the hit face's stored unit normal; every output holds n_scans * H * W entries.
+ * hits_per_scan_host [n_scans], *n_hits_host = their sum, *tests_host (may be NULL) as above.  Synchronises `stream`. */
+int p2s_mesh_tof_scan(p2s_trimesh_t m, const double *poses_host, int32_t n_scans, const p2s_tof_sensor *sensor, double sigma,
+                      const double *noise_dev, int method, double *noisy_out_dev, double *clean_out_dev, int32_t *face_out_dev,
+                      double *normal_out_dev, int32_t *hits_per_scan_host, int64_t *n_hits_host, int64_t *tests_host, void *stream);
+/* get_query_pts_for_mesh (source/sdf.py:288-315): out_dev [n_far + n_close][3] float32 = n_far points u - 1/2
+ * (u_far_dev [n_far][3] float64 in [0, 1)), then the surface samples samples_dev [n_close][3] float32 of the faces
+ * face_dev [n_close] (p2s_mesh_sample_surface) moved along the face's stored unit normal by
+ * (u_offset_dev[i] - 1/2) * 2 * patch_radius.  Stream-ordered. */
+int p2s_mesh_query_points(p2s_trimesh_t m, const float *samples_dev, const int32_t *face_dev, const double *u_offset_dev,
+                          const double *u_far_dev, int64_t n_close, int64_t n_far, double patch_radius, float *out_dev,
+                          void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * "next" row: the per-shape text / debug files of save_evaluation and implicit_surface_to_mesh, written
  * by native HOST code (no device is touched; all pointers are host pointers).  Byte-identical to what the reference's
  * numpy / Python calls write.

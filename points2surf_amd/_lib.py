@@ -87,6 +87,12 @@ PROTOTYPES = {
     'p2s_trimesh_info': (c_int, [c_void_p, ctypes.POINTER(c_int64)]),
     'p2s_mesh_distance': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   ctypes.POINTER(c_int64), c_void_p]),
+    'p2s_mesh_raycast': (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_double, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+                                 c_void_p]),
+    'p2s_mesh_tof_scan': (c_int, [c_void_p, c_void_p, ctypes.c_int32, c_void_p, ctypes.c_double, c_void_p, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p]),
+    'p2s_mesh_query_points': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_double, c_void_p,
+                                      c_void_p]),
     'p2s_set_profiling': (c_int, [c_void_p, c_int]),
     'p2s_get_counters': (c_int, [c_void_p, ctypes.POINTER(Counters)]),
     'p2s_model_capture_logits': (c_int, [c_void_p, c_void_p, c_int64]),
@@ -99,6 +105,12 @@ PROTOTYPES = {
     'p2s_write_query_vis_ply': (c_int, [ctypes.c_char_p, c_void_p, c_void_p, c_int64]),
     'p2s_write_coff_samples': (c_int, [ctypes.c_char_p, c_void_p, c_void_p, c_int64]),
 }
+
+
+class TofSensor(ctypes.Structure):
+    """mirror of ``p2s_tof_sensor``"""
+    _fields_ = [('width', ctypes.c_int32), ('height', ctypes.c_int32), ('tan_half_w', ctypes.c_double),
+                ('tan_half_h', ctypes.c_double), ('max_distance', ctypes.c_double)]
 
 
 class WorkerStreams(ctypes.Structure):

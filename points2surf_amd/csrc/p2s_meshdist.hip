@@ -20,6 +20,7 @@
 //   p2s_md_exhaustive_kernel  every query against every triangle (yardstick of the index, and for tiny meshes)
 //   p2s_md_finalize_kernel    closest point, distance, pseudonormal sign, flag of the queries whose sign is not trusted
 //   p2s_md_winding_kernel     generalised winding number (Jacobson et al. 2013) of a flagged query: one workgroup each
+// First-hit ray casting, the time-of-flight scan and the query points on the same handle: p2s_meshray.inl (end of file).
 //
 // The pseudonormal sign holds for ONE closed surface that does not intersect itself.  A closed mesh of several connected
 // components may be a union of overlapping solids (the reference's 00011084 is: 170 of its 2,000 GT queries lie just outside
@@ -1181,3 +1182,8 @@ extern "C" int p2s_mesh_distance(p2s_trimesh_t m, const float *query_dev, int64_
     if (n_winding_host) *n_winding_host = (int64_t)hc[1];
     return P2S_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// ray casting, time-of-flight scan and query points on the same handle
+// ---------------------------------------------------------------------------------------------
+#include "p2s_meshray.inl"
