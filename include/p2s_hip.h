@@ -436,7 +436,8 @@ int p2s_trimesh_destroy(p2s_trimesh_t m);
  * [1] closed (every undirected edge traversed exactly once in each direction), [2] inverted (closed and signed volume
  * < 0: stored flipped), [3] number of open or non-manifold edges, [4] cells per axis of the index, [5] point-triangle
  * tests of the last indexed p2s_mesh_distance call on this handle, [6] connected components (closed meshes; 0
- * otherwise), [7] 0.  The components of a closed mesh may overlap (a union of solids): with 2..16 components the sign is
+ * otherwise), [7] faces under the degenerate rule (|ab x ac|^2 <= 2^-90 |ab|^2 |ac|^2; they enter the rounding term of
+ * p2s_mesh_winding).  The components of a closed mesh may overlap (a union of solids): with 2..16 components the sign is
  * the sum of the per-component pseudonormal signs (one nearest-triangle pass per component); with more, every signed
  * query is decided by the winding number (O(n_faces) per query). */
 int p2s_trimesh_info(p2s_trimesh_t m, int64_t *info_host);
@@ -445,9 +446,25 @@ int p2s_trimesh_info(p2s_trimesh_t m, int64_t *info_host);
  * (nearest face) and closest_out_dev [n][3] float64 may be NULL.  signed_ != 0 on a mesh that is not closed:
  * P2S_EINVAL, nothing written.  method 0 = index, 1 = exhaustive (every query against every triangle: the yardstick of
  * the index; identical results).  *n_winding_host (may be NULL) = queries decided by the winding number.
- * Synchronises `stream`. */
+ * signed_ = 2: the same distance with EVERY sign from the generalised winding number (p2s_mesh_winding, method 0,
+ * tau = 2^-10), inside iff |w| > 0.5: defined on any mesh, closed or not; a query with d <= 1e-8 keeps its unsigned d;
+ * *n_winding_host = queries the tree left undecided and the exact sum decided.  Synchronises `stream`. */
 int p2s_mesh_distance(p2s_trimesh_t m, const float *query_dev, int64_t n, int signed_, int method, double *dist_out_dev,
                       int32_t *face_out_dev, double *closest_out_dev, int64_t *n_winding_host, void *stream);
+
+/* Generalised winding number (Jacobson et al. 2013) of every query, defined for open meshes too: w_out_dev [n] float64.
+ * method 0 = a walk of the handle's octree: a node at distance d from its box centre beyond twice its half-diagonal r is
+ * taken as one dipole of its area-weighted normal when its error bound A r / (2 pi (d - r)^3) is at most
+ * tau * A / A_root (A the node's area), so the accepted bounds of a query sum to at most tau; other nodes are opened, leaf
+ * cells add their triangles exactly.  err_out_dev [n] (may be NULL) = the sum of the accepted bounds plus the rounding term
+ *     2^-53 F (K + F / 256 + 32) + D 2^-46 / pi,
+ * F = faces, K = terms added for the query (at most F), D = info[7]: |w_out - w_exact| <= err.  A query with
+ * | |w| - 0.5 | <= err is re-decided: it gets the exact sum and err 0.  method 1 = the exact sum for every query
+ * (O(n_faces) each: the yardstick; err 0).  tau finite in [0, 0.25], else P2S_EINVAL and nothing written; tau = 0 opens
+ * every node.  stats_host[4] (may be NULL): nodes accepted, triangles evaluated, queries re-decided exactly, 0.  A
+ * non-finite query gives NaN (w and err).  Synchronises `stream`. */
+int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t n, int method, double tau, double *w_out_dev,
+                     double *err_out_dev, int64_t *stats_host, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * "next" row: scanning a mesh into a point cloud and drawing the GT query points -- what the reference's

@@ -87,6 +87,8 @@ PROTOTYPES = {
     'p2s_trimesh_info': (c_int, [c_void_p, ctypes.POINTER(c_int64)]),
     'p2s_mesh_distance': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   ctypes.POINTER(c_int64), c_void_p]),
+    'p2s_mesh_winding': (c_int, [c_void_p, c_void_p, c_int64, c_int, ctypes.c_double, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+                                 c_void_p]),
     'p2s_mesh_raycast': (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_double, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int64),
                                  c_void_p]),
     'p2s_mesh_tof_scan': (c_int, [c_void_p, c_void_p, ctypes.c_int32, c_void_p, ctypes.c_double, c_void_p, c_int, c_void_p, c_void_p,

@@ -20,6 +20,10 @@
 //   p2s_md_exhaustive_kernel  every query against every triangle (yardstick of the index, and for tiny meshes)
 //   p2s_md_finalize_kernel    closest point, distance, pseudonormal sign, flag of the queries whose sign is not trusted
 //   p2s_md_winding_kernel     generalised winding number (Jacobson et al. 2013) of a flagged query: one workgroup each
+//   p2s_md_cell_sort_kernel / p2s_md_stri_kernel / p2s_md_moments_leaf_kernel   fixed triangle order per cell, node moments
+//   p2s_md_wtree_kernel       the winding number of every query by a walk of the octree: far nodes as dipoles with a
+//                             certified error bound, near leaf cells exactly (p2s_mesh_winding, p2s_mesh_distance signed_ 2)
+//   p2s_md_wsign_kernel       sign of the distance from that winding number
 // First-hit ray casting, the time-of-flight scan and the query points on the same handle: p2s_meshray.inl (end of file).
 //
 // The pseudonormal sign holds for ONE closed surface that does not intersect itself.  A closed mesh of several connected
@@ -68,6 +72,8 @@ struct p2s_trimesh_s {
     int *sface = nullptr;          // [F]     face ids sorted by cell
     double *stri = nullptr;        // [F][9]  triangles in that order
     int *nodes = nullptr;          // [(8^(L+1) - 1) / 7][6]  lo, hi as ordered integers of the float32 bounds
+    double *mom = nullptr;         // [same][4]  sum of the area vectors 1/2 (b - a) x (c - a) and of the areas of the node's triangles
+    long long n_degenerate = 0;    // faces under the 2^-90 rule (they add nothing to the moments)
     unsigned char *fbad = nullptr; // [F]     the face's normal is not trusted (zero area, or a sliver: see SLIVER_REL)
     int *vbad = nullptr;           // [V]     the vertex touches such a face
     long long last_tests = 0;
@@ -490,16 +496,15 @@ __global__ __launch_bounds__(256) void p2s_md_nodes_init_kernel(int *__restrict_
     }
 }
 
-// the order within a cell is whatever the atomics give; no result depends on it (ties are decided by face id)
+// the order within a cell is whatever the atomics give; p2s_md_cell_sort_kernel then makes it ascending in the face id
 __global__ __launch_bounds__(256) void p2s_md_fill_kernel(const double *__restrict__ tri, const int *__restrict__ fcell, long long F,
                                                           const int *__restrict__ start, int *__restrict__ cursor,
-                                                          int *__restrict__ sface, double *__restrict__ stri, int *__restrict__ leaf) {
+                                                          int *__restrict__ sface, int *__restrict__ leaf) {
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
     const int cell = fcell[f];
     const int at = start[cell] + atomicAdd(&cursor[cell], 1);
     sface[at] = (int)f;
-    for (int k = 0; k < 9; ++k) stri[9 * (long long)at + k] = tri[9 * f + k];
     for (int k = 0; k < 3; ++k) {
         const float a = (float)tri[9 * f + k], b = (float)tri[9 * f + 3 + k], c = (float)tri[9 * f + 6 + k];      // exact: float32 vertices
         atomicMin(&leaf[6 * (long long)cell + k], f2o(fminf(a, fminf(b, c))));
@@ -507,24 +512,105 @@ __global__ __launch_bounds__(256) void p2s_md_fill_kernel(const double *__restri
     }
 }
 
+// The face ids of every cell in ascending order, so that two handles of one mesh hold the same sface / stri and every sum
+// taken "in sface order" (the node moments, the exact terms of p2s_md_wtree_kernel) is reproducible.  No distance or ray
+// result depends on the order (ties are decided by face id).  One thread per cell, in place: insertion sort for the usual
+// handful of faces, heapsort beyond (a cell holds one to two triangles on average, see the choice of G).
+__global__ __launch_bounds__(256) void p2s_md_cell_sort_kernel(const int *__restrict__ start, long long cells, int *__restrict__ sface) {
+    const long long cell = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (cell >= cells) return;
+    int *a = sface + start[cell];
+    const int n = start[cell + 1] - start[cell];
+    if (n <= 16) {
+        for (int i = 1; i < n; ++i) {
+            const int v = a[i];
+            int j = i;
+            for (; j > 0 && a[j - 1] > v; --j) a[j] = a[j - 1];
+            a[j] = v;
+        }
+        return;
+    }
+    auto sift = [&](int root, int end) {             // max-heap on a[0, end)
+        const int v = a[root];
+        for (;;) {
+            int ch = 2 * root + 1;
+            if (ch >= end) break;
+            if (ch + 1 < end && a[ch + 1] > a[ch]) ++ch;
+            if (a[ch] <= v) break;
+            a[root] = a[ch];
+            root = ch;
+        }
+        a[root] = v;
+    };
+    for (int i = n / 2 - 1; i >= 0; --i) sift(i, n);
+    for (int end = n - 1; end > 0; --end) {
+        const int v = a[0];
+        a[0] = a[end];
+        a[end] = v;
+        sift(0, end);
+    }
+}
+__global__ __launch_bounds__(256) void p2s_md_stri_kernel(const double *__restrict__ tri, const int *__restrict__ sface, long long F,
+                                                          double *__restrict__ stri) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= F) return;
+    const long long f = sface[t];
+    for (int k = 0; k < 9; ++k) stri[9 * t + k] = tri[9 * f + k];
+}
+
+// moments of a leaf cell: N = sum 1/2 (b - a) x (c - a), A = sum 1/2 |(b - a) x (c - a)| over its triangles in sface order
+// (ascending face id), one thread per cell; a face under the 2^-90 degenerate rule adds 0 to both and is counted
+__global__ __launch_bounds__(256) void p2s_md_moments_leaf_kernel(const double *__restrict__ stri, const int *__restrict__ start, long long cells,
+                                                                  double *__restrict__ mom, unsigned long long *__restrict__ n_degenerate) {
+    const long long cell = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (cell >= cells) return;
+    double N[3] = {0.0, 0.0, 0.0}, A = 0.0;
+    unsigned long long deg = 0;
+    const int t1 = start[cell + 1];
+    for (int t = start[cell]; t < t1; ++t) {
+        const double *P = stri + 9 * (long long)t;
+        double ab[3], ac[3], n[3];
+        for (int k = 0; k < 3; ++k) {
+            ab[k] = P[3 + k] - P[k];
+            ac[k] = P[6 + k] - P[k];
+        }
+        cross3(ab, ac, n);
+        const double nn = dot3(n, n);
+        if (!(nn > DEGENERATE_REL * (dot3(ab, ab) * dot3(ac, ac)))) {
+            ++deg;
+            continue;
+        }
+        for (int k = 0; k < 3; ++k) N[k] += 0.5 * n[k];
+        A += 0.5 * sqrt(nn);
+    }
+    for (int k = 0; k < 3; ++k) mom[4 * cell + k] = N[k];
+    mom[4 * cell + 3] = A;
+    if (deg) atomicAdd(n_degenerate, deg);
+}
+
 // level l (n = 2^l nodes per axis) from level l + 1
-__global__ __launch_bounds__(256) void p2s_md_nodes_up_kernel(int *__restrict__ parent, const int *__restrict__ child, int l) {
+// and the parent's moments: its children's, added in the fixed order 0..7
+__global__ __launch_bounds__(256) void p2s_md_nodes_up_kernel(int *__restrict__ parent, const int *__restrict__ child, double *__restrict__ pmom,
+                                                              const double *__restrict__ cmom, int l) {
     const int n = 1 << l;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)n * n * n) return;
     const int z = (int)(i & (n - 1)), y = (int)((i >> l) & (n - 1)), x = (int)(i >> (2 * l));
     int mn[3] = {0x7f800000, 0x7f800000, 0x7f800000}, mx[3] = {(int)0x807fffff, (int)0x807fffff, (int)0x807fffff};
+    double mo[4] = {0.0, 0.0, 0.0, 0.0};
     for (int c = 0; c < 8; ++c) {
         const long long j = ((long long)(2 * x + (c >> 2)) * (2 * n) + (2 * y + ((c >> 1) & 1))) * (2 * n) + (2 * z + (c & 1));
         for (int k = 0; k < 3; ++k) {
             mn[k] = min(mn[k], child[6 * j + k]);
             mx[k] = max(mx[k], child[6 * j + 3 + k]);
         }
+        for (int k = 0; k < 4; ++k) mo[k] += cmom[4 * j + k];
     }
     for (int k = 0; k < 3; ++k) {
         parent[6 * i + k] = mn[k];
         parent[6 * i + 3 + k] = mx[k];
     }
+    for (int k = 0; k < 4; ++k) pmom[4 * i + k] = mo[k];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -786,37 +872,206 @@ __global__ __launch_bounds__(256) void p2s_md_comp_apply_kernel(FinalArgs a) {
 }
 
 // generalised winding number w(p) = sum over faces of 2 atan2(a . (b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) / 4 pi
-// (a, b, c the corners minus p; van Oosterom & Strackee 1983); inside iff |w| > 0.5.  One workgroup per flagged query.
-__global__ __launch_bounds__(256) void p2s_md_winding_kernel(const double *__restrict__ tri, long long F, const float *__restrict__ q,
-                                                             const int *__restrict__ flagged, double *__restrict__ dist) {
-    __shared__ double ws[4];
-    const int i = flagged[blockIdx.x];
-    const double p[3] = {(double)q[3 * (long long)i], (double)q[3 * (long long)i + 1], (double)q[3 * (long long)i + 2]};
-    double sm = 0.0;
-    for (long long f = threadIdx.x; f < F; f += 256) {
-        double a[3], b[3], c[3], x[3];
-        for (int k = 0; k < 3; ++k) {
-            a[k] = tri[9 * f + k] - p[k];
-            b[k] = tri[9 * f + 3 + k] - p[k];
-            c[k] = tri[9 * f + 6 + k] - p[k];
-        }
-        const double la = sqrt(dot3(a, a)), lb = sqrt(dot3(b, b)), lc = sqrt(dot3(c, c));
-        cross3(b, c, x);
-        const double num = dot3(a, x);
-        const double den = ((la * lb * lc + dot3(a, b) * lc) + dot3(b, c) * la) + dot3(c, a) * lb;
-        sm += atan2(num, den);
+// (a, b, c the corners minus p; van Oosterom & Strackee 1983); inside iff |w| > 0.5.
+// The atan2 of one triangle t [9] (half its signed solid angle): the one place it is computed.
+__device__ __forceinline__ double winding_term(const double *__restrict__ t, const double *p) {
+    double a[3], b[3], c[3], x[3];
+    for (int k = 0; k < 3; ++k) {
+        a[k] = t[k] - p[k];
+        b[k] = t[3 + k] - p[k];
+        c[k] = t[6 + k] - p[k];
     }
+    const double la = sqrt(dot3(a, a)), lb = sqrt(dot3(b, b)), lc = sqrt(dot3(c, c));
+    cross3(b, c, x);
+    const double num = dot3(a, x);
+    const double den = ((la * lb * lc + dot3(a, b) * lc) + dot3(b, c) * la) + dot3(c, a) * lb;
+    return atan2(num, den);
+}
+
+// The exact sum, one workgroup per query: query flagged[blockIdx.x], or blockIdx.x itself without a list.  With `dist` the
+// sign of dist[i] is set from it; with `w_out` the value is written (its bound err_out[i], if asked for, is 0: this IS the
+// yardstick).  A non-finite query gives NaN.
+__global__ __launch_bounds__(256) void p2s_md_winding_kernel(const double *__restrict__ tri, long long F, const float *__restrict__ q,
+                                                             const int *__restrict__ flagged, double *__restrict__ dist,
+                                                             double *__restrict__ w_out, double *__restrict__ err_out) {
+    __shared__ double ws[4];
+    const long long i = flagged ? (long long)flagged[blockIdx.x] : (long long)blockIdx.x;
+    const double p[3] = {(double)q[3 * i], (double)q[3 * i + 1], (double)q[3 * i + 2]};
+    double sm = 0.0;
+    for (long long f = threadIdx.x; f < F; f += 256) sm += winding_term(tri + 9 * f, p);
     for (int d = 32; d > 0; d >>= 1) sm += __shfl_xor(sm, d);
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = sm;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double w = (((ws[0] + ws[1]) + ws[2]) + ws[3]) / 6.283185307179586;
-        const double d = fabs(dist[i]);
-        dist[i] = fabs(w) > 0.5 ? d : -d;
+        const double w = finite3(p) ? (((ws[0] + ws[1]) + ws[2]) + ws[3]) / 6.283185307179586 : NAN;
+        if (dist) {
+            const double d = fabs(dist[i]);
+            dist[i] = fabs(w) > 0.5 ? d : -d;
+        }
+        if (w_out) w_out[i] = w;
+        if (err_out) err_out[i] = finite3(p) ? 0.0 : NAN;
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// hierarchical winding number
+// ---------------------------------------------------------------------------------------------
+// One query per lane walks the octree depth first.  A node with box centre c, half-diagonal r and moments N (sum of the
+// area vectors) and A (sum of the areas) may stand for all its triangles as ONE dipole
+//     w_node ~ N . (c - p) / (4 pi d^3),   d = |c - p|.
+// Error.  The exact contribution of a triangle T with unit normal n and area a is the integral over T of
+// K(x) = n . (x - p) / (4 pi |x - p|^3), and a K(c) is its share of the dipole.  4 pi |y|^3 grad K = n - 3 (n . y^) y^ (y = x - p)
+// has the squared norm 1 + 3 cos^2 <= 4, so |grad K| <= 1 / (2 pi |y|^3).  Every point of the box lies within r of c, the
+// segment from c to it stays at least d - r from p, hence |K(x) - K(c)| <= r / (2 pi (d - r)^3) and, summed with the areas,
+//     |w_node - dipole| <= A r / (2 pi (d - r)^3) =: bound.
+// A node is taken as a dipole only if  tau > 0,  d >= 2 r,  A <= 2 pi d^2  and  bound <= tau A / A_root;  otherwise it is
+// opened: its non-empty children are pushed, or, for a leaf cell, its triangles are added exactly (winding_term, in sface
+// order).  The accepted nodes are disjoint, so their areas sum to at most A_root and their bounds to at most tau.
+// d >= 2 r and A <= 2 pi d^2 cost nothing where the budget rule holds (it asks for far more) and are what the rounding term
+// below stands on: |dipole| <= A / (4 pi d^2) <= 1/2 like every exact term, and seen from p the corners of a triangle of the
+// node lie within 60 degrees of each other, so the denominator of its atan2 is above 2.5 |a||b||c| and the exhaustive
+// kernel's own term is within 4 ulp of the true solid angle.
+// Outputs: w~ = (sum of the atan2 terms) / 2 pi + sum of the dipoles, and
+//     eps = sum of the accepted bounds + 2^-53 F (K + F / 256 + 32) + D 2^-46 / pi,
+// K = terms added for this query (triangles + dipoles), F = faces, D = degenerate faces of the mesh.  The second term
+// covers, with u = 2^-53 and every term at most 1/2 in magnitude: this kernel's sequential sum (K u K / 2), the exhaustive
+// kernel's sum of F terms in 256 strided partial sums and a reduction ((F / 256 + 10) u F / 2), the rounding of the moments
+// (the cross products carry 4 u |ab||ac| <= 16 u r^2 each and the sums of at most F terms F u A, against 4 pi d^2: below
+// 2 F u over all accepted nodes), the 4 ulp per triangle inside an accepted node (4 F u / 2 pi), the dipole's own arithmetic
+// (2 u each) and the rounding of the bound sum (K u / 4): together below half of it.  The third: a degenerate face is not
+// in the moments; its area is at most 2^-46 |ab||ac| <= 2^-46 (2 r)^2, so for d >= 2 r it contributes at most
+// 2^-46 r^2 / (pi (d - r)^2) <= 2^-46 / pi.  The query is decided when | |w~| - 0.5 | > eps: inside / outside is then what the
+// exact sum gives.  r is rounded up by 2^-30 (c and r come from float64 arithmetic on the float32 box).
+// Stack: a pop of an inner node pushes at most 8, so the depth is at most 7 L + 1 = 50 for L <= MD_MAX_L = 7: one LDS
+// column of WT_STACK = 52 entries per lane, 13 KiB per workgroup (the scheme of p2s_mr_index_kernel).  A push beyond it
+// cannot happen; if it ever did the call fails (ctr[3]) instead of dropping a node.
+constexpr int MD_MAX_L = 7;
+constexpr int WT_STACK = 52;
+static_assert(WT_STACK >= 7 * MD_MAX_L + 1, "depth-first stack: 7 entries stay per opened level, plus the 8th child of the last");
+static_assert(3 * MD_MAX_L + 3 <= 27, "a node id is (level << 27) | linear index");
+
+struct WTreeDev {
+    const int *nodes;
+    const double *mom;
+    const int *cell_start;
+    const double *stri;
+    int L;
+    long long F, n_degenerate;
+    double tau;
+};
+
+__device__ __forceinline__ double wtree_rounding(double F, double K, double D) {
+    return 1.1102230246251565e-16 * (F * ((K + F * 0.00390625) + 32.0)) + D * 4.523328512768113e-15;      // 2^-53, 2^-46 / pi
+}
+
+// ctr: [0] nodes accepted, [1] triangles evaluated, [2] undecided queries (with `undecided`: their list), [3] stack overflow
+__global__ __launch_bounds__(64) void p2s_md_wtree_kernel(WTreeDev ix, const float *__restrict__ q, long long n, double *__restrict__ w_out,
+                                                          double *__restrict__ err_out, int *__restrict__ undecided,
+                                                          unsigned long long *__restrict__ ctr) {
+    __shared__ int stack[WT_STACK * 64];
+    const int lane = threadIdx.x;
+    const long long i = (long long)blockIdx.x * 64 + lane;
+    unsigned long long accepted = 0, tris = 0;
+    if (i < n) {
+        const double p[3] = {(double)q[3 * i], (double)q[3 * i + 1], (double)q[3 * i + 2]};
+        if (!finite3(p)) {
+            w_out[i] = NAN;
+            if (err_out) err_out[i] = NAN;
+        } else {
+            const double a_root = ix.mom[3];
+            double sa = 0.0, sd = 0.0, sb = 0.0;
+            int sp = 0;
+            stack[(sp++) * 64 + lane] = 0;
+            while (sp > 0) {
+                const int node = stack[(--sp) * 64 + lane];
+                const int l = node >> 27, lin = node & 0x7ffffff;
+                const long long at = ((1ll << (3 * l)) - 1) / 7 + lin;
+                const int *bx = ix.nodes + 6 * at;
+                const double *mo = ix.mom + 4 * at;
+                double cp[3], e[3];
+                for (int k = 0; k < 3; ++k) {
+                    const double lo = o2f(bx[k]), hi = o2f(bx[3 + k]);
+                    cp[k] = 0.5 * (lo + hi) - p[k];
+                    e[k] = hi - lo;
+                }
+                const double r = (0.5 * sqrt(dot3(e, e))) * 1.0000000009313226, d = sqrt(dot3(cp, cp)), A = mo[3];
+                if (ix.tau > 0.0 && d >= 2.0 * r && A <= 6.283185307179586 * (d * d)) {
+                    const double g = d - r, g3 = g * g * g;
+                    const double bound = (A * r) / (6.283185307179586 * g3);
+                    if (g3 > 0.0 && bound * a_root <= ix.tau * A) {
+                        sd += dot3(mo, cp) / (12.566370614359172 * (d * d * d));
+                        sb += bound;
+                        ++accepted;
+                        continue;
+                    }
+                }
+                if (l == ix.L) {
+                    const int t1 = ix.cell_start[lin + 1];
+                    for (int t = ix.cell_start[lin]; t < t1; ++t) {
+                        sa += winding_term(ix.stri + 9 * (long long)t, p);
+                        ++tris;
+                    }
+                } else {
+                    const int nn = 1 << l;
+                    const int z = lin & (nn - 1), y = (lin >> l) & (nn - 1), x = lin >> (2 * l);
+                    const long long coff = ((1ll << (3 * (l + 1))) - 1) / 7;
+                    for (int c = 7; c >= 0; --c) {           // child 0 is popped first: a fixed order
+                        const int clin = ((2 * x + (c >> 2)) * (2 * nn) + (2 * y + ((c >> 1) & 1))) * (2 * nn) + (2 * z + (c & 1));
+                        const int *cb = ix.nodes + 6 * (coff + clin);
+                        if (cb[0] > cb[3]) continue;         // empty: no triangle, nothing to add
+                        if (sp < WT_STACK) stack[(sp++) * 64 + lane] = ((l + 1) << 27) | clin;
+                        else atomicOr(ctr + 3, 1ull);
+                    }
+                }
+            }
+            const double w = sa / 6.283185307179586 + sd;
+            const double eps = sb + wtree_rounding((double)ix.F, (double)(accepted + tris), (double)ix.n_degenerate);
+            w_out[i] = w;
+            if (err_out) err_out[i] = eps;
+            if (undecided && !(fabs(fabs(w) - 0.5) > eps)) undecided[atomicAdd(ctr + 2, 1ull)] = (int)i;
+        }
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+        accepted += __shfl_xor(accepted, s);
+        tris += __shfl_xor(tris, s);
+    }
+    if (lane == 0) {
+        if (accepted) atomicAdd(ctr, accepted);
+        if (tris) atomicAdd(ctr + 1, tris);
+    }
+}
+
+// signed_ == 2: the sign of every distance from the winding number, inside iff |w| > 0.5; d <= 1e-8 (tol.merge) and NaN stay;
+// an undecided query goes to the exact sum (p2s_md_winding_kernel)
+__global__ __launch_bounds__(256) void p2s_md_wsign_kernel(const double *__restrict__ w, const double *__restrict__ err, long long n,
+                                                           double *__restrict__ dist, int *__restrict__ flagged,
+                                                           unsigned long long *__restrict__ n_flagged) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double d = dist[i];
+    if (!(d > 1.0e-8)) return;
+    if (!(fabs(fabs(w[i]) - 0.5) > err[i])) flagged[atomicAdd(n_flagged, 1ull)] = (int)i;
+    else dist[i] = fabs(w[i]) > 0.5 ? d : -d;
+}
+
 unsigned blocks(long long n, int per) { return (unsigned)std::max<long long>(1, (n + per - 1) / per); }
+
+constexpr double WINDING_TAU_DEFAULT = 0.0009765625;       // 2^-10
+
+// ctr [4] as p2s_md_wtree_kernel takes it (zeroed by the caller)
+void launch_wtree(const p2s_trimesh_s *m, const float *q, long long n, double tau, double *w, double *err, int *undecided,
+                  unsigned long long *ctr, hipStream_t s) {
+    WTreeDev ix;
+    ix.nodes = m->nodes;
+    ix.mom = m->mom;
+    ix.cell_start = m->cell_start;
+    ix.stri = m->stri;
+    ix.L = m->L;
+    ix.F = m->F;
+    ix.n_degenerate = m->n_degenerate;
+    ix.tau = tau;
+    hipLaunchKernelGGL(p2s_md_wtree_kernel, dim3(blocks(n, 64)), dim3(64), 0, s, ix, q, n, w, err, undecided, ctr);
+}
 
 }  // namespace
 
@@ -847,7 +1102,7 @@ extern "C" int p2s_trimesh_create(const float *verts_dev, int64_t n_verts, const
     // two triangles per occupied cell (measured on the 0.92 M-face mesh: ~110 triangle tests per query); the octree over
     // the G^3 cells is 24 bytes per node (55 MB at G = 128)
     int L = 1;
-    while (L < 7 && (double)(1 << L) * (double)(1 << L) * 8.0 < (double)F) ++L;
+    while (L < MD_MAX_L && (double)(1 << L) * (double)(1 << L) * 8.0 < (double)F) ++L;
     const int G = 1 << L;
     const long long cells = (long long)G * G * G, n_nodes = ((1ll << (3 * (L + 1))) - 1) / 7, leaf_off = ((1ll << (3 * L)) - 1) / 7;
     unsigned cap = 1024;
@@ -858,7 +1113,7 @@ extern "C" int p2s_trimesh_create(const float *verts_dev, int64_t n_verts, const
     auto take = [&](size_t bytes) { const size_t o = at; at += up(bytes); return o; };
     const size_t o_tri = take((size_t)F * 72), o_stri = take((size_t)F * 72), o_fn = take((size_t)F * 24), o_vn = take((size_t)V * 32),
                  o_fidx = take((size_t)F * 12), o_adj = take((size_t)F * 12), o_sface = take((size_t)F * 4),
-                 o_start = take((size_t)(cells + 1) * 4), o_nodes = take((size_t)n_nodes * 24),
+                 o_start = take((size_t)(cells + 1) * 4), o_nodes = take((size_t)n_nodes * 24), o_mom = take((size_t)n_nodes * 32),
                  o_parent = take((size_t)F * 4), o_scomp = take((size_t)F * 4), o_fbad = take((size_t)F), o_vbad = take((size_t)V * 4);
     const size_t persistent = at;
     // build scratch: a block of its own, back in the cache when the build is over
@@ -913,6 +1168,7 @@ extern "C" int p2s_trimesh_create(const float *verts_dev, int64_t n_verts, const
     m->sface = (int *)(arena + o_sface);
     m->cell_start = (int *)(arena + o_start);
     m->nodes = (int *)(arena + o_nodes);
+    m->mom = (double *)(arena + o_mom);
     m->fbad = (unsigned char *)(arena + o_fbad);
     m->vbad = (int *)(arena + o_vbad);
     auto dec = [](int i) { const int b = i >= 0 ? i : i ^ 0x7fffffff; float f; memcpy(&f, &b, 4); return f; };
@@ -981,15 +1237,22 @@ extern "C" int p2s_trimesh_create(const float *verts_dev, int64_t n_verts, const
             hipLaunchKernelGGL(p2s_md_setup_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, a);
             hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, a.count, cells, m->cell_start);
             hipLaunchKernelGGL(p2s_md_fill_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, m->tri, a.fcell, F, m->cell_start, cursor, m->sface,
-                               m->stri, m->nodes + 6 * leaf_off);
+                               m->nodes + 6 * leaf_off);
+            hipLaunchKernelGGL(p2s_md_cell_sort_kernel, dim3(blocks(cells, 256)), dim3(256), 0, s, m->cell_start, cells, m->sface);
+            hipLaunchKernelGGL(p2s_md_stri_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, m->tri, m->sface, F, m->stri);
+            hipLaunchKernelGGL(p2s_md_moments_leaf_kernel, dim3(blocks(cells, 256)), dim3(256), 0, s, m->stri, m->cell_start, cells,
+                               m->mom + 4 * leaf_off, ctr + 4);
             for (int l = L - 1; l >= 0; --l) {
                 const long long off = ((1ll << (3 * l)) - 1) / 7, coff = ((1ll << (3 * (l + 1))) - 1) / 7;
                 hipLaunchKernelGGL(p2s_md_nodes_up_kernel, dim3(blocks(1ll << (3 * l), 256)), dim3(256), 0, s, m->nodes + 6 * off,
-                                   m->nodes + 6 * coff, l);
+                                   m->nodes + 6 * coff, m->mom + 4 * off, m->mom + 4 * coff, l);
             }
             e = hipGetLastError();
         }
+        unsigned long long n_deg = 0;
+        if (e == hipSuccess) e = hipMemcpyAsync(&n_deg, ctr + 4, 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
+        m->n_degenerate = (long long)n_deg;
         if (e == hipSuccess && m->closed) {
             int *parent = (int *)(arena + o_parent);
             hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, parent, F, 1);
@@ -1064,7 +1327,7 @@ extern "C" int p2s_trimesh_info(p2s_trimesh_t m, int64_t *info_host) {
     info_host[4] = m->G;
     info_host[5] = m->last_tests;
     info_host[6] = m->components;
-    info_host[7] = 0;
+    info_host[7] = m->n_degenerate;
     return P2S_OK;
 }
 
@@ -1075,6 +1338,12 @@ extern "C" int p2s_mesh_distance(p2s_trimesh_t m, const float *query_dev, int64_
         p2s_set_error("p2s_mesh_distance: bad argument");
         return P2S_EINVAL;
     }
+    if (signed_ != 0 && signed_ != 1 && signed_ != 2) {
+        p2s_set_error("p2s_mesh_distance: signed_ is 0 (unsigned), 1 (pseudonormal) or 2 (winding number)");
+        return P2S_EINVAL;
+    }
+    const bool by_winding = signed_ == 2;          // the unsigned distance, then every sign from the winding number
+    if (by_winding) signed_ = 0;
     if (signed_ && !m->closed) {
         p2s_set_error("p2s_mesh_distance: the mesh is not closed (%lld open or non-manifold edges): no signed distance", m->bad_edges);
         return P2S_EINVAL;
@@ -1095,7 +1364,8 @@ extern "C" int p2s_mesh_distance(p2s_trimesh_t m, const float *query_dev, int64_
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const bool per_comp = signed_ && m->components >= 2 && m->components <= 16;
     const size_t b_face = up((size_t)n * 4), b_flag = up((size_t)n * 4 * (per_comp ? 3 : 1)), b_pd = up((size_t)n * parts * 8), b_pf = up((size_t)n * parts * 4);
-    char *ws = (char *)p2s_pool_alloc(m->device, b_face + b_flag + b_pd + b_pf + 256);     // + the call's own counters
+    const size_t b_w = by_winding ? up((size_t)n * 16) : 0;                                // w~ and its bound
+    char *ws = (char *)p2s_pool_alloc(m->device, b_face + b_flag + b_pd + b_pf + 256 + b_w);     // + the call's own counters
     if (!ws) {
         p2s_set_error("p2s_mesh_distance: out of device memory");
         return P2S_ENOMEM;
@@ -1163,13 +1433,24 @@ extern "C" int p2s_mesh_distance(p2s_trimesh_t m, const float *query_dev, int64_
             hipLaunchKernelGGL(p2s_md_comp_sign_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, a);
         }
         if (per_comp) hipLaunchKernelGGL(p2s_md_comp_apply_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, a);
+        if (by_winding) {
+            double *w = (double *)(ws + b_face + b_flag + b_pd + b_pf + 256), *err = w + n;
+            launch_wtree(m, query_dev, (long long)n, WINDING_TAU_DEFAULT, w, err, nullptr, ctr + 4, s);
+            hipLaunchKernelGGL(p2s_md_wsign_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, w, err, (long long)n, dist_out_dev, flagged, ctr + 1);
+        }
         e = hipGetLastError();
     }
-    unsigned long long hc[2] = {};
-    if (e == hipSuccess) e = hipMemcpyAsync(hc, ctr, 16, hipMemcpyDeviceToHost, s);
+    unsigned long long hc[8] = {};
+    if (e == hipSuccess) e = hipMemcpyAsync(hc, ctr, 64, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && hc[7]) {
+        p2s_pool_free(m->device, ws);
+        p2s_set_error("p2s_mesh_distance: the winding walk overflowed its stack");
+        return P2S_EHIP;
+    }
     if (e == hipSuccess && hc[1] > 0) {
-        hipLaunchKernelGGL(p2s_md_winding_kernel, dim3((unsigned)hc[1]), dim3(256), 0, s, m->tri, m->F, query_dev, flagged, dist_out_dev);
+        hipLaunchKernelGGL(p2s_md_winding_kernel, dim3((unsigned)hc[1]), dim3(256), 0, s, m->tri, m->F, query_dev, flagged, dist_out_dev,
+                           (double *)nullptr, (double *)nullptr);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
@@ -1180,6 +1461,66 @@ extern "C" int p2s_mesh_distance(p2s_trimesh_t m, const float *query_dev, int64_
     }
     m->last_tests = (long long)hc[0];
     if (n_winding_host) *n_winding_host = (int64_t)hc[1];
+    return P2S_OK;
+}
+
+extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t n, int method, double tau, double *w_out_dev,
+                                double *err_out_dev, int64_t *stats_host, void *stream) {
+    if (stats_host) stats_host[0] = stats_host[1] = stats_host[2] = stats_host[3] = 0;
+    if (!m || n < 0 || n > (1ll << 30) || (n > 0 && (!query_dev || !w_out_dev)) || (method != 0 && method != 1) ||
+        !(tau >= 0.0 && tau <= 0.25)) {                       // false for NaN
+        p2s_set_error("p2s_mesh_winding: bad argument (method 0 or 1, tau in [0, 0.25])");
+        return P2S_EINVAL;
+    }
+    if (n == 0) return P2S_OK;
+    P2S_HIP_CHECK(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long hc[4] = {};
+    hipError_t e = hipSuccess;
+    if (method == 1) {
+        hipLaunchKernelGGL(p2s_md_winding_kernel, dim3((unsigned)n), dim3(256), 0, s, m->tri, m->F, query_dev, (const int *)nullptr,
+                           (double *)nullptr, w_out_dev, err_out_dev);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        hc[1] = (unsigned long long)n * (unsigned long long)m->F;
+    } else {
+        const size_t b_list = ((size_t)n * 4 + 255) & ~(size_t)255;
+        char *ws = (char *)p2s_pool_alloc(m->device, b_list + 256);
+        if (!ws) {
+            p2s_set_error("p2s_mesh_winding: out of device memory");
+            return P2S_ENOMEM;
+        }
+        int *undecided = (int *)ws;
+        unsigned long long *ctr = (unsigned long long *)(ws + b_list);
+        e = hipMemsetAsync(ctr, 0, 64, s);
+        if (e == hipSuccess) {
+            launch_wtree(m, query_dev, (long long)n, tau, w_out_dev, err_out_dev, undecided, ctr, s);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(hc, ctr, 32, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess && hc[3]) {
+            p2s_pool_free(m->device, ws);
+            p2s_set_error("p2s_mesh_winding: the walk overflowed its stack");
+            return P2S_EHIP;
+        }
+        if (e == hipSuccess && hc[2] > 0) {                     // undecided: the exact value, bound 0
+            hipLaunchKernelGGL(p2s_md_winding_kernel, dim3((unsigned)hc[2]), dim3(256), 0, s, m->tri, m->F, query_dev, (const int *)undecided,
+                               (double *)nullptr, w_out_dev, err_out_dev);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+        }
+        p2s_pool_free(m->device, ws);
+    }
+    if (e != hipSuccess) {
+        p2s_set_error("p2s_mesh_winding: %s", hipGetErrorString(e));
+        return P2S_EHIP;
+    }
+    if (stats_host) {
+        stats_host[0] = (int64_t)hc[0];
+        stats_host[1] = (int64_t)hc[1];
+        stats_host[2] = (int64_t)hc[2];
+    }
     return P2S_OK;
 }
 

@@ -4,7 +4,8 @@
 in float64, positive inside like trimesh.  Torch tensors are containers only; no CPU fallback.
 
 ``python -m points2surf_amd.gt_sdf --indir DATASET`` writes ``DATASET/05_query_dist`` from ``03_meshes`` and
-``05_query_pts``.
+``05_query_pts``; ``--sign winding`` takes every sign from the generalised winding number (p2s_mesh_winding), which is
+defined for open meshes too, where the default ``--sign pseudonormal`` refuses them.
 """
 import argparse
 import ctypes
@@ -19,6 +20,14 @@ from . import ply as _ply
 from .file_utils import call_necessary as _call_necessary
 
 METHODS = {'index': 0, 'exhaustive': 1}
+WINDING_METHODS = {'tree': 0, 'exhaustive': 1}
+SIGNS = ('pseudonormal', 'winding')
+
+
+def winding_rounding(n_faces, terms, n_degenerate=0):
+    """the rounding term of the winding bound (include/p2s_hip.h, p2s_mesh_winding): ``terms`` = triangles and dipoles
+    added for the query, at most ``n_faces``"""
+    return 2.0 ** -53 * n_faces * (terms + n_faces / 256.0 + 32.0) + n_degenerate * 2.0 ** -46 / np.pi
 
 
 class TriMesh:
@@ -49,11 +58,11 @@ class TriMesh:
 
     def info(self):
         """dict: n_faces, closed, inverted, bad_edges (open or non-manifold), grid (cells per axis), tests (point-triangle
-        tests of the last indexed distance call), components (of a closed mesh)"""
+        tests of the last indexed distance call), components (of a closed mesh), degenerate (faces under the 2^-90 rule)"""
         a = (ctypes.c_int64 * 8)()
         _lib.check(self.lib.p2s_trimesh_info(self.handle, a))
         return dict(n_faces=int(a[0]), closed=bool(a[1]), inverted=bool(a[2]), bad_edges=int(a[3]), grid=int(a[4]),
-                    tests=int(a[5]), components=int(a[6]))
+                    tests=int(a[5]), components=int(a[6]), degenerate=int(a[7]))
 
     @property
     def closed(self):
@@ -62,7 +71,30 @@ class TriMesh:
     def distance(self, queries, signed=True, method='index', want_face=False, want_closest=False):
         """float64 device tensor [n]: the (signed: positive inside) distance of every query; with ``want_face`` /
         ``want_closest`` also the nearest face [n] int32 / the closest point [n, 3] float64.  ``self.n_winding`` = queries
-        of this call whose sign the winding number decided."""
+        of this call whose sign the winding number decided.  ``signed='winding'``: every sign from the generalised
+        winding number (inside iff |w| > 0.5), on any mesh, closed or not; ``self.n_winding`` = queries the tree walk left
+        undecided, re-decided by the exact sum."""
+        q = self._queries(queries)
+        n = int(q.shape[0])
+        if isinstance(signed, str):
+            if signed != 'winding':
+                raise ValueError("signed must be True, False or 'winding' (got %r)" % (signed,))
+            mode = 2
+        else:
+            mode = int(bool(signed))
+        dist = torch.empty((n,), dtype=torch.float64, device=self.device)
+        face = torch.empty((n,), dtype=torch.int32, device=self.device) if want_face else None
+        closest = torch.empty((n, 3), dtype=torch.float64, device=self.device) if want_closest else None
+        nw = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.p2s_mesh_distance(self.handle, _engine._ptr(q), n, mode, METHODS[method],
+                                                  _engine._ptr(dist), _engine._ptr(face), _engine._ptr(closest),
+                                                  ctypes.byref(nw), _engine._stream_ptr(self.device)))
+        self.n_winding = int(nw.value)
+        out = (dist,) + ((face,) if want_face else ()) + ((closest,) if want_closest else ())
+        return out[0] if len(out) == 1 else out
+
+    def _queries(self, queries):
         if self.handle is None:
             raise RuntimeError('TriMesh is closed')
         if isinstance(queries, np.ndarray):
@@ -70,17 +102,24 @@ class TriMesh:
         q = queries.to(self.device, torch.float32).contiguous()
         if q.ndim != 2 or q.shape[1] != 3:
             raise ValueError('queries must be [n, 3] (got %s)' % (tuple(q.shape),))
+        return q
+
+    def winding(self, queries, method='tree', tau=2 ** -10, want_bound=False, want_stats=False):
+        """float64 device tensor [n]: the generalised winding number of every query (Jacobson et al. 2013; defined for open
+        meshes).  ``method='tree'``: far octree nodes as dipoles, their certified error bounds summing to at most ``tau``
+        per query; a query with | |w| - 0.5 | within its bound gets the exact sum.  ``'exhaustive'``: the exact sum for
+        every query.  ``want_bound``: also the bound [n] (0 where exact); ``want_stats``: also a dict accepted (nodes),
+        triangles (evaluated), redecided (queries)."""
+        q = self._queries(queries)
         n = int(q.shape[0])
-        dist = torch.empty((n,), dtype=torch.float64, device=self.device)
-        face = torch.empty((n,), dtype=torch.int32, device=self.device) if want_face else None
-        closest = torch.empty((n, 3), dtype=torch.float64, device=self.device) if want_closest else None
-        nw = ctypes.c_int64(0)
+        w = torch.empty((n,), dtype=torch.float64, device=self.device)
+        err = torch.empty((n,), dtype=torch.float64, device=self.device) if want_bound else None
+        st = (ctypes.c_int64 * 4)()
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.p2s_mesh_distance(self.handle, _engine._ptr(q), n, int(bool(signed)), METHODS[method],
-                                                  _engine._ptr(dist), _engine._ptr(face), _engine._ptr(closest),
-                                                  ctypes.byref(nw), _engine._stream_ptr(self.device)))
-        self.n_winding = int(nw.value)
-        out = (dist,) + ((face,) if want_face else ()) + ((closest,) if want_closest else ())
+            _lib.check(self.lib.p2s_mesh_winding(self.handle, _engine._ptr(q), n, WINDING_METHODS[method], float(tau),
+                                                 _engine._ptr(w), _engine._ptr(err), st, _engine._stream_ptr(self.device)))
+        out = (w,) + ((err,) if want_bound else ()) + \
+            ((dict(accepted=int(st[0]), triangles=int(st[1]), redecided=int(st[2])),) if want_stats else ())
         return out[0] if len(out) == 1 else out
 
     def close(self):
@@ -95,10 +134,12 @@ class TriMesh:
             pass
 
 
-def query_dist(mesh, query_pts):
+def query_dist(mesh, query_pts, sign='pseudonormal'):
     """make_dataset.py:464-474: the signed distances of ``query_pts`` with NaN -> 0, inf -> 1, clamped to [-1, 1], as a
     float32 numpy array (the content of 05_query_dist/<shape>.npy)"""
-    d = mesh.distance(query_pts, signed=True)
+    if sign not in SIGNS:
+        raise ValueError('sign must be one of %s (got %r)' % (SIGNS, sign))
+    d = mesh.distance(query_pts, signed='winding' if sign == 'winding' else True)
     d = torch.nan_to_num(d, nan=0.0, posinf=1.0, neginf=1.0).clamp_(-1.0, 1.0)
     return d.to(torch.float32).cpu().numpy()
 
@@ -108,10 +149,12 @@ def load_mesh(path, device=None):
     return TriMesh(np.asarray(v, dtype=np.float32), np.asarray(f), device=device)
 
 
-def write_query_dist_dir(mesh_dir, query_pts_dir, out_dir, device=None):
+def write_query_dist_dir(mesh_dir, query_pts_dir, out_dir, device=None, sign='pseudonormal'):
     """05_query_dist/<mesh>.npy for every 03_meshes/<mesh> that has 05_query_pts/<mesh>.npy (get_query_pts_dist_ms of
     make_dataset.py:481-530 without the query-point generation); files that are up to date are skipped.  Returns the
-    list of files written."""
+    list of files written.  ``sign='pseudonormal'`` refuses a mesh that is not closed; ``'winding'`` signs any mesh."""
+    if sign not in SIGNS:
+        raise ValueError('sign must be one of %s (got %r)' % (SIGNS, sign))
     os.makedirs(out_dir, exist_ok=True)
     written = []
     for name in sorted(os.listdir(mesh_dir)):
@@ -124,10 +167,10 @@ def write_query_dist_dir(mesh_dir, query_pts_dir, out_dir, device=None):
             continue
         mesh = load_mesh(f_mesh, device=device)
         try:
-            if not mesh.closed:
+            if sign == 'pseudonormal' and not mesh.closed:
                 raise ValueError('%s is not closed (%d open or non-manifold edges): no signed distance'
                                  % (f_mesh, mesh.info()['bad_edges']))
-            np.save(f_out, query_dist(mesh, np.load(f_pts).astype(np.float32)))
+            np.save(f_out, query_dist(mesh, np.load(f_pts).astype(np.float32), sign=sign))
         finally:
             mesh.close()
         written.append(f_out)
@@ -137,9 +180,11 @@ def write_query_dist_dir(mesh_dir, query_pts_dir, out_dir, device=None):
 def main(argv=None):
     ap = argparse.ArgumentParser(description='write DATASET/05_query_dist from 03_meshes and 05_query_pts')
     ap.add_argument('--indir', required=True)
+    ap.add_argument('--sign', choices=SIGNS, default='pseudonormal',
+                    help='pseudonormal: closed meshes only (the default); winding: the generalised winding number, open meshes too')
     opt = ap.parse_args(argv)
     for f in write_query_dist_dir(os.path.join(opt.indir, '03_meshes'), os.path.join(opt.indir, '05_query_pts'),
-                                  os.path.join(opt.indir, '05_query_dist')):
+                                  os.path.join(opt.indir, '05_query_dist'), sign=opt.sign):
         print(f)
 
 

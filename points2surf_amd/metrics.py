@@ -156,13 +156,16 @@ def mesh_comparison(new_meshes_dir_abs, ref_meshes_dir_abs, num_processes, repor
     return results
 
 
-def sdf_error(rec_dir, ref_meshes_dir, report_name, device=None):
+def sdf_error(rec_dir, ref_meshes_dir, report_name, device=None, sign='pseudonormal'):
     """How far the predicted SDF lies from the truth, over the WHOLE query grid (eval_predictions of the reference looks at
     the 2,000 GT queries only): for every ``rec_dir/dist_ms/<s>.xyz.npy`` + ``rec_dir/query_pts_ms/<s>.xyz.npy`` with a GT
     mesh ``ref_meshes_dir/<s>.*`` the exact signed distance of every query to the mesh (p2s_mesh_distance, clamped to
     [-1, 1] like the GT files) and, against the prediction, the MSE, the mean and max of |d_pred - d_gt| and the share of
-    wrong signs.  One CSV in the style of mesh_comparison; returns its rows."""
+    wrong signs.  One CSV in the style of mesh_comparison; returns its rows.  ``sign='pseudonormal'`` writes -1 for a GT
+    mesh that is not closed; ``sign='winding'`` signs every mesh by the generalised winding number."""
     from . import gt_sdf as _gt
+    if sign not in _gt.SIGNS:
+        raise ValueError('sign must be one of %s (got %r)' % (_gt.SIGNS, sign))
     dev = _dev(device)
     dist_dir, pts_dir = os.path.join(rec_dir, 'dist_ms'), os.path.join(rec_dir, 'query_pts_ms')
     ref_files = sorted(f for f in os.listdir(ref_meshes_dir) if os.path.isfile(os.path.join(ref_meshes_dir, f)))
@@ -175,11 +178,11 @@ def sdf_error(rec_dir, ref_meshes_dir, report_name, device=None):
         f_ref = os.path.join(ref_meshes_dir, match[0])
         mesh = _gt.load_mesh(f_ref, device=dev)
         try:
-            if not mesh.closed:
+            if sign == 'pseudonormal' and not mesh.closed:
                 results.append((os.path.join(dist_dir, name), f_ref, '0', '-1', '-1', '-1', '-1'))
                 continue
             pred = torch.from_numpy(np.load(os.path.join(dist_dir, name)).astype(np.float64).reshape(-1)).to(dev)
-            gt = mesh.distance(np.load(f_pts).astype(np.float32), signed=True).clamp_(-1.0, 1.0)
+            gt = mesh.distance(np.load(f_pts).astype(np.float32), signed='winding' if sign == 'winding' else True).clamp_(-1.0, 1.0)
         finally:
             mesh.close()
         err = (pred - gt).abs()
