@@ -507,6 +507,55 @@ int p2s_mesh_query_points(p2s_trimesh_t m, const float *samples_dev, const int32
                           void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * "next" row: repair of a raw triangle mesh and its normalisation -- the stages 02_meshes_cleaned and
+ * 03_meshes of the reference's make_dataset.py (_clean_mesh :383-413: trimesh.process, fill_holes, fix_winding,
+ * fix_inversion, is_volume; _normalize_mesh :71-88).  The project's own definition of the stage (unpinned: trimesh
+ * absent); every result is a function of the input alone, whatever the order in which threads run.
+ * Steps, in this order:
+ *  a. indices out of range or a non-finite vertex: P2S_EINVAL, before anything dereferences them;
+ *  b. weld: vertices with equal float32 coordinates (-0.0 counts as +0.0; NO rounding to a tolerance) become the one of
+ *     the smallest input index;
+ *  c. faces with a repeated index after welding are dropped; of faces with the same vertex set (any rotation or winding)
+ *     the smallest face id survives; faces under the degenerate rule (|ab x ac|^2 <= 2^-90 |ab|^2 |ac|^2) are counted
+ *     and kept (removing them opens T-junctions);
+ *  d. orient: faces are neighbours across an undirected edge that exactly two faces use; a component is a connected set
+ *     under that relation (edges of more than two faces connect nothing).  Faces are flipped so that neighbours traverse
+ *     their shared edge in opposite directions, the face of the smallest id keeping its winding; a component where that
+ *     is impossible (a Moebius strip) is left exactly as it came and counted;
+ *  e. holes: a boundary edge is used by exactly one face and directed as that face traverses it; a hole is a cycle of
+ *     boundary edges whose vertices all have exactly one incoming and one outgoing boundary edge.  Holes of at most
+ *     max_hole_edges edges (0..64; 4 = what trimesh.repair.fill_holes fills) get a fan from their smallest vertex index:
+ *     with the loop in boundary direction v0, v1, ..., v(n-1), the faces (v0, v(k+1), v(k)), k = 1 .. n-2, appended after
+ *     the surviving input faces, holes by ascending v0, k ascending.  Longer holes, holes through a vertex with several
+ *     boundary edges and every boundary of an unorientable component are left;
+ *  f. components are taken again with the new faces; one without a boundary edge whose six-fold signed volume (float64,
+ *     fixed order) is negative is flipped whole; zero volume or an open component: not flipped;
+ *  g. unreferenced vertices go, the others keep the order of their representatives; faces keep the order of their input
+ *     ids, added faces behind them; a face flipped (in d or f, not both) is written (a, c, b).
+ * report_host [16] int64:
+ *   [0] n_verts | n_faces << 32 (the input)   [1] vertices out   [2] faces out   [3] vertices welded away
+ *   [4] collapsed faces dropped   [5] duplicate faces dropped   [6] degenerate faces kept   [7] faces flipped in d
+ *   [8] components (of f)   [9] unorientable components (of d)   [10] components inverted   [11] holes filled
+ *   [12] faces added   [13] holes left: connected groups of the boundary edges that remain (two holes through one vertex
+ *   are one group)   [14] boundary edges left | edges of more than two faces << 32
+ *   [15] verdict bits: 1 watertight (no boundary edge, no edge of more than two faces), 2 winding_consistent (every edge
+ *   of exactly two faces is traversed once in each direction), 4 is_volume (both, and the total signed volume > 0).
+ * Capacity: every added face closes a hole of n >= 3 boundary edges with n - 2 faces, holes share no boundary edge and a
+ * surviving face has 3 edges, so faces added <= 3 faces - 2 holes: cap_faces = 4 * n_faces and cap_verts = n_verts
+ * always suffice (n_faces + 3 n_faces (K - 2) / K for max_hole_edges = K >= 3; n_faces below).  Smaller buffers:
+ * P2S_EINVAL with the needed counts in report [1], [2], nothing written.  n_faces = 0 is legal (n_verts = 0 too) and so
+ * is an empty result.  face_src_out_dev [cap_faces]: the input face id, -1 for an added face.  Build scratch comes from
+ * the device's block cache and returns to it before the call ends.  Synchronises `stream`. */
+int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const int32_t *faces_dev, int64_t n_faces, int max_hole_edges,
+                    float *verts_out_dev, int64_t cap_verts, int32_t *faces_out_dev, int32_t *face_src_out_dev, int64_t cap_faces,
+                    int64_t *report_host, int device, void *stream);
+#define P2S_EFLAT        -7   /* p2s_mesh_normalize: the bounding box has a zero extent on an axis (the reference skips the mesh) */
+/* _normalize_mesh: in float64 c = (lo + hi) / 2, s = 1 / max extent, v' = (double(v) - c) * s, rounded once to float32
+ * (contraction off).  verts_out_dev may be verts_dev.  info_host [4] (may be NULL): c, s.  A non-finite vertex or
+ * n_verts < 1: P2S_EINVAL; a zero extent on any axis: P2S_EFLAT; nothing written then.  Synchronises `stream`. */
+int p2s_mesh_normalize(const float *verts_dev, int64_t n_verts, float *verts_out_dev, double *info_host, int device, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * "next" row: the per-shape text / debug files of save_evaluation and implicit_surface_to_mesh, written
  * by native HOST code (no device is touched; all pointers are host pointers).  Byte-identical to what the reference's
  * numpy / Python calls write.

@@ -25,6 +25,7 @@
 //                             certified error bound, near leaf cells exactly (p2s_mesh_winding, p2s_mesh_distance signed_ 2)
 //   p2s_md_wsign_kernel       sign of the distance from that winding number
 // First-hit ray casting, the time-of-flight scan and the query points on the same handle: p2s_meshray.inl (end of file).
+// Repair and normalisation of a raw mesh with the same edge table, components, scan and volume sums: p2s_meshrepair.inl.
 //
 // The pseudonormal sign holds for ONE closed surface that does not intersect itself.  A closed mesh of several connected
 // components may be a union of overlapping solids (the reference's 00011084 is: 170 of its 2,000 GT queries lie just outside
@@ -1528,3 +1529,4 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
 // ray casting, time-of-flight scan and query points on the same handle
 // ---------------------------------------------------------------------------------------------
 #include "p2s_meshray.inl"
+#include "p2s_meshrepair.inl"
