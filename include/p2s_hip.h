@@ -354,6 +354,10 @@ int p2s_subsample_workers(p2s_cloud_t c, const p2s_worker_streams *ws, const flo
 int p2s_model_capture_logits(p2s_model_t m, float *logits_out_dev, int64_t capacity_queries);
 /* test hook: the next pipeline call on this model fails with P2S_EHIP before chunk `chunk_index` (-1 = off) */
 int p2s_debug_fault_chunk(p2s_model_t m, int chunk_index);
+/* test hook: the pooled features of the STN pass, [2 encoders: local, global][n_queries][1024], as the last
+ * p2s_encode_decode / p2s_encode_features call of n_queries <= 8192 queries (one internal batch) left them in the model's
+ * workspace, copied to out_dev on `stream` (the stream of that call) */
+int p2s_debug_stn_pool(p2s_model_t m, int n_queries, float *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * "next" row: the consumer of the SDF samples.  add_samples_to_volume + propagate_sign
@@ -578,7 +582,15 @@ typedef struct {
     int64_t launches_chain;      /* number of point-chain kernel launches (2 per chunk; 3 with a QSTN) */
     double  ms_chain_qstn;       /* QSTN trunk launch (models with use_point_stn); its head layers count under ms_stn_head */
     int64_t fallback_queries;    /* fp16 pair encoder: queries of the call re-run through the fp32 kernels (activation > 6e4) */
-    double  reserved[6];
+    /* fp32 encoders, screened conv3 (0 with P2S_CONV3_DENSE=1 or where the dense conv3 runs).  The three took
+       the place of three reserved slots: the size and the earlier members of the struct are unchanged.  They are counted on
+       the device: p2s_get_counters copies them to the host (a blocking copy) and they are those of the last call only once
+       the stream that call ran on has been synchronised */
+    int64_t conv3_confirmed;     /* fp32 dot products computed for the max-pools of the screened items */
+    int64_t conv3_items_dense;   /* items the screen could not decide (activation beyond the half range, ties beyond the
+                                    candidate queue): run again through the dense conv3 inside the same kernel */
+    int64_t conv3_items;         /* (query, encoder, pass) items that entered the screened kernel */
+    double  reserved[3];
 } p2s_counters;
 int p2s_set_profiling(p2s_model_t m, int enabled);
 int p2s_get_counters(p2s_model_t m, p2s_counters *out);

@@ -23,7 +23,8 @@ class Counters(ctypes.Structure):
                 ('ms_knn', ctypes.c_double), ('ms_subsample', ctypes.c_double), ('ms_grid', ctypes.c_double),
                 ('queries', ctypes.c_int64), ('launches_chain', ctypes.c_int64),
                 ('ms_chain_qstn', ctypes.c_double), ('fallback_queries', ctypes.c_int64),
-                ('reserved', ctypes.c_double * 6)]
+                ('conv3_confirmed', ctypes.c_int64), ('conv3_items_dense', ctypes.c_int64), ('conv3_items', ctypes.c_int64),
+                ('reserved', ctypes.c_double * 3)]
 
 
 # name -> (restype, argtypes): every symbol include/p2s_hip.h declares
@@ -70,6 +71,7 @@ PROTOTYPES = {
     'p2s_random_rotations': (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     'p2s_rotate_points': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     'p2s_debug_fault_chunk': (c_int, [c_void_p, c_int]),
+    'p2s_debug_stn_pool': (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     'p2s_sdf_volume': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, ctypes.c_float, c_int, c_int, c_void_p,
                                ctypes.POINTER(ctypes.c_int32), c_void_p]),
     'p2s_marching_cubes': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int64),

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <algorithm>
 #include <mutex>
+#include <cstdlib>
 
 static thread_local char g_err[512] = "";
 
@@ -50,6 +51,43 @@ void *P2sScratchLock::get(size_t bytes) {
     return sl.p;
 }
 
+// the operands of the screened conv3 (p2s_chain_screen.inl) of the fp32 encoders (mode 0; the 16-bit modes are untouched: the
+// fp32 re-run of the fp16 pair mode takes queries with an activation beyond the half range, which the screen would hand to the
+// dense conv3 anyway).  P2S_CONV3_DENSE=1, read here once, keeps the dense conv3 (the A/B switch); so does a conv3 weight that
+// does not fit the half range
+static int screen_init(p2s_model_s *m) {
+    if (m->cfg.encoder_bf16 != 0) return P2S_OK;
+    const char *dense = getenv("P2S_CONV3_DENSE");
+    if (dense && atoi(dense) != 0) return P2S_OK;
+    int *flag = nullptr;
+    bool ok = hipMalloc(&m->scr_w3h, (size_t)4 * 2 * P2S_SCR_PIECE * 2) == hipSuccess && hipMalloc(&m->scr_mu, (size_t)4 * 1024 * 4) == hipSuccess &&
+              hipMalloc(&m->scr_counters, 3 * 8) == hipSuccess && hipMalloc(&flag, 4) == hipSuccess &&
+              hipMemset(m->scr_counters, 0, 3 * 8) == hipSuccess && hipMemset(flag, 0, 4) == hipSuccess;
+    int rc = P2S_OK, h = 0;
+    if (!ok) {
+        (void)hipGetLastError();
+        p2s_set_error("hipMalloc(screen operands of conv3) failed");
+        rc = P2S_ENOMEM;
+    }
+    for (int i = 0; i < 4 && rc == P2S_OK; ++i) {
+        const P2sLayer layer = i < 2 ? L_S3 : L_M3;
+        rc = p2s_launch_screen_prepare(m->w32(layer, i & 1), const_cast<unsigned short *>(m->screen_w(layer, i & 1)),
+                                       const_cast<float *>(m->screen_mu(layer, i & 1)), nullptr, flag);
+    }
+    if (rc == P2S_OK && hipMemcpy(&h, flag, 4, hipMemcpyDeviceToHost) != hipSuccess) {
+        p2s_set_error("hipMemcpy(conv3 range flag) failed");
+        rc = P2S_EHIP;
+    }
+    if (flag) (void)hipFree(flag);
+    if (rc == P2S_OK && h) {          // a conv3 weight beyond the half range: this model keeps the dense conv3
+        (void)hipFree(m->scr_w3h);
+        (void)hipFree(m->scr_mu);
+        m->scr_w3h = nullptr;
+        m->scr_mu = nullptr;
+    }
+    return rc;
+}
+
 // p2s_model_create: the device side of a new handle; on failure the caller destroys the half-built handle and frees *wflag
 static int model_init(p2s_model_s *m, const float *blob_host, size_t n_floats, int **wflag) {
     const p2s_model_cfg &cfg = m->cfg;
@@ -64,6 +102,10 @@ static int model_init(p2s_model_s *m, const float *blob_host, size_t n_floats, i
         return P2S_EHIP;
     }
     const Precision prec = p2s_precision(cfg);
+    {
+        const int rc = screen_init(m);
+        if (rc) return rc;
+    }
     if (!prec.pieces) return P2S_OK;
     // 16-bit fragments of the layers that have them in this mode, packed on the device from the fp32 fragments: blob_h holds
     // the kinds of p2s_layers in turn, a per-encoder kind encoder by encoder
@@ -197,6 +239,9 @@ int p2s_model_destroy(p2s_model_t m) {
     if (m->ws) (void)hipFree(m->ws);
     if (m->blob) (void)hipFree(m->blob);
     if (m->blob_h) (void)hipFree(m->blob_h);
+    if (m->scr_w3h) (void)hipFree(m->scr_w3h);
+    if (m->scr_mu) (void)hipFree(m->scr_mu);
+    if (m->scr_counters) (void)hipFree(m->scr_counters);
     for (void *p : {(void *)m->fb.flags, (void *)m->fb.count, (void *)m->fb.patch, (void *)m->fb.sub, (void *)m->fb.query,
                     (void *)m->fb.radius, (void *)m->fb.index, (void *)m->fb.sdf, (void *)m->fb.logits})
         if (p) (void)hipFree(p);
@@ -217,6 +262,14 @@ int p2s_set_profiling(p2s_model_t m, int enabled) {
 int p2s_get_counters(p2s_model_t m, p2s_counters *out) {
     if (!m || !out) return P2S_EINVAL;
     *out = m->counters;
+    if (m->scr_counters) {            // the screened conv3 counts on the device; valid once the call's stream is synchronised
+        unsigned long long h[3] = {};
+        P2S_HIP_CHECK(hipSetDevice(m->device));
+        P2S_HIP_CHECK(hipMemcpy(h, m->scr_counters, sizeof(h), hipMemcpyDeviceToHost));
+        out->conv3_confirmed = (int64_t)h[0];
+        out->conv3_items_dense = (int64_t)h[1];
+        out->conv3_items = (int64_t)h[2];
+    }
     return P2S_OK;
 }
 
@@ -281,6 +334,7 @@ ModelCall::ModelCall(p2s_model_s *m_, hipStream_t s_, bool pipeline_) : m(m_), s
     rc = [&]() -> int {
         P2S_HIP_CHECK(hipSetDevice(m->device));
         prof_reset(m);
+        if (m->scr_counters) P2S_HIP_CHECK(hipMemsetAsync(m->scr_counters, 0, 3 * 8, s));
         if (m->fb.count) {
             P2S_HIP_CHECK(hipMemsetAsync(m->fb.count, 0, 4, s));
             P2S_HIP_CHECK(hipMemsetAsync(m->fb.flags, 0, (size_t)m->max_chunk * 4, s));

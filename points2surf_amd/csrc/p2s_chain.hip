@@ -25,6 +25,7 @@
 // Padding rows of the last tile replicate the item's last point (max is idempotent).
 #include "p2s_common.h"
 #include <cstdlib>
+#include <atomic>
 
 namespace {
 
@@ -205,9 +206,85 @@ __device__ __forceinline__ float half_sum(float m) {
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-template <bool SUM>
-__global__ __launch_bounds__(256, 3) void p2s_chain_kernel(ChainArgs args) {
-    __shared__ __attribute__((aligned(16))) float smem[MT * SA + MT * SB];
+// ---- screened conv3 (p2s_chain_screen.inl) --------------------------------------------------------------------------
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+constexpr int SCR_HB = 128 + 8;      // halfs per row of an fp16 piece of the conv2 output tile (the fp16 pair kernel's layout)
+constexpr int SCR_QCAP = 256;        // candidates a wave's queue holds: < 64 left over + what one column tile may add
+constexpr float P2S_SCR_KAPPA = 0x1p-14f;   // k_screen + k_fp32 of the margin (derived in p2s_chain_screen.inl)
+// LDS of the screened kernel (floats): the two fp32 tiles, the h1 piece (h0 lies over bufA), the exact pool E [1024], the four
+// waves' candidate queues, the reduction scratch
+constexpr int SCR_OFF_H1 = MT * SA + MT * SB;
+constexpr int SCR_OFF_E = SCR_OFF_H1 + MT * SCR_HB / 2;
+constexpr int SCR_OFF_Q = SCR_OFF_E + 1024;
+constexpr int SCR_OFF_RED = SCR_OFF_Q + 4 * SCR_QCAP;
+constexpr int SCR_LDS_FLOATS = SCR_OFF_RED + 8;
+static_assert(MT * SCR_HB * 2 <= MT * SA * 4, "the h0 piece fits the 64-channel tile it lies over");
+static_assert(2 * SCR_LDS_FLOATS * 4 <= 160 * 1024, "two workgroups per CU");
+
+__device__ __forceinline__ u32x4 scr_bufld(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
+    return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
+}
+// A fragment of rows row0 .. row0+31, k-block kb of one fp16 piece: 8 consecutive k of row l & 31, k = 16 kb + 8 (l >> 5) + [0, 8)
+__device__ __forceinline__ u32x4 scr_lds_a(const unsigned short *buf, int row0, int kb, int lane) {
+    return *reinterpret_cast<const u32x4 *>(buf + (row0 + (lane & 31)) * SCR_HB + 16 * kb + 8 * (lane >> 5));
+}
+__device__ __forceinline__ f32x16 scr_mfma(u32x4 a, u32x4 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+// two fp32 values -> their fp16 pairs, packed (a low half): h0 = fp16(x), h1 = fp16((x - h0) * 2^11)
+__device__ __forceinline__ void scr_split(float a, float b, unsigned &p0, unsigned &p1) {
+    const f32x2 v = {a, b};
+    const f16x2 h = __builtin_convertvector(v, f16x2);
+    p0 = __builtin_bit_cast(unsigned, h);
+    const f32x2 r = {(a - (float)h[0]) * 2048.0f, (b - (float)h[1]) * 2048.0f};
+    p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
+}
+// One candidate (entry = row << 16 | channel within the wave's 256): the fp32 dot product of row `row` of the conv2 tile with
+// column c of the packed conv3 fragments ([N/32][16][2][32][4]: k = 8 g + 4 kk + t), summed as the dense kernel's MFMA chain
+// sums it -- g ascending, t = 0..3, k = 8g+t then 8g+4+t into one accumulator; a row of the 16-row tail (`split`): the kk = 0
+// and the kk = 1 chain apart, then their sum (tail_colmax) -- and pooled into E[channel] by an order-preserving integer max
+__device__ __forceinline__ void scr_confirm(unsigned entry, const float *hB, const float *__restrict__ w3, int wave, bool tail,
+                                            float *E) {
+    const int row = (int)(entry >> 16), cw = (int)(entry & 0xffffu);
+    const int c = 256 * wave + cw;
+    const float *hrow = hB + row * SB;
+    const float *wcol = w3 + ((long long)(c >> 5) * (16 * 64) + (c & 31)) * 4;
+    const bool split = tail && row >= 32;
+    float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll 4
+    for (int g = 0; g < 16; ++g) {
+        const f32x4 ha = lds4(hrow + 8 * g), hb = lds4(hrow + 8 * g + 4);
+        const f32x4 wa = ldg4(wcol + g * 256), wb = ldg4(wcol + g * 256 + 128);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            s0 = fmaf(ha[t], wa[t], s0);
+            const float x = fmaf(hb[t], wb[t], split ? s1 : s0);
+            s1 = split ? x : s1;
+            s0 = split ? s0 : x;
+        }
+    }
+    const float s = split ? s0 + s1 : s0;
+    const int bits = (int)__float_as_uint(s);
+    if (bits >= 0) atomicMax(reinterpret_cast<int *>(E + cw), bits);
+    else atomicMin(reinterpret_cast<unsigned *>(E + cw), (unsigned)bits);
+}
+
+// SCREEN (max pool, full chain only): conv3 through p2s_chain_screen.inl, two workgroups per CU (78 KB of LDS); an item the
+// screen cannot decide runs a second time with the dense conv3 below
+template <bool SUM, bool SCREEN = false>
+__global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArgs args) {
+    static_assert(!(SUM && SCREEN), "the screen selects for a max");
+    float *smem;
+    if constexpr (SCREEN) {
+        extern __shared__ __attribute__((aligned(16))) float smem_screen[];
+        smem = smem_screen;
+    } else {
+        __shared__ __attribute__((aligned(16))) float smem_dense[MT * SA + MT * SB];
+        smem = smem_dense;
+    }
     float *bufA = smem;
     float *bufB = smem + MT * SA;
 
@@ -273,12 +350,29 @@ __global__ __launch_bounds__(256, 3) void p2s_chain_kernel(ChainArgs args) {
     };
 
 #ifdef P2S_DEV_ABLATE
-    const int ablate = args.ablate;   // timing-only variants (wrong results): tools/ablate.sh builds with -DP2S_DEV_ABLATE
+    const int ablate = args.ablate;   // timing-only variants (wrong results): tools/ablate.sh builds with -DP2S_DEV_ABLATE=<variant>
 #else
     constexpr int ablate = 0;
 #endif
     const int ntiles = (P + MT - 1) / MT;
     float nx0, nx1, nx2;
+    // screened conv3: the state of p2s_chain_screen.inl
+    float *scr_h1 = smem + SCR_OFF_H1, *scr_E = smem + SCR_OFF_E + 256 * wave, *scr_red = smem + SCR_OFF_RED;
+    unsigned *scr_q = reinterpret_cast<unsigned *>(smem + SCR_OFF_Q) + SCR_QCAP * wave;
+    const float *__restrict__ scr_mu = args.w3mu[bsel];
+    const __amdgpu_buffer_rsrc_t rs3h = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(args.w3h[bsel]), 0,
+                                                                           (int)(P2S_SCR_PIECE * 4), 0x00020000);
+    float sr0 = -INFINITY, sr1 = -INFINITY, sr2 = -INFINITY, sr3 = -INFINITY, sr4 = -INFINITY, sr5 = -INFINITY, sr6 = -INFINITY,
+          sr7 = -INFINITY;                     // running maxima of the screen values of this lane's column of the 8 column tiles
+    bool undec = false;                        // the screen cannot decide this item (wave-uniform)
+    float scr_Hsq = 0.0f;                      // largest squared row norm of the conv2 tiles of the item so far
+    int nconf = 0;                             // fp32 chains this wave ran
+    bool dense_pass = !SCREEN;
+    if constexpr (SCREEN) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) scr_E[64 * i + lane] = -INFINITY;
+    }
+    for (;;) {
     load_point(0, nx0, nx1, nx2);
     for (int tile = 0; tile < ntiles; ++tile) {
       f32x4 bA0, bA1, aA0, aA1, bB0, bB1, aB0, aB1;   // conv3 operand register sets
@@ -288,9 +382,14 @@ __global__ __launch_bounds__(256, 3) void p2s_chain_kernel(ChainArgs args) {
         if (!short_chain) load_b8(wb, rs0b, lane16, (wave & 1) * 8192);      // conv0b weights, in flight across the barrier
         else load_b8(wb, rs2, lane16, wave * 8192);
         if (has_rot) {
-            const float y0 = R[0] * x0 + R[1] * x1 + R[2] * x2;
-            const float y1 = R[3] * x0 + R[4] * x1 + R[5] * x2;
-            const float y2 = R[6] * x0 + R[7] * x1 + R[8] * x2;
+            // spelled out, contraction off: left to the compiler, the choice of which products fuse differed between the
+            // instantiations of this kernel, and the screened and the dense conv3 must see the same points bit for bit.
+            // The pattern is the one the compiler had chosen for the dense kernel before (read off its disassembly: y0's
+            // third product is rounded on its own and added, y1 / y2 are two nested fma), so its results are unchanged
+#pragma clang fp contract(off)
+            const float y0 = __builtin_fmaf(R[0], x0, R[1] * x1) + R[2] * x2;
+            const float y1 = __builtin_fmaf(R[5], x2, __builtin_fmaf(R[3], x0, R[4] * x1));
+            const float y2 = __builtin_fmaf(R[8], x2, __builtin_fmaf(R[6], x0, R[7] * x1));
             x0 = y0; x1 = y1; x2 = y2;
         }
         bad = bad || !(fabsf(x0) <= 3.0e38f) || !(fabsf(x1) <= 3.0e38f) || !(fabsf(x2) <= 3.0e38f);
@@ -339,8 +438,10 @@ __global__ __launch_bounds__(256, 3) void p2s_chain_kernel(ChainArgs args) {
             f32x16 acc[2];
             layer_k64<2>(bufA, SA, 0, wb, lane, acc);
             // first conv3 weight fragments, in flight across the barrier
-            bA0 = bufld4(w3rsrc, lane16, w3soff);
-            bA1 = bufld4(w3rsrc, lane16, w3soff + 16 * 1024);
+            if (!SCREEN || dense_pass) {
+                bA0 = bufld4(w3rsrc, lane16, w3soff);
+                bA1 = bufld4(w3rsrc, lane16, w3soff + 16 * 1024);
+            }
             store_tile_bias_relu(acc[0], bufB, SB, 0, 32 * wave, br.b2, lane);
             store_tile_bias_relu(acc[1], bufB, SB, 32, 32 * wave, br.b2, lane);
         }
@@ -350,6 +451,12 @@ __global__ __launch_bounds__(256, 3) void p2s_chain_kernel(ChainArgs args) {
         bA1 = bufld4(w3rsrc, lane16, w3soff + 16 * 1024);
       }
       if (ablate == 2) continue;
+      if constexpr (SCREEN) {
+        if (!dense_pass) {
+#include "p2s_chain_screen.inl"
+            continue;
+        }
+      }
         // ---- conv3 (K = 128, N = 1024) + running max over points -----------------------------------
         // wave w owns channels [256w, 256w+256) = 8 column tiles, processed as 4 pairs with a
         // 2 (row tiles) x 2 (column tiles) register block: 64 accumulator registers.
@@ -368,6 +475,30 @@ __global__ __launch_bounds__(256, 3) void p2s_chain_kernel(ChainArgs args) {
 #undef P2S_TAIL
         }
         // next tile's first layer writes bufA, whose last readers (conv2) are behind the barrier above
+    }
+    if constexpr (SCREEN) {
+        if (!dense_pass) {
+            // the item's verdict: one wave that could not decide sends the whole workgroup through the dense conv3
+            if (lane == 0) scr_red[4 + wave] = undec ? 1.0f : 0.0f;
+            __syncthreads();
+            const bool redo = (scr_red[4] + scr_red[5] + scr_red[6] + scr_red[7]) != 0.0f;
+            if (args.scr_counters) {
+                if (lane == 0 && !redo) atomicAdd(args.scr_counters + 0, (unsigned long long)nconf);
+                if (tid == 0) {
+                    atomicAdd(args.scr_counters + 2, 1ull);
+                    if (redo) atomicAdd(args.scr_counters + 1, 1ull);
+                }
+            }
+            if (redo) {
+                dense_pass = true;
+                continue;
+            }
+            __builtin_amdgcn_wave_barrier();
+            rm0 = scr_E[(lane & 31)];       rm1 = scr_E[32 + (lane & 31)];  rm2 = scr_E[64 + (lane & 31)];  rm3 = scr_E[96 + (lane & 31)];
+            rm4 = scr_E[128 + (lane & 31)]; rm5 = scr_E[160 + (lane & 31)]; rm6 = scr_E[192 + (lane & 31)]; rm7 = scr_E[224 + (lane & 31)];
+        }
+    }
+    break;
     }
 
     // ---- pooled affine epilogue: out = [relu](max + bias) ------------------------------------------
@@ -461,15 +592,60 @@ int p2s_launch_chain(const ChainArgs &args_in, hipStream_t stream) {
     ChainArgs args = args_in;
     constexpr int padlds = 0;
 #ifdef P2S_DEV_ABLATE
-    static const int ablate = getenv("P2S_CHAIN_ABLATE") ? atoi(getenv("P2S_CHAIN_ABLATE")) : 0;
-    args.ablate = ablate;
+    args.ablate = P2S_DEV_ABLATE + 0;      // the variant is the value of the define (1 = conv3 only, 2 = all but conv3)
 #endif
     // both branches of a launch pool alike (pass 2 of a sym_op='sum' model: sum; every other launch: max)
-    if (args.br[0].pool_sum || (args.br[1].n_items > 0 && args.br[1].pool_sum))
+    const bool sum = args.br[0].pool_sum || (args.br[1].n_items > 0 && args.br[1].pool_sum);
+    if (args.screen) {
+        if (sum || args.br[0].short_chain || (args.br[1].n_items > 0 && args.br[1].short_chain) || !args.w3h[0] || !args.w3mu[0] ||
+            (args.br[1].n_items > 0 && (!args.w3h[1] || !args.w3mu[1]))) {
+            p2s_set_error("p2s_launch_chain: the screened conv3 takes full-chain max-pool passes with their screen operands");
+            return P2S_EINVAL;
+        }
+        // the kernel's LDS exceeds the default limit: raised once per device
+        static std::atomic<bool> lds_set[P2S_MAX_DEVICES];
+        int dev = 0;
+        P2S_HIP_CHECK(hipGetDevice(&dev));
+        if (dev < 0 || dev >= P2S_MAX_DEVICES || !lds_set[dev].load()) {
+            const hipError_t attr = hipFuncSetAttribute((const void *)p2s_chain_kernel<false, true>,
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, SCR_LDS_FLOATS * 4);
+            if (attr != hipSuccess) {
+                p2s_set_error("p2s_launch_chain: %d bytes of LDS for the screened conv3 refused: %s", SCR_LDS_FLOATS * 4, hipGetErrorString(attr));
+                return P2S_EHIP;
+            }
+            if (dev >= 0 && dev < P2S_MAX_DEVICES) lds_set[dev].store(true);
+        }
+        hipLaunchKernelGGL((p2s_chain_kernel<false, true>), dim3(n), dim3(256), SCR_LDS_FLOATS * 4, stream, args);
+    } else if (sum)
         hipLaunchKernelGGL(p2s_chain_kernel<true>, dim3(n), dim3(256), padlds, stream, args);
     else
         hipLaunchKernelGGL(p2s_chain_kernel<false>, dim3(n), dim3(256), padlds, stream, args);
     P2S_LAUNCH_CHECK("p2s_chain_kernel");
+    return P2S_OK;
+}
+
+// margin coefficient of the screened conv3, one thread per output channel: 2 kappa (|w_c| + 2^-10), |w_c| in double from the
+// packed fp32 fragments and rounded up
+__global__ void p2s_screen_mu_kernel(const float *__restrict__ w3, float *__restrict__ mu) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= 1024) return;
+    double ss = 0.0;
+    for (int g = 0; g < 16; ++g)
+        for (int u = 0; u < 8; ++u) {
+            const double w = w3[(((long long)(c >> 5) * 16 + g) * 64 + (u >> 2) * 32 + (c & 31)) * 4 + (u & 3)];
+            ss += w * w;
+        }
+    const float norm = (float)(sqrt(ss) * (1.0 + 0x1p-20));
+    mu[c] = 2.0f * P2S_SCR_KAPPA * (norm * (1.0f + 0x1p-10f) + 0x1p-10f);
+}
+
+int p2s_launch_screen_prepare(const float *w32, unsigned short *dst, float *mu, hipStream_t stream, int *range_flag) {
+    for (int piece = 0; piece < 2; ++piece) {
+        const int rc = p2s_launch_pack_bf16(w32, dst + piece * P2S_SCR_PIECE, 128, 1024, 0, 0, 1, piece, 1, stream, range_flag);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(p2s_screen_mu_kernel, dim3(4), dim3(256), 0, stream, w32, mu);
+    P2S_LAUNCH_CHECK("p2s_screen_mu_kernel");
     return P2S_OK;
 }
 

@@ -101,8 +101,20 @@ ChainArgs chain_args(const Chunk &c) {
     a.w1_piece_stride = (long long)2 * c.C * 4096;
     return a;
 }
-int launch_chain(const ChainArgs &a, const Chunk &c, hipStream_t s) {
-    return c.prec.pieces ? p2s_launch_chain_bf16(a, s) : p2s_launch_chain(a, s);
+// an fp32 run of the STN or main pass (slot 0 = encoder 1, slot 1 = encoder 0): conv3 is screened where the model holds the
+// screen operands and the pass pools by max
+int launch_chain(ChainArgs &a, const Chunk &c, hipStream_t s, Pass pass = PASS_QSTN) {
+    if (c.prec.pieces) return p2s_launch_chain_bf16(a, s);
+    a.screen = pass != PASS_QSTN && c.m->scr_w3h && !a.br[0].pool_sum && !a.br[1].pool_sum;
+    if (a.screen) {
+        const P2sLayer l3 = pass == PASS_STN ? L_S3 : L_M3;
+        for (int slot = 0; slot < 2; ++slot) {
+            a.w3h[slot] = c.m->screen_w(l3, 1 - slot);
+            a.w3mu[slot] = c.m->screen_mu(l3, 1 - slot);
+        }
+        a.scr_counters = c.m->scr_counters;
+    }
+    return p2s_launch_chain(a, s);
 }
 
 // FC layer `layer` over the g.Z slices of dense rows A [Z][C][K] -> out (+ z * c_z) [C][ldc]; g keeps M, Z, relu and A2.  The
@@ -224,7 +236,7 @@ int p2s_run_chunk(p2s_model_s *m, Precision prec, const float *patch, const floa
     // ---- pass 1: stem + STN trunk + max-pool, both encoders (global items first: longest first) ----
     ChainArgs a = chain_args(c);
     for (int slot = 0; slot < 2; ++slot) fill_branch(a.br[slot], c, PASS_STN, 1 - slot);   // slot 0 = feat_global (e=1), slot 1 = feat_local (e=0)
-    if ((rc = launch_chain(a, c, s))) return rc;
+    if ((rc = launch_chain(a, c, s, PASS_STN))) return rc;
     const int ev1 = p2s_prof_mark(m, s);
 
     // ---- STN head: 1024 -> 512 -> 256 -> 4096 (+I), then W1' = W1 . trans2 -------------------------
@@ -258,7 +270,7 @@ int p2s_run_chunk(p2s_model_s *m, Precision prec, const float *patch, const floa
 
     // ---- pass 2: stem (recomputed) + transformed conv1 + conv2 + conv3 + max-pool -------------------
     for (int slot = 0; slot < 2; ++slot) fill_branch(a.br[slot], c, PASS_MAIN, 1 - slot);
-    if ((rc = launch_chain(a, c, s))) return rc;
+    if ((rc = launch_chain(a, c, s, PASS_MAIN))) return rc;
     const int ev3 = p2s_prof_mark(m, s);
     m->counters.launches_chain += 2;
 
@@ -299,6 +311,17 @@ int p2s_run_chunk(p2s_model_s *m, Precision prec, const float *patch, const floa
                            radius, m->cfg.points_per_patch * 3, m->cfg.sub_sample_size * 3, index0, m->fb.patch, m->fb.sub, m->fb.query, m->fb.radius, m->fb.index);
         P2S_LAUNCH_CHECK("p2s_fb_collect_kernel");
     }
+    return P2S_OK;
+}
+
+extern "C" int p2s_debug_stn_pool(p2s_model_t m, int n_queries, float *out_dev, void *stream) {
+    if (!m || !out_dev || n_queries < 1 || n_queries > m->ws_chunk || n_queries > m->max_chunk) {
+        p2s_set_error("p2s_debug_stn_pool: no workspace of a call of %d queries (one internal batch)", n_queries);
+        return P2S_EINVAL;
+    }
+    P2S_HIP_CHECK(hipSetDevice(m->device));
+    const Ws w = carve(m->ws, m->cfg, p2s_precision(m->cfg), n_queries);
+    P2S_HIP_CHECK(hipMemcpyAsync(out_dev, w.g_stn, (size_t)2 * n_queries * 1024 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return P2S_OK;
 }
 

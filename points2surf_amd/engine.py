@@ -124,6 +124,13 @@ class Model:
         """test hook: the next pipeline call fails with P2S_EHIP before chunk ``chunk_index`` (-1 = off)"""
         _lib.check(self.lib.p2s_debug_fault_chunk(self.handle, int(chunk_index)))
 
+    def debug_stn_pool(self, n_queries):
+        """test hook: the pooled STN-pass features [2 (local, global), n_queries, 1024] of the last forward / features call"""
+        out = torch.empty((2, n_queries, 1024), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.p2s_debug_stn_pool(self.handle, int(n_queries), _ptr(out), _stream_ptr(self.device)))
+        return out
+
     def set_profiling(self, on):
         _lib.check(self.lib.p2s_set_profiling(self.handle, int(bool(on))))
 

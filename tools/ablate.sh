@@ -1,13 +1,9 @@
 #!/bin/bash
-# timing-only ablations of the chain kernel (development aid).  Needs a library built with the ablation switch:
-#   P2S_EXTRA_HIPCC_FLAGS=-DP2S_DEV_ABLATE python -m points2surf_amd.build --force
-run() {
-  python tools/quick_bench.py --B 4096 --iters 3 2>/dev/null | tail -1 | python -c '
+# timing of the chain kernel of the library that is loaded (development aid).  The timing-only ablations are build variants,
+# -DP2S_DEV_ABLATE=<variant> (1 = conv3 only, 2 = all but conv3; the results of such a build are wrong).  Build one beside the
+# shipped library and point P2S_LIB_PATH at it; this script builds nothing and replaces nothing:
+#   P2S_LIB_PATH=/path/to/variant/libp2s_hip.so tools/ablate.sh
+python tools/quick_bench.py --B 4096 --iters 3 2>/dev/null | tail -1 | python -c '
 import sys, json
 d = json.loads(sys.stdin.read())
 print(round(d["ms"], 2), "ms; chain_stn", round(d["stages_ms"]["ms_chain_stn"], 2), "chain_main", round(d["stages_ms"]["ms_chain_main"], 2))'
-}
-for ab in ${ABL:-0 1 2}; do
-  echo -n "ablate=$ab: "
-  P2S_CHAIN_ABLATE=$ab run
-done
