@@ -244,15 +244,15 @@ __device__ __forceinline__ void scr_split(float a, float b, unsigned &p0, unsign
 }
 // One candidate (entry = row << 16 | channel within the wave's 256): the fp32 dot product of row `row` of the conv2 tile with
 // column c of the packed conv3 fragments ([N/32][16][2][32][4]: k = 8 g + 4 kk + t), summed as the dense kernel's MFMA chain
-// sums it -- g ascending, t = 0..3, k = 8g+t then 8g+4+t into one accumulator; a row of the 16-row tail (`split`): the kk = 0
-// and the kk = 1 chain apart, then their sum (tail_colmax) -- and pooled into E[channel] by an order-preserving integer max
-__device__ __forceinline__ void scr_confirm(unsigned entry, const float *hB, const float *__restrict__ w3, int wave, bool tail,
-                                            float *E) {
+// sums it -- g ascending, t = 0..3, k = 8g+t then 8g+4+t into one accumulator; a row of the 16-row tail (SPLIT): the kk = 0
+// and the kk = 1 chain apart, then their sum (tail_colmax) -- and pooled into E[channel] by an order-preserving integer max.
+// The form is a template parameter, chosen per batch: a per-lane choice cost 16 selects beside the 8 fmaf of every k-group
+template <bool SPLIT>
+__device__ __forceinline__ void scr_confirm(unsigned entry, const float *hB, const float *__restrict__ w3, int wave, float *E) {
     const int row = (int)(entry >> 16), cw = (int)(entry & 0xffffu);
     const int c = 256 * wave + cw;
     const float *hrow = hB + row * SB;
     const float *wcol = w3 + ((long long)(c >> 5) * (16 * 64) + (c & 31)) * 4;
-    const bool split = tail && row >= 32;
     float s0 = 0.0f, s1 = 0.0f;
 #pragma unroll 4
     for (int g = 0; g < 16; ++g) {
@@ -261,12 +261,11 @@ __device__ __forceinline__ void scr_confirm(unsigned entry, const float *hB, con
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             s0 = fmaf(ha[t], wa[t], s0);
-            const float x = fmaf(hb[t], wb[t], split ? s1 : s0);
-            s1 = split ? x : s1;
-            s0 = split ? s0 : x;
+            if constexpr (SPLIT) s1 = fmaf(hb[t], wb[t], s1);
+            else s0 = fmaf(hb[t], wb[t], s0);
         }
     }
-    const float s = split ? s0 + s1 : s0;
+    const float s = SPLIT ? s0 + s1 : s0;
     const int bits = (int)__float_as_uint(s);
     if (bits >= 0) atomicMax(reinterpret_cast<int *>(E + cw), bits);
     else atomicMin(reinterpret_cast<unsigned *>(E + cw), (unsigned)bits);
@@ -351,8 +350,9 @@ __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArg
 
 #ifdef P2S_DEV_ABLATE
     const int ablate = args.ablate;   // timing-only variants (wrong results): tools/ablate.sh builds with -DP2S_DEV_ABLATE=<variant>
+    constexpr int scr_abl = P2S_DEV_ABLATE + 0;   // 3 .. 5, of the screened conv3, at compile time: its schedule stays the shipped one
 #else
-    constexpr int ablate = 0;
+    constexpr int ablate = 0, scr_abl = 0;
 #endif
     const int ntiles = (P + MT - 1) / MT;
     float nx0, nx1, nx2;
@@ -592,7 +592,7 @@ int p2s_launch_chain(const ChainArgs &args_in, hipStream_t stream) {
     ChainArgs args = args_in;
     constexpr int padlds = 0;
 #ifdef P2S_DEV_ABLATE
-    args.ablate = P2S_DEV_ABLATE + 0;      // the variant is the value of the define (1 = conv3 only, 2 = all but conv3)
+    args.ablate = P2S_DEV_ABLATE + 0;      // the variant is the value of the define (1 = conv3 only, 2 = all but conv3, 3 .. 5 = parts of the screen)
 #endif
     // both branches of a launch pool alike (pass 2 of a sym_op='sum' model: sum; every other launch: max)
     const bool sum = args.br[0].pool_sum || (args.br[1].n_items > 0 && args.br[1].pool_sum);

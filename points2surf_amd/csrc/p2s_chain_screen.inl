@@ -41,8 +41,22 @@
 {
             unsigned short *hp0 = reinterpret_cast<unsigned short *>(bufA);      // h0 [64][SCR_HB] over the conv2 input tile
             unsigned short *hp1 = reinterpret_cast<unsigned short *>(scr_h1);    // h1 [64][SCR_HB]
+            // ---- the weight stream: ONE ring over the tile's 8 column tiles x 8 k-blocks ---------------------------------
+            // A wave's fragments of consecutive k-blocks and column tiles are consecutive KBs of the packed pieces, so the
+            // stream does not know column tiles: the fragments of k-block j + 3 are requested while the MFMAs of k-block j
+            // issue (4 slots of 2 x 4 registers, 3 in flight), across the select, the queue and the confirm of a column tile
+            // too.  The first three are requested here and land during the split.  (The last three requests of a tile run
+            // past the wave's own fragments: they read the next wave's, or, past the end of the buffer, zeros; nothing uses them.)
+            const int soff0 = wave * 8 * 8 * 1024;          // bytes: 8 k-blocks of 64 lanes x 16 B per column tile
+            u32x4 rb0[4], rb1[4];
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                rb0[s] = scr_bufld(rs3h, lane16, soff0 + s * 1024);
+                rb1[s] = scr_bufld(rs3h, lane16, (int)(P2S_SCR_PIECE * 2) + soff0 + s * 1024);
+            }
+            float mu_c = scr_mu[256 * wave + (lane & 31)];                       // margin coefficient of column tile 0
             // ---- h -> fp16 pair beside the fp32 tile; row norms --------------------------------------------------------
-            {
+            if (scr_abl != 5) {
                 const int p = tid >> 2, q = tid & 3;
                 const float *src = bufB + p * SB + 32 * q;
                 float ss = 0.0f;
@@ -79,46 +93,92 @@
             scr_Hsq = fmaxf(scr_Hsq, fmaxf(fmaxf(scr_red[0], scr_red[1]), fmaxf(scr_red[2], scr_red[3])));
             const float Heff = sqrtf(scr_Hsq) * (1.0f + 0x1p-10f) + 0x1p-10f;
             const bool tail = tile == ntiles - 1 && P - tile * MT <= 48;         // the dense kernel's 16-row tail tile
-            // rows of this tile that are points of the item, as a mask over this lane's 32 values of a column
+            // rows of this tile that are points of the item, as a mask over this lane's 32 values of a column.  A tail tile with
+            // at most 32 points: the dense kernel pools its padded rows 32 .. 47 too, replicas of the last point summed by the
+            // two-chain form, while that point's own row takes the plain chain -- row 32 stands for them here
             unsigned vmask = 0;
             {
                 const int nvalid = P - tile * MT;
+                const bool replica = tail && nvalid <= 32;
 #pragma unroll
                 for (int j = 0; j < 32; ++j) {
                     const int row = 32 * (j >> 4) + (j & 3) + 8 * ((j & 15) >> 2) + 4 * (lane >> 5);
-                    vmask |= (row < nvalid ? 1u : 0u) << j;
+                    vmask |= (row < nvalid || (replica && row == 32) ? 1u : 0u) << j;
                 }
+            }
+            // A fragments one k-block ahead of their MFMAs; they are the same for every column tile, so k-block 7 fetches
+            // k-block 0 of the next one
+            u32x4 fa[2][2];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                fa[r][0] = scr_lds_a(hp0, 32 * r, 0, lane);
+                fa[r][1] = scr_lds_a(hp1, 32 * r, 0, lane);
             }
             int qn = 0;                                                          // entries in this wave's queue (wave-uniform)
 #pragma unroll 1
             for (int ct = 0; ct < 8; ++ct) {
-                const int soff = (wave * 8 + ct) * 8 * 1024;    // bytes: 8 k-blocks of 64 lanes x 16 B per column tile
-                const float mu = scr_mu[256 * wave + 32 * ct + (lane & 31)] * Heff;
+                const int soff = soff0 + ct * 8 * 1024;
                 f32x16 acc[2][2];
-#pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    acc[r][0] = zero16();
-                    acc[r][1] = zero16();
-                }
+                // per accumulator the order of the products is a1 b0, a0 b1 (acc1) and a0 b0 (acc0), k-blocks ascending; the two
+                // row tiles alternate so that no MFMA follows one it depends on.  One memory instruction per MFMA shadow.
 #pragma unroll
                 for (int kb = 0; kb < 8; ++kb) {
-                    const u32x4 b0 = scr_bufld(rs3h, lane16, soff + kb * 1024);
-                    const u32x4 b1 = scr_bufld(rs3h, lane16, (int)(P2S_SCR_PIECE * 2) + soff + kb * 1024);
+                    const int use = kb & 3, req = (kb + 3) & 3;
+                    const u32x4 b0 = rb0[use], b1 = rb1[use];
+                    rb0[req] = scr_bufld(rs3h, lane16, soff + (kb + 3) * 1024);
+                    rb1[req] = scr_bufld(rs3h, lane16, (int)(P2S_SCR_PIECE * 2) + soff + (kb + 3) * 1024);
+                    u32x4 na[2][2];
+                    // the h1 fragments first: their registers are free after the first two MFMAs
+                    na[0][1] = scr_lds_a(hp1, 0, (kb + 1) & 7, lane);
+                    na[1][1] = scr_lds_a(hp1, 32, (kb + 1) & 7, lane);
+                    na[0][0] = scr_lds_a(hp0, 0, (kb + 1) & 7, lane);
+                    na[1][0] = scr_lds_a(hp0, 32, (kb + 1) & 7, lane);
+                    if (kb == 0) {
+                        acc[0][1] = scr_mfma(fa[0][1], b0, zero16());
+                        acc[1][1] = scr_mfma(fa[1][1], b0, zero16());
+                    } else {
+                        acc[0][1] = scr_mfma(fa[0][1], b0, acc[0][1]);
+                        acc[1][1] = scr_mfma(fa[1][1], b0, acc[1][1]);
+                    }
+                    acc[0][1] = scr_mfma(fa[0][0], b1, acc[0][1]);
+                    acc[1][1] = scr_mfma(fa[1][0], b1, acc[1][1]);
+                    if (kb == 0) {
+                        acc[0][0] = scr_mfma(fa[0][0], b0, zero16());
+                        acc[1][0] = scr_mfma(fa[1][0], b0, zero16());
+                    } else {
+                        acc[0][0] = scr_mfma(fa[0][0], b0, acc[0][0]);
+                        acc[1][0] = scr_mfma(fa[1][0], b0, acc[1][0]);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    }
 #pragma unroll
                     for (int r = 0; r < 2; ++r) {
-                        const u32x4 a0 = scr_lds_a(hp0, 32 * r, kb, lane), a1 = scr_lds_a(hp1, 32 * r, kb, lane);
-                        acc[r][1] = scr_mfma(a1, b0, acc[r][1]);
-                        acc[r][1] = scr_mfma(a0, b1, acc[r][1]);
-                        acc[r][0] = scr_mfma(a0, b0, acc[r][0]);
+                        fa[r][0] = na[r][0];
+                        fa[r][1] = na[r][1];
                     }
                 }
+                if (scr_abl == 3) {       // MFMAs and their loads only: one value of each accumulator, pooled, keeps them live
+                    sr0 = fmaxf(sr0, (acc[0][0][0] + acc[0][1][0]) + (acc[1][0][0] + acc[1][1][0]));
+                    if (ct == 7) scr_E[lane] = sr0;
+                    continue;
+                }
+                const float mu = mu_c * Heff;
+                mu_c = scr_mu[256 * wave + 32 * (ct < 7 ? ct + 1 : 7) + (lane & 31)];   // the next column tile's, behind the ring's requests
                 float tv[32];
 #pragma unroll
                 for (int j = 0; j < 32; ++j) tv[j] = fmaf(acc[j >> 4][1][j & 15], 0x1p-11f, acc[j >> 4][0][j & 15]);
                 float m = fmaxf(tv[0], tv[1]);
 #pragma unroll
-                for (int j = 2; j < 32; ++j) m = fmaxf(m, tv[j]);
-                m = fmaxf(m, __shfl_xor(m, 32));
+                for (int j = 2; j < 32; j += 2) m = fmaxf(fmaxf(m, tv[j]), tv[j + 1]);
+                m = half_max(m);
                 float R;
                 if (ct == 0) R = sr0 = fmaxf(sr0, m);
                 else if (ct == 1) R = sr1 = fmaxf(sr1, m);
@@ -153,11 +213,18 @@
                     qn += n;
                 }
                 __builtin_amdgcn_wave_barrier();
-                // full batches now, the rest with the tile's last column tile (the fp32 rows leave LDS with the tile)
+                if (scr_abl == 4) qn = 0; // everything but the confirm
+                // full batches now, the rest with the tile's last column tile (the fp32 rows leave LDS with the tile).  Rows of
+                // the 16-row tail take the two-chain form, every other candidate the plain chain: the form is chosen per
+                // batch, wave-uniformly, and a batch of a tail tile that holds both runs both, each under its own lanes
                 while (!undec && (qn >= 64 || (ct == 7 && qn > 0))) {
                     const int n = qn < 64 ? qn : 64;
-                    const int at = qn - n + lane;
-                    if (lane < n) scr_confirm(scr_q[at], bufB, w3, wave, tail, scr_E);
+                    const unsigned entry = scr_q[qn - n + (lane < n ? lane : 0)];
+                    const bool split = tail && (entry >> 16) >= 32u;
+                    if (lane < n && !split) scr_confirm<false>(entry, bufB, w3, wave, scr_E);
+                    if (tail && __ballot(lane < n && split) != 0ull) {
+                        if (lane < n && split) scr_confirm<true>(entry, bufB, w3, wave, scr_E);
+                    }
                     qn -= n;
                     nconf += n;
                 }

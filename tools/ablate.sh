@@ -1,9 +1,12 @@
 #!/bin/bash
 # timing of the chain kernel of the library that is loaded (development aid).  The timing-only ablations are build variants,
-# -DP2S_DEV_ABLATE=<variant> (1 = conv3 only, 2 = all but conv3; the results of such a build are wrong).  Build one beside the
+# -DP2S_DEV_ABLATE=<variant> (1 = conv3 only, 2 = all but conv3; of the screened conv3: 3 = its MFMAs and their loads only,
+# 4 = everything but the confirm, 5 = everything but the split; the results of such a build are wrong).  Build one beside the
 # shipped library and point P2S_LIB_PATH at it; this script builds nothing and replaces nothing:
-#   P2S_LIB_PATH=/path/to/variant/libp2s_hip.so tools/ablate.sh
-python tools/quick_bench.py --B 4096 --iters 3 2>/dev/null | tail -1 | python -c '
+#   P2S_LIB_PATH=/path/to/variant/libp2s_hip.so tools/ablate.sh [queries per launch, default 4096]
+python tools/quick_bench.py --B "${1:-4096}" --iters 3 2>/dev/null | tail -1 | python -c '
 import sys, json
 d = json.loads(sys.stdin.read())
-print(round(d["ms"], 2), "ms; chain_stn", round(d["stages_ms"]["ms_chain_stn"], 2), "chain_main", round(d["stages_ms"]["ms_chain_main"], 2))'
+c = d.get("device_clock") or {}
+print(round(d["ms"], 2), "ms; chain_stn", round(d["stages_ms"]["ms_chain_stn"], 2), "chain_main", round(d["stages_ms"]["ms_chain_main"], 2),
+      "; sclk MHz", round(c.get("sclk_MHz_mean", 0)), "power W", round(c.get("power_W_mean", 0)))'

@@ -33,18 +33,23 @@ def main():
     rad = torch.rand((B,), device='cuda', generator=g) * 0.1 + 0.05
     m.forward(patch, sub, q, rad, want_sdf=True)
     torch.cuda.synchronize()
+    from bench import ClockSampler          # shader clock and power over the timed loop (None where the hwmon files are missing)
+    clocks = ClockSampler()
+    clocks.start()
     t0 = time.time()
     for _ in range(args.iters):
         m.forward(patch, sub, q, rad, want_sdf=True)
     torch.cuda.synchronize()
     dt = (time.time() - t0) / args.iters
+    clock = clocks.stop()
     m.set_profiling(True)
     m.forward(patch, sub, q, rad, want_sdf=True)
     torch.cuda.synchronize()
     c = m.counters()
     qps = B / dt
     print(json.dumps({'model': args.model, 'B': B, 'ms': dt * 1e3, 'qps': qps,
-                      'tflops': qps * FLOP_PER_QUERY[args.model] / 1e12, 'stages_ms': c}))
+                      'tflops': qps * FLOP_PER_QUERY[args.model] / 1e12, 'stages_ms': c,
+                      'device_clock': clock}))
 
 
 if __name__ == '__main__':
