@@ -1,8 +1,8 @@
 // "next" row f-6: first-hit ray casting on the mesh handle, the time-of-flight scan built on it, and the query points of
 // the GT data -- the part of the reference's make_dataset.py that starts one BlenSor process per mesh (:242-380, 5..30
 // scans of 176 x 144 rays) and calls trimesh (source/sdf.py:288-315).  Included at the end of p2s_meshdist.hip: the
-// handle, the octree of AABBs, the ordered-integer bounds, dot3 / cross3 / finite3, DEGENERATE_REL and the one-workgroup
-// scan (p2s_md_scan_kernel) are that file's, used here and not copied.
+// handle, the octree with its walk helpers (p2s_mesh_octree.inl), the host scaffold, the ordered-integer bounds, dot3 /
+// cross3 / finite3, DEGENERATE_REL and the one-workgroup scan (p2s_md_scan_kernel) are that unit's, used here, not copied.
 //   p2s_mr_index_kernel       first hit per ray: depth-first descent of the octree, children in the ray's front-to-back order
 //   p2s_mr_exhaustive_kernel  every ray against every triangle, faces split over grid.y, prepared triangles staged in LDS
 //   p2s_mr_merge_kernel       the parts of the exhaustive kernel into one answer per ray
@@ -25,7 +25,6 @@
 //  * a direction component below 2^-1022 in magnitude (subnormal) is taken as 0;
 //  * a ray with a non-finite component (|x| > 1e300) or a zero direction misses: face -1, t = +inf; no NaN leaves a
 //    kernel (every acceptance is a conjunction of comparisons, false for NaN).
-#include <vector>
 
 namespace {
 
@@ -104,17 +103,6 @@ __device__ __forceinline__ bool slab_reaches(const int *__restrict__ node, const
     return e < INFINITY && e <= limit;
 }
 
-constexpr int RAY_STACK = 52;
-
-struct RayIndexDev {
-    const int *nodes;
-    const int *cell_start;
-    const int *sface;
-    const double *stri;
-    int L;
-    double scale;
-};
-
 // Thread -> ray.  tile_w == 0: thread i casts ray i.  Otherwise the rays are S images of tile_h rows x tile_w columns
 // (ray = (scan * tile_h + row) * tile_w + column) and a wave holds an 8 x 8 pixel tile of one image: its 64 rays leave one
 // point in a narrow bundle, descend the same nodes and test the same triangles, so the wave diverges little.
@@ -138,14 +126,13 @@ __device__ __forceinline__ long long ray_of_thread(long long i, long long n, int
 // |bound - o| / |d_k| <= 2^-50 M / |d_k| against a slack of E / |d_k| = 2^-24 M / |d_k|.  So the computed entry into the
 // grown box is <= the computed t of every hit inside, with 26 bits to spare, whatever the conditioning of the
 // intersection itself: t and face equal the exhaustive kernel's bit for bit.  The order of the descent changes the cost
-// only.  The stack lives in LDS (one column per lane: conflict-free, and no scratch round trips).  A pop of an inner node
-// pushes at most 8, so the depth is at most 7 L + 1 = 50 for L <= 7: RAY_STACK = 52 entries, 13 KiB per wave (12 waves per CU
-// by LDS; 64 entries = 16 KiB = 10 waves measured the same to within run-to-run noise, profiles/scan/README.md).  A push
-// beyond the stack cannot happen for L <= 7; if it ever did, the call fails (overflow word) instead of dropping a node.
-__global__ __launch_bounds__(64) void p2s_mr_index_kernel(RayIndexDev ix, const double *__restrict__ rays, long long n, double t_max,
+// only.  The stack is a LaneStack (p2s_mesh_octree.inl): 13 KiB of LDS per wave, 12 waves per CU by LDS; 64 entries =
+// 16 KiB = 10 waves measured the same to within run-to-run noise (profiles/scan/README.md).  Its overflow word is RC_OVERFLOW.
+enum RayCtr { RC_TESTS, RC_OVERFLOW };
+__global__ __launch_bounds__(64) void p2s_mr_index_kernel(OctreeDev ix, const double *__restrict__ rays, long long n, double t_max,
                                                           int tile_w, int tile_h, double *__restrict__ t_out, int *__restrict__ face_out,
-                                                          unsigned long long *__restrict__ tests_total) {
-    __shared__ int stack[RAY_STACK * 64];
+                                                          unsigned long long *__restrict__ ctr) {
+    __shared__ int lds[OCT_STACK * 64];
     const int lane = threadIdx.x;
     const long long r = ray_of_thread((long long)blockIdx.x * 64 + lane, n, tile_w, tile_h);
     unsigned long long tests = 0;
@@ -165,16 +152,16 @@ __global__ __launch_bounds__(64) void p2s_mr_index_kernel(RayIndexDev ix, const 
                 inv[k] = 1.0 / d[k];
                 m = (m << 1) | (d[k] < 0.0 ? 1 : 0);
             }
-            int sp = 0;
-            stack[(sp++) * 64 + lane] = 0;
-            while (sp > 0) {
-                const int node = stack[(--sp) * 64 + lane];
-                const int l = node >> 27, lin = node & 0x7ffffff;
-                const long long off = ((1ll << (3 * l)) - 1) / 7;
-                if (!slab_reaches(ix.nodes + 6 * (off + lin), o, d, inv, g, fmin(best, t_max))) continue;
+            LaneStack stack(lds, lane);
+            stack.push(oct_id(0, 0), ctr + RC_OVERFLOW);
+            while (!stack.empty()) {
+                const int node = stack.pop();
+                const int l = oct_level(node), lin = oct_lin(node);
+                if (!slab_reaches(oct_box(ix, l, lin), o, d, inv, g, fmin(best, t_max))) continue;
                 if (l == ix.L) {
-                    const int t1 = ix.cell_start[lin + 1];
-                    for (int t = ix.cell_start[lin]; t < t1; ++t) {
+                    int t0, t1;
+                    oct_leaf_range(ix, lin, &t0, &t1);
+                    for (int t = t0; t < t1; ++t) {
                         double p[PREP_DOUBLES];
                         tri_prep(ix.stri + 9 * (long long)t, p);
                         const double th = ray_tri(p, o, d, t_max, E);
@@ -186,15 +173,12 @@ __global__ __launch_bounds__(64) void p2s_mr_index_kernel(RayIndexDev ix, const 
                         }
                     }
                 } else {
-                    const int nn = 1 << l;
-                    const int z = lin & (nn - 1), y = (lin >> l) & (nn - 1), x = lin >> (2 * l);
-                    const long long coff = ((1ll << (3 * (l + 1))) - 1) / 7;
+                    int xyz[3];
+                    oct_xyz(l, lin, xyz);
                     for (int j = 7; j >= 0; --j) {       // pushed back to front: the child the ray enters first is popped first
-                        const int c = j ^ m;
-                        const int clin = ((2 * x + (c >> 2)) * (2 * nn) + (2 * y + ((c >> 1) & 1))) * (2 * nn) + (2 * z + (c & 1));
-                        if (!slab_reaches(ix.nodes + 6 * (coff + clin), o, d, inv, g, fmin(best, t_max))) continue;
-                        if (sp < RAY_STACK) stack[(sp++) * 64 + lane] = ((l + 1) << 27) | clin;
-                        else atomicOr(tests_total + 1, 1ull);
+                        const int clin = oct_child_lin(l, xyz, j ^ m);
+                        if (!slab_reaches(oct_box(ix, l + 1, clin), o, d, inv, g, fmin(best, t_max))) continue;
+                        stack.push(oct_id(l + 1, clin), ctr + RC_OVERFLOW);
                     }
                 }
             }
@@ -202,8 +186,7 @@ __global__ __launch_bounds__(64) void p2s_mr_index_kernel(RayIndexDev ix, const 
         t_out[r] = best;
         face_out[r] = bestf;
     }
-    for (int s = 32; s > 0; s >>= 1) tests += __shfl_xor(tests, s);
-    if (lane == 0 && tests) atomicAdd(tests_total, tests);
+    wave_count(ctr + RC_TESTS, tests);
 }
 
 // every ray against the faces [y * per, (y + 1) * per): part_t / part_f [gridDim.y][n]
@@ -361,44 +344,43 @@ __global__ __launch_bounds__(256) void p2s_mr_query_pts_kernel(const double *__r
     }
 }
 
-// the exhaustive kernel's split of the faces over grid.y (as p2s_mesh_distance's)
-void ray_parts(long long F, long long n, int *parts, long long *per) {
-    const long long want = std::max<long long>(1, 2048 / (long long)blocks(n, 256));
-    int p = (int)std::min<long long>(std::min<long long>(want, 256), std::max<long long>(1, F / RX_TILE));
-    long long q = (F + p - 1) / p;
-    q = (q + RX_TILE - 1) / RX_TILE * RX_TILE;
-    *parts = (int)((F + q - 1) / q);
-    *per = q;
+// what a cast needs besides its rays: the parts of the exhaustive kernel [parts][n] (method 1) and the RayCtr words
+struct CastWs {
+    double *part_t;
+    int *part_f;
+    unsigned long long *ctr;
+    char *base;                    // (p2s_mesh_raycast: a block of its own)
+    size_t bytes;
+};
+CastWs carve_cast(Carver &c, size_t n, int parts) {
+    CastWs w = {};
+    w.part_t = c.take<double>(n * parts);
+    w.part_f = c.take<int>(n * parts);
+    w.ctr = c.take<unsigned long long>(8);
+    return w;
 }
 
-// launches the cast of n rays (no synchronisation); part_t / part_f: [parts][n] for method 1
+// launches the cast of n rays (no synchronisation)
 void ray_cast_launch(p2s_trimesh_t m, const double *rays, long long n, double t_max, int method, int tile_w, int tile_h, double *t_out,
-                     int *face_out, double *part_t, int *part_f, int parts, long long per, unsigned long long *tests, hipStream_t s) {
+                     int *face_out, const CastWs &w, int parts, long long per, hipStream_t s) {
     if (method == 0) {
-        RayIndexDev ix;
-        ix.nodes = m->nodes;
-        ix.cell_start = m->cell_start;
-        ix.sface = m->sface;
-        ix.stri = m->stri;
-        ix.L = m->L;
-        ix.scale = m->scale;
         long long threads = n;
         if (tile_w > 0) threads = (n / ((long long)tile_w * tile_h)) * ((tile_w + 7) / 8) * ((tile_h + 7) / 8) * 64;
-        hipLaunchKernelGGL(p2s_mr_index_kernel, dim3(blocks(threads, 64)), dim3(64), 0, s, ix, rays, n, t_max, tile_w, tile_h, t_out, face_out,
-                           tests);
+        hipLaunchKernelGGL(p2s_mr_index_kernel, dim3(blocks(threads, 64)), dim3(64), 0, s, octree_of(m), rays, n, t_max, tile_w, tile_h, t_out,
+                           face_out, w.ctr);
     } else {
         hipLaunchKernelGGL(p2s_mr_exhaustive_kernel, dim3(blocks(n, 256), parts), dim3(256), 0, s, m->tri, m->F, per, m->scale, rays, n, t_max,
-                           part_t, part_f);
-        hipLaunchKernelGGL(p2s_mr_merge_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, part_t, part_f, parts, n, t_out, face_out);
+                           w.part_t, w.part_f);
+        hipLaunchKernelGGL(p2s_mr_merge_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, w.part_t, w.part_f, parts, n, t_out, face_out);
     }
 }
-
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+const char *const RAY_OVERFLOW = "traversal stack overflow (an index deeper than 7 levels)";
 
 }  // namespace
 
 extern "C" int p2s_mesh_raycast(p2s_trimesh_t m, const double *rays_dev, int64_t n, double t_max, int method, double *t_out_dev,
                                 int32_t *face_out_dev, int64_t *tests_host, void *stream) {
+    static const char *const who = "p2s_mesh_raycast";
     if (tests_host) *tests_host = 0;
     if (!m || n < 0 || n > (1ll << 30) || (n > 0 && (!rays_dev || !t_out_dev || !face_out_dev)) || (method != 0 && method != 1) ||
         !(t_max == t_max)) {
@@ -410,38 +392,49 @@ extern "C" int p2s_mesh_raycast(p2s_trimesh_t m, const double *rays_dev, int64_t
     hipStream_t s = (hipStream_t)stream;
     int parts = 0;
     long long per = m->F;
-    if (method == 1) ray_parts(m->F, n, &parts, &per);
-    const size_t b_pt = up256((size_t)n * parts * 8), b_pf = up256((size_t)n * parts * 4);
-    char *ws = (char *)p2s_pool_alloc(m->device, b_pt + b_pf + 256);
-    if (!ws) {
-        p2s_set_error("p2s_mesh_raycast: out of device memory");
-        return P2S_ENOMEM;
-    }
-    unsigned long long *ctr = (unsigned long long *)(ws + b_pt + b_pf);
-    hipError_t e = hipMemsetAsync(ctr, 0, 64, s);
-    if (e == hipSuccess) {
-        ray_cast_launch(m, rays_dev, n, t_max, method, 0, 0, t_out_dev, face_out_dev, (double *)ws, (int *)(ws + b_pt), parts, per, ctr, s);
-        e = hipGetLastError();
-    }
-    unsigned long long hc[2] = {};
-    if (e == hipSuccess) e = hipMemcpyAsync(hc, ctr, 16, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    p2s_pool_free(m->device, ws);
-    if (e != hipSuccess) {
-        p2s_set_error("p2s_mesh_raycast: %s", hipGetErrorString(e));
-        return P2S_EHIP;
-    }
-    if (hc[1]) {
-        p2s_set_error("p2s_mesh_raycast: traversal stack overflow (an index deeper than 7 levels)");
-        return P2S_EHIP;
-    }
-    if (tests_host) *tests_host = method == 0 ? (int64_t)hc[0] : (int64_t)n * m->F;
+    if (method == 1) exhaustive_parts(m->F, n, RX_TILE, &parts, &per);
+    MeshScratch pool(m->device);
+    const CastWs w = pool.carve([&](char *b) {
+        Carver c{b};
+        return c.done(carve_cast(c, (size_t)n, parts));
+    });
+    if (!w.base) return mesh_oom(who, s);
+    MESH_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
+    ray_cast_launch(m, rays_dev, n, t_max, method, 0, 0, t_out_dev, face_out_dev, w, parts, per, s);
+    unsigned long long hc[8] = {};
+    const int rc = read_counters(who, w.ctr, hc, RC_OVERFLOW, RAY_OVERFLOW, s);
+    if (rc != P2S_OK) return rc;
+    if (tests_host) *tests_host = method == 0 ? (int64_t)hc[RC_TESTS] : (int64_t)n * m->F;
     return P2S_OK;
 }
+
+namespace {
+struct ScanWs {
+    double *rays, *t, *pose;       // [n][6], [n], [S][12]
+    int *face, *block_count, *block_start, *scan_count;
+    CastWs cast;
+    char *base;
+    size_t bytes;
+};
+ScanWs carve_scan(char *base, size_t n, size_t n_scans, size_t nb, int parts) {
+    Carver c{base};
+    ScanWs w;
+    w.rays = c.take<double>(n * 6);
+    w.t = c.take<double>(n);
+    w.face = c.take<int>(n);
+    w.pose = c.take<double>(n_scans * 12);
+    w.block_count = c.take<int>(nb + 1);
+    w.block_start = c.take<int>(nb + 1);
+    w.scan_count = c.take<int>(n_scans);
+    w.cast = carve_cast(c, n, parts);
+    return c.done(w);
+}
+}  // namespace
 
 extern "C" int p2s_mesh_tof_scan(p2s_trimesh_t m, const double *poses_host, int32_t n_scans, const p2s_tof_sensor *sensor, double sigma,
                                  const double *noise_dev, int method, double *noisy_out_dev, double *clean_out_dev, int32_t *face_out_dev,
                                  double *normal_out_dev, int32_t *hits_per_scan_host, int64_t *n_hits_host, int64_t *tests_host, void *stream) {
+    static const char *const who = "p2s_mesh_tof_scan";
     if (n_hits_host) *n_hits_host = 0;
     if (tests_host) *tests_host = 0;
     if (!m || n_scans < 0 || n_scans > 4096 || !sensor || !n_hits_host || (method != 0 && method != 1) || !(sigma >= 0.0) ||
@@ -491,66 +484,30 @@ extern "C" int p2s_mesh_tof_scan(p2s_trimesh_t m, const double *poses_host, int3
     hipStream_t s = (hipStream_t)stream;
     int parts = 0;
     long long per = m->F;
-    if (method == 1) ray_parts(m->F, n, &parts, &per);
+    if (method == 1) exhaustive_parts(m->F, n, RX_TILE, &parts, &per);
     const long long nb = (n + 1023) / 1024;
-    const size_t b_rays = up256((size_t)n * 48), b_t = up256((size_t)n * 8), b_face = up256((size_t)n * 4), b_pose = up256(pose.size() * 8),
-                 b_cnt = up256((size_t)(nb + 1) * 4), b_scan = up256((size_t)n_scans * 4), b_pt = up256((size_t)n * parts * 8),
-                 b_pf = up256((size_t)n * parts * 4);
-    char *ws = (char *)p2s_pool_alloc(m->device, b_rays + b_t + b_face + b_pose + 2 * b_cnt + b_scan + b_pt + b_pf + 256);
-    if (!ws) {
-        p2s_set_error("p2s_mesh_tof_scan: out of device memory");
-        return P2S_ENOMEM;
-    }
-    char *at = ws;
-    auto take = [&](size_t b) { char *p = at; at += b; return p; };
-    double *rays = (double *)take(b_rays), *t = (double *)take(b_t);
-    int *face = (int *)take(b_face);
-    double *pose_dev = (double *)take(b_pose);
-    int *block_count = (int *)take(b_cnt), *block_start = (int *)take(b_cnt), *scan_count = (int *)take(b_scan);
-    double *part_t = (double *)take(b_pt);
-    int *part_f = (int *)take(b_pf);
-    unsigned long long *ctr = (unsigned long long *)take(256);
-    hipError_t e = hipMemcpyAsync(pose_dev, pose.data(), pose.size() * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(ctr, 0, 64, s);
-    if (e == hipSuccess) e = hipMemsetAsync(scan_count, 0, (size_t)n_scans * 4, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(p2s_mr_rays_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, pose_dev, n, W, H, sensor->tan_half_w, sensor->tan_half_h, rays);
-        ray_cast_launch(m, rays, n, sensor->max_distance, method, W, H, t, face, part_t, part_f, parts, per, ctr, s);
-        hipLaunchKernelGGL(p2s_mr_count_kernel, dim3((unsigned)nb), dim3(1024), 0, s, face, n, per_scan, block_count, scan_count);
-        hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, block_count, nb, block_start);
-        CompactArgs a;
-        a.rays = rays;
-        a.t = t;
-        a.noise = noise_dev;
-        a.fn = m->fn;
-        a.face = face;
-        a.block_start = block_start;
-        a.n = n;
-        a.sigma = sigma;
-        a.noisy = noisy_out_dev;
-        a.clean = clean_out_dev;
-        a.normal = normal_out_dev;
-        a.face_out = face_out_dev;
-        hipLaunchKernelGGL(p2s_mr_compact_kernel, dim3((unsigned)nb), dim3(1024), 0, s, a);
-        e = hipGetLastError();
-    }
-    unsigned long long hc[2] = {};
+    MeshScratch pool(m->device);
+    const ScanWs w = pool.carve([&](char *b) { return carve_scan(b, (size_t)n, (size_t)n_scans, (size_t)nb, parts); });
+    if (!w.base) return mesh_oom(who, s);
+    MESH_CHECK(who, hipMemcpyAsync(w.pose, pose.data(), pose.size() * 8, hipMemcpyHostToDevice, s));
+    MESH_CHECK(who, hipMemsetAsync(w.cast.ctr, 0, MESH_COUNTERS, s));
+    MESH_CHECK(who, hipMemsetAsync(w.scan_count, 0, (size_t)n_scans * 4, s));
+    hipLaunchKernelGGL(p2s_mr_rays_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, w.pose, n, W, H, sensor->tan_half_w, sensor->tan_half_h, w.rays);
+    ray_cast_launch(m, w.rays, n, sensor->max_distance, method, W, H, w.t, w.face, w.cast, parts, per, s);
+    hipLaunchKernelGGL(p2s_mr_count_kernel, dim3((unsigned)nb), dim3(1024), 0, s, w.face, n, per_scan, w.block_count, w.scan_count);
+    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, w.block_count, nb, w.block_start);
+    const CompactArgs a = {w.rays, w.t, noise_dev, m->fn, w.face, w.block_start, n, sigma, noisy_out_dev, clean_out_dev, normal_out_dev,
+                           face_out_dev};
+    hipLaunchKernelGGL(p2s_mr_compact_kernel, dim3((unsigned)nb), dim3(1024), 0, s, a);
+    unsigned long long hc[8] = {};
     int total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(hc, ctr, 16, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, block_start + nb, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(hits_per_scan_host, scan_count, (size_t)n_scans * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    p2s_pool_free(m->device, ws);
-    if (e != hipSuccess) {
-        p2s_set_error("p2s_mesh_tof_scan: %s", hipGetErrorString(e));
-        return P2S_EHIP;
-    }
-    if (hc[1]) {
-        p2s_set_error("p2s_mesh_tof_scan: traversal stack overflow (an index deeper than 7 levels)");
-        return P2S_EHIP;
-    }
+    MESH_CHECK(who, hipGetLastError());
+    MESH_CHECK(who, hipMemcpyAsync(&total, w.block_start + nb, 4, hipMemcpyDeviceToHost, s));
+    MESH_CHECK(who, hipMemcpyAsync(hits_per_scan_host, w.scan_count, (size_t)n_scans * 4, hipMemcpyDeviceToHost, s));
+    const int rc = read_counters(who, w.cast.ctr, hc, RC_OVERFLOW, RAY_OVERFLOW, s);
+    if (rc != P2S_OK) return rc;
     *n_hits_host = total;
-    if (tests_host) *tests_host = method == 0 ? (int64_t)hc[0] : (int64_t)n * m->F;
+    if (tests_host) *tests_host = method == 0 ? (int64_t)hc[RC_TESTS] : (int64_t)n * m->F;
     return P2S_OK;
 }
 

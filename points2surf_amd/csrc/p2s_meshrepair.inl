@@ -20,8 +20,6 @@
 // exclusive scans, float64 sums run in the fixed order of the shared volume kernels; where a slot is written by whichever
 // thread comes last (a vertex's next boundary vertex) the value is used only if one thread writes it.
 
-#include <vector>
-
 namespace {
 
 __device__ __forceinline__ unsigned rp_bits(float x) {              // -0.0 counts as +0.0
@@ -149,22 +147,6 @@ __global__ __launch_bounds__(256) void p2s_rp_gather_kernel(const float *__restr
     if (!(dot3(n, n) > DEGENERATE_REL * (dot3(ab, ab) * dot3(ac, ac)))) atomicAdd(degenerate, 1ull);
 }
 
-// the slot of an edge that p2s_md_edges_kernel inserted
-__device__ __forceinline__ unsigned rp_edge_slot(const EdgeTable &t, int a, int b) {
-    const unsigned long long key = edge_key(a, b);
-    unsigned h = edge_hash(key) & t.mask;
-    while (t.key[h] != key) h = (h + 1) & t.mask;
-    return h;
-}
-__global__ __launch_bounds__(256) void p2s_rp_edge_faces_kernel(const int *__restrict__ faces, long long F, EdgeTable t, int *fmn, int *fmx) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= 3 * F) return;
-    const long long f = i / 3;
-    const int e = (int)(i - 3 * f);
-    const unsigned h = rp_edge_slot(t, faces[3 * f + e], faces[3 * f + (e + 1) % 3]);
-    atomicMin(&fmn[h], (int)f);
-    atomicMax(&fmx[h], (int)f);
-}
 // adj: the other face of an edge that exactly two faces use, else -1; par: 1 when both traverse it in the same direction
 __global__ __launch_bounds__(256) void p2s_rp_adj_kernel(const int *__restrict__ faces, long long F, EdgeTable t, const int *__restrict__ fmn,
                                                          const int *__restrict__ fmx, int *__restrict__ adj, unsigned char *__restrict__ par) {
@@ -421,59 +403,98 @@ unsigned rp_table_cap(long long n) {             // a power of two >= 2 n: load 
     while ((long long)cap < 2 * n) cap <<= 1;
     return cap;
 }
-float rp_o2f(int i) {
-    const int b = i >= 0 ? i : i ^ 0x7fffffff;
-    float f;
-    memcpy(&f, &b, 4);
-    return f;
+
+// the counters of p2s_mesh_repair, zeroed before each of its three phases
+enum RepairCtr {
+    RP_WELDED = 0, RP_COLLAPSED, RP_DUPLICATE,                                               // b, c
+    RP_DEGENERATE = 0, RP_FLIPPED, RP_UNORIENTABLE, RP_HOLES,                                // d, e
+    RP_BOUNDARY = 0, RP_NONMANIFOLD, RP_INCONSISTENT, RP_COMPONENTS, RP_BGROUPS, RP_INVERTED, RP_VOLUME      // f, g
+};
+
+// the four blocks of p2s_mesh_repair, each carved when its sizes are known
+struct RpWeldWs {                                // b, c
+    int *ctl;
+    unsigned long long *ctr;
+    int *vslot, *fslot, *rep, *wfa, *keep, *kstart;
+    char *base;
+    size_t bytes;
+};
+RpWeldWs carve_weld(char *base, size_t V, size_t F, unsigned vcap, unsigned fcap) {
+    Carver c{base};
+    RpWeldWs w;
+    w.ctl = c.take<int>(16);
+    w.ctr = c.take<unsigned long long>(8);
+    w.vslot = c.take<int>(vcap);
+    w.fslot = c.take<int>(fcap);
+    w.rep = c.take<int>(V);
+    w.wfa = c.take<int>(F * 3);
+    w.keep = c.take<int>(F);
+    w.kstart = c.take<int>(F + 1);
+    return c.done(w);
 }
-
-// blocks of the device's cache, all returned when the call ends
-struct RpScratch {
-    int device;
-    std::vector<void *> held;
-    explicit RpScratch(int d) : device(d) {}
-    ~RpScratch() {
-        for (void *p : held) p2s_pool_free(device, p);
-    }
-    char *get(size_t bytes) {
-        void *p = p2s_pool_alloc(device, bytes ? bytes : 256);
-        if (p) held.push_back(p);
-        return (char *)p;
-    }
+struct RpOrientWs {                              // d, e: on the F0 surviving faces
+    int *wf, *src, *fmn, *fmx, *adj, *link, *badroot;
+    unsigned char *par, *flipped, *unor;
+    int *vtx;                                    // [5][V] outc, inc, nxt, blocked, addc (zeroed as one)
+    int *bparent, *addstart;
+    EdgeTable t;
+    char *base;
+    size_t bytes;
 };
-struct RpArena {                                 // carves one block
-    size_t at = 0;
-    size_t take(size_t bytes) {
-        const size_t o = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
+RpOrientWs carve_orient(char *base, size_t V, size_t F0, unsigned ecap) {
+    Carver c{base};
+    RpOrientWs w;
+    w.wf = c.take<int>(F0 * 3);
+    w.src = c.take<int>(F0);
+    w.t = carve_edges(c, ecap);
+    w.fmn = c.take<int>(ecap);
+    w.fmx = c.take<int>(ecap);
+    w.adj = c.take<int>(F0 * 3);
+    w.par = c.take<unsigned char>(F0 * 3);
+    w.link = c.take<int>(F0);
+    w.badroot = c.take<int>(F0);
+    w.flipped = c.take<unsigned char>(F0);
+    w.unor = c.take<unsigned char>(F0);
+    w.vtx = c.take<int>(V * 5);
+    w.bparent = c.take<int>(V);
+    w.addstart = c.take<int>(V + 1);
+    return c.done(w);
+}
+struct RpFillWs {                                // f, g: on the F1 faces of the filled mesh
+    int *wf, *fmn, *fmx, *adj, *parent, *flag, *rstart, *used, *vstart, *onb;
+    EdgeTable t;
+    char *base;
+    size_t bytes;
 };
-
-#define RP_CHECK(expr)                                                                  \
-    do {                                                                                \
-        hipError_t _e = (expr);                                                         \
-        if (_e != hipSuccess) {                                                         \
-            (void)hipStreamSynchronize(s);                                              \
-            p2s_set_error("p2s_mesh_repair: %s (%s)", hipGetErrorString(_e), #expr);    \
-            return P2S_EHIP;                                                            \
-        }                                                                               \
-    } while (0)
-
-// the edge table of `faces`: p2s_md_edges_kernel, then the two extreme face ids of every edge when asked for
-int rp_build_edges(const int *faces, long long F, EdgeTable t, unsigned cap, int *fmn, int *fmx, hipStream_t s) {
-    RP_CHECK(hipMemsetAsync(t.key, 0xff, (size_t)cap * 8, s));
-    RP_CHECK(hipMemsetAsync(t.cnt, 0, (size_t)cap * 8, s));
-    RP_CHECK(hipMemsetAsync(t.face, 0xff, (size_t)cap * 8, s));
-    hipLaunchKernelGGL(p2s_md_edges_kernel, dim3(blocks(3 * F, 256)), dim3(256), 0, s, faces, F, t);
-    if (fmn) {
-        RP_CHECK(hipMemsetAsync(fmn, 0x7f, (size_t)cap * 4, s));
-        RP_CHECK(hipMemsetAsync(fmx, 0xff, (size_t)cap * 4, s));
-        hipLaunchKernelGGL(p2s_rp_edge_faces_kernel, dim3(blocks(3 * F, 256)), dim3(256), 0, s, faces, F, t, fmn, fmx);
-    }
-    RP_CHECK(hipGetLastError());
-    return P2S_OK;
+RpFillWs carve_fill(char *base, size_t V, size_t F1, unsigned ecap) {
+    Carver c{base};
+    RpFillWs w;
+    w.wf = c.take<int>(F1 * 3);
+    w.t = carve_edges(c, ecap);
+    w.fmn = c.take<int>(ecap);
+    w.fmx = c.take<int>(ecap);
+    w.adj = c.take<int>(F1 * 3);
+    w.parent = c.take<int>(F1);
+    w.flag = c.take<int>(F1);
+    w.rstart = c.take<int>(F1 + 1);
+    w.used = c.take<int>(V);
+    w.vstart = c.take<int>(V + 1);
+    w.onb = c.take<int>(V);
+    return c.done(w);
+}
+struct RpVolumeWs {                              // f: the closed components' own volumes
+    double *tri, *vol;
+    int *roots;
+    char *base;
+    size_t bytes;
+};
+RpVolumeWs carve_volume(char *base, size_t F1, size_t n_closed) {
+    Carver c{base};
+    RpVolumeWs w;
+    w.tri = c.take<double>(F1 * 9);
+    w.roots = c.take<int>(n_closed);
+    w.vol = c.take<double>(n_closed);
+    return c.done(w);
 }
 
 }  // namespace
@@ -481,6 +502,7 @@ int rp_build_edges(const int *faces, long long F, EdgeTable t, unsigned cap, int
 extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const int32_t *faces_dev, int64_t n_faces, int max_hole_edges,
                                float *verts_out_dev, int64_t cap_verts, int32_t *faces_out_dev, int32_t *face_src_out_dev,
                                int64_t cap_faces, int64_t *report_host, int device, void *stream) {
+    static const char *const who = "p2s_mesh_repair";
     if (!report_host || n_verts < 0 || n_faces < 0 || n_verts > (1ll << 27) || n_faces > (1ll << 25) || max_hole_edges < 0 ||
         max_hole_edges > 64 || cap_verts < 0 || cap_faces < 0 || (n_verts > 0 && !verts_dev) || (n_faces > 0 && !faces_dev) ||
         (cap_verts > 0 && !verts_out_dev) || (cap_faces > 0 && (!faces_out_dev || !face_src_out_dev))) {
@@ -500,30 +522,18 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
     auto publish = [&]() {
         for (int k = 0; k < 16; ++k) report_host[k] = rep_out[k];
     };
-    RpScratch pool(device);
-    auto oom = [&]() {
-        (void)hipStreamSynchronize(s);
-        p2s_set_error("p2s_mesh_repair: out of device memory");
-        return P2S_ENOMEM;
-    };
+    MeshScratch pool(device);
+    int rc;
 
     // ---- a. validate
-    char *cb = pool.get(1024);
-    if (!cb) return oom();
-    int *ctl = (int *)cb;                                            // 64 words
-    unsigned long long *ctr = (unsigned long long *)(cb + 256);      // 32 counters
+    const unsigned vcap = rp_table_cap(V), fcap = rp_table_cap(F);
+    const RpWeldWs A = pool.carve([&](char *b) { return carve_weld(b, (size_t)V, (size_t)F, vcap, fcap); });
+    if (!A.base) return mesh_oom(who, s);
+    int *ctl = A.ctl;
+    unsigned long long *ctr = A.ctr, hc[8] = {};
     if (V > 0 || F > 0) {
-        const int ctl_init[16] = {0, 0x7f800000, 0x7f800000, 0x7f800000, (int)0x807fffff, (int)0x807fffff, (int)0x807fffff, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        int h[16] = {};
-        RP_CHECK(hipMemcpyAsync(ctl, ctl_init, 64, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(p2s_md_validate_kernel, dim3(blocks(std::max(V, F), 256)), dim3(256), 0, s, verts_dev, V, faces_dev, F, ctl);
-        RP_CHECK(hipGetLastError());
-        RP_CHECK(hipMemcpyAsync(h, ctl, 64, hipMemcpyDeviceToHost, s));
-        RP_CHECK(hipStreamSynchronize(s));
-        if (h[0]) {
-            p2s_set_error("p2s_mesh_repair: %s", (h[0] & 2) ? "face index out of range" : "non-finite vertex");
-            return P2S_EINVAL;
-        }
+        float box[6];
+        if ((rc = mesh_validate(who, verts_dev, V, faces_dev, F, ctl, box, s)) != P2S_OK) return rc;
     }
     if (F == 0) {                                                    // nothing references a vertex: the empty mesh
         rep_out[15] = 1 | 2;                                         // no edge at all; no volume
@@ -532,33 +542,23 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
     }
 
     // ---- b, c. weld, collapsed and duplicate faces
-    const unsigned vcap = rp_table_cap(V), fcap = rp_table_cap(F);
-    RpArena A;
-    const size_t a_vslot = A.take((size_t)vcap * 4), a_fslot = A.take((size_t)fcap * 4), a_rep = A.take((size_t)V * 4),
-                 a_wfa = A.take((size_t)F * 12), a_keep = A.take((size_t)F * 4), a_kstart = A.take((size_t)(F + 1) * 4);
-    char *pa = pool.get(A.at);
-    if (!pa) return oom();
-    int *vslot = (int *)(pa + a_vslot), *fslot = (int *)(pa + a_fslot), *rep = (int *)(pa + a_rep), *wfa = (int *)(pa + a_wfa),
-        *keep = (int *)(pa + a_keep), *kstart = (int *)(pa + a_kstart);
-    RP_CHECK(hipMemsetAsync(vslot, 0xff, (size_t)vcap * 4, s));
-    RP_CHECK(hipMemsetAsync(fslot, 0xff, (size_t)fcap * 4, s));
-    RP_CHECK(hipMemsetAsync(ctr, 0, 256, s));
-    hipLaunchKernelGGL(p2s_rp_weld_insert_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, verts_dev, V, vslot, vcap - 1);
-    hipLaunchKernelGGL(p2s_rp_weld_map_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, verts_dev, V, vslot, vcap - 1, rep, ctr + 0);
-    hipLaunchKernelGGL(p2s_rp_face_weld_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, faces_dev, F, rep, wfa, keep, ctr + 1);
-    hipLaunchKernelGGL(p2s_rp_face_insert_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, wfa, F, keep, fslot, fcap - 1);
-    hipLaunchKernelGGL(p2s_rp_face_keep_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, wfa, F, keep, fslot, fcap - 1, ctr + 2);
-    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, keep, F, kstart);
-    RP_CHECK(hipGetLastError());
-    unsigned long long hc[32] = {};
+    MESH_CHECK(who, hipMemsetAsync(A.vslot, 0xff, (size_t)vcap * 4, s));
+    MESH_CHECK(who, hipMemsetAsync(A.fslot, 0xff, (size_t)fcap * 4, s));
+    MESH_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
+    hipLaunchKernelGGL(p2s_rp_weld_insert_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, verts_dev, V, A.vslot, vcap - 1);
+    hipLaunchKernelGGL(p2s_rp_weld_map_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, verts_dev, V, A.vslot, vcap - 1, A.rep, ctr + RP_WELDED);
+    hipLaunchKernelGGL(p2s_rp_face_weld_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, faces_dev, F, A.rep, A.wfa, A.keep, ctr + RP_COLLAPSED);
+    hipLaunchKernelGGL(p2s_rp_face_insert_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, A.wfa, F, A.keep, A.fslot, fcap - 1);
+    hipLaunchKernelGGL(p2s_rp_face_keep_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, A.wfa, F, A.keep, A.fslot, fcap - 1, ctr + RP_DUPLICATE);
+    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, A.keep, F, A.kstart);
     int hF0 = 0;
-    RP_CHECK(hipMemcpyAsync(hc, ctr, 256, hipMemcpyDeviceToHost, s));
-    RP_CHECK(hipMemcpyAsync(&hF0, kstart + F, 4, hipMemcpyDeviceToHost, s));
-    RP_CHECK(hipStreamSynchronize(s));
+    MESH_CHECK(who, hipGetLastError());
+    MESH_CHECK(who, hipMemcpyAsync(&hF0, A.kstart + F, 4, hipMemcpyDeviceToHost, s));
+    if ((rc = read_counters(who, ctr, hc, -1, nullptr, s)) != P2S_OK) return rc;
     const long long F0 = hF0;
-    rep_out[3] = (long long)hc[0];
-    rep_out[4] = (long long)hc[1];
-    rep_out[5] = (long long)hc[2];
+    rep_out[3] = (long long)hc[RP_WELDED];
+    rep_out[4] = (long long)hc[RP_COLLAPSED];
+    rep_out[5] = (long long)hc[RP_DUPLICATE];
     if (F0 == 0) {
         rep_out[15] = 1 | 2;
         publish();
@@ -566,160 +566,100 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
     }
 
     // ---- d. orient
-    const unsigned ecap0 = rp_table_cap(3 * F0);
-    RpArena B;
-    const size_t b_wf = B.take((size_t)F0 * 12), b_src = B.take((size_t)F0 * 4), b_key = B.take((size_t)ecap0 * 8),
-                 b_cnt = B.take((size_t)ecap0 * 8), b_face = B.take((size_t)ecap0 * 8), b_fmn = B.take((size_t)ecap0 * 4),
-                 b_fmx = B.take((size_t)ecap0 * 4), b_adj = B.take((size_t)F0 * 12), b_par = B.take((size_t)F0 * 3),
-                 b_link = B.take((size_t)F0 * 4), b_bad = B.take((size_t)F0 * 4), b_flip = B.take((size_t)F0), b_unor = B.take((size_t)F0),
-                 b_vtx = B.take((size_t)V * 4 * 6), b_addstart = B.take((size_t)(V + 1) * 4);
-    char *pb = pool.get(B.at);
-    if (!pb) return oom();
-    int *wf = (int *)(pb + b_wf), *src = (int *)(pb + b_src), *fmn = (int *)(pb + b_fmn), *fmx = (int *)(pb + b_fmx), *adj = (int *)(pb + b_adj),
-        *link = (int *)(pb + b_link), *badroot = (int *)(pb + b_bad), *addstart = (int *)(pb + b_addstart);
-    unsigned char *par = (unsigned char *)(pb + b_par), *flipped = (unsigned char *)(pb + b_flip), *unor = (unsigned char *)(pb + b_unor);
-    int *outc = (int *)(pb + b_vtx), *inc = outc + V, *nxt = inc + V, *blocked = nxt + V, *addc = blocked + V, *bparent = addc + V;
-    EdgeTable t0;
-    t0.key = (unsigned long long *)(pb + b_key);
-    t0.cnt = (int *)(pb + b_cnt);
-    t0.face = (int *)(pb + b_face);
-    t0.mask = ecap0 - 1;
-    RP_CHECK(hipMemsetAsync(ctr, 0, 256, s));
-    hipLaunchKernelGGL(p2s_rp_gather_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, verts_dev, wfa, F, keep, kstart, wf, src, ctr + 0);
-    int rc = rp_build_edges(wf, F0, t0, ecap0, fmn, fmx, s);
+    const RpOrientWs B = pool.carve([&](char *b) { return carve_orient(b, (size_t)V, (size_t)F0, rp_table_cap(3 * F0)); });
+    if (!B.base) return mesh_oom(who, s);
+    MESH_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
+    hipLaunchKernelGGL(p2s_rp_gather_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, verts_dev, A.wfa, F, A.keep, A.kstart, B.wf, B.src,
+                       ctr + RP_DEGENERATE);
+    if ((rc = build_edges(who, B.wf, F0, B.t, B.fmn, B.fmx, s)) != P2S_OK) return rc;
+    hipLaunchKernelGGL(p2s_rp_adj_kernel, dim3(blocks(3 * F0, 256)), dim3(256), 0, s, B.wf, F0, B.t, B.fmn, B.fmx, B.adj, B.par);
+    hipLaunchKernelGGL(p2s_rp_par_compress_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, B.link, F0, 1);
+    rc = until_unchanged(who, "the orientation", ctl, s, [&] {
+        hipLaunchKernelGGL(p2s_rp_par_hook_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, B.adj, B.par, B.link, F0, ctl);
+        hipLaunchKernelGGL(p2s_rp_par_compress_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, B.link, F0, 0);
+    });
     if (rc != P2S_OK) return rc;
-    hipLaunchKernelGGL(p2s_rp_adj_kernel, dim3(blocks(3 * F0, 256)), dim3(256), 0, s, wf, F0, t0, fmn, fmx, adj, par);
-    hipLaunchKernelGGL(p2s_rp_par_compress_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, link, F0, 1);
-    RP_CHECK(hipGetLastError());
-    {
-        // until a round hooks nothing: a round that sees two trees joined by an edge merges at least one pair, so it ends
-        int changed = 1;
-        for (int it = 0; it < 100000 && changed; ++it) {
-            RP_CHECK(hipMemsetAsync(ctl, 0, 4, s));
-            hipLaunchKernelGGL(p2s_rp_par_hook_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, adj, par, link, F0, ctl);
-            hipLaunchKernelGGL(p2s_rp_par_compress_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, link, F0, 0);
-            RP_CHECK(hipGetLastError());
-            RP_CHECK(hipMemcpyAsync(&changed, ctl, 4, hipMemcpyDeviceToHost, s));
-            RP_CHECK(hipStreamSynchronize(s));
-        }
-        if (changed) {
-            p2s_set_error("p2s_mesh_repair: the orientation did not converge");
-            return P2S_EHIP;
-        }
-    }
-    RP_CHECK(hipMemsetAsync(badroot, 0, (size_t)F0 * 4, s));
-    hipLaunchKernelGGL(p2s_rp_par_check_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, adj, par, link, F0, badroot);
-    hipLaunchKernelGGL(p2s_rp_par_apply_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, link, badroot, F0, wf, flipped, unor, ctr + 1);
-    RP_CHECK(hipGetLastError());
+    MESH_CHECK(who, hipMemsetAsync(B.badroot, 0, (size_t)F0 * 4, s));
+    hipLaunchKernelGGL(p2s_rp_par_check_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, B.adj, B.par, B.link, F0, B.badroot);
+    hipLaunchKernelGGL(p2s_rp_par_apply_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, B.link, B.badroot, F0, B.wf, B.flipped, B.unor,
+                       ctr + RP_FLIPPED);                            // and RP_UNORIENTABLE behind it
 
     // ---- e. holes, on the oriented faces
-    rc = rp_build_edges(wf, F0, t0, ecap0, nullptr, nullptr, s);
-    if (rc != P2S_OK) return rc;
-    RP_CHECK(hipMemsetAsync(outc, 0, (size_t)V * 4 * 5, s));         // outc, inc, nxt, blocked, addc
-    hipLaunchKernelGGL(p2s_rp_boundary_kernel, dim3(blocks(3 * F0, 256)), dim3(256), 0, s, wf, F0, t0, unor, outc, inc, nxt, blocked);
-    hipLaunchKernelGGL(p2s_rp_hole_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, V, K, outc, inc, nxt, blocked, addc, ctr + 3);
-    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, addc, V, addstart);
-    RP_CHECK(hipGetLastError());
+    if ((rc = build_edges(who, B.wf, F0, B.t, nullptr, nullptr, s)) != P2S_OK) return rc;
+    int *outc = B.vtx, *inc = outc + V, *nxt = inc + V, *blocked = nxt + V, *addc = blocked + V;
+    MESH_CHECK(who, hipMemsetAsync(B.vtx, 0, (size_t)V * 4 * 5, s));
+    hipLaunchKernelGGL(p2s_rp_boundary_kernel, dim3(blocks(3 * F0, 256)), dim3(256), 0, s, B.wf, F0, B.t, B.unor, outc, inc, nxt, blocked);
+    hipLaunchKernelGGL(p2s_rp_hole_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, V, K, outc, inc, nxt, blocked, addc, ctr + RP_HOLES);
+    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, addc, V, B.addstart);
     int h_added = 0;
-    RP_CHECK(hipMemcpyAsync(hc, ctr, 256, hipMemcpyDeviceToHost, s));
-    RP_CHECK(hipMemcpyAsync(&h_added, addstart + V, 4, hipMemcpyDeviceToHost, s));
-    RP_CHECK(hipStreamSynchronize(s));
-    rep_out[6] = (long long)hc[0];
-    rep_out[7] = (long long)hc[1];
-    rep_out[9] = (long long)hc[2];
-    rep_out[11] = (long long)hc[3];
+    MESH_CHECK(who, hipGetLastError());
+    MESH_CHECK(who, hipMemcpyAsync(&h_added, B.addstart + V, 4, hipMemcpyDeviceToHost, s));
+    if ((rc = read_counters(who, ctr, hc, -1, nullptr, s)) != P2S_OK) return rc;
+    rep_out[6] = (long long)hc[RP_DEGENERATE];
+    rep_out[7] = (long long)hc[RP_FLIPPED];
+    rep_out[9] = (long long)hc[RP_UNORIENTABLE];
+    rep_out[11] = (long long)hc[RP_HOLES];
     rep_out[12] = h_added;
     const long long F1 = F0 + h_added;
 
     // ---- f. components of the filled mesh, inversion
     const unsigned ecap1 = rp_table_cap(3 * F1);
-    RpArena C;
-    const size_t c_wf = C.take((size_t)F1 * 12), c_key = C.take((size_t)ecap1 * 8), c_cnt = C.take((size_t)ecap1 * 8),
-                 c_face = C.take((size_t)ecap1 * 8), c_fmn = C.take((size_t)ecap1 * 4), c_fmx = C.take((size_t)ecap1 * 4),
-                 c_adj = C.take((size_t)F1 * 12), c_parent = C.take((size_t)F1 * 4), c_flag = C.take((size_t)F1 * 4),
-                 c_rstart = C.take((size_t)(F1 + 1) * 4), c_used = C.take((size_t)V * 4), c_vstart = C.take((size_t)(V + 1) * 4),
-                 c_onb = C.take((size_t)V * 4);
-    char *pc = pool.get(C.at);
-    if (!pc) return oom();
-    int *wf1 = (int *)(pc + c_wf), *fmn1 = (int *)(pc + c_fmn), *fmx1 = (int *)(pc + c_fmx), *adj1 = (int *)(pc + c_adj),
-        *parent = (int *)(pc + c_parent), *flag = (int *)(pc + c_flag), *rstart = (int *)(pc + c_rstart), *used = (int *)(pc + c_used),
-        *vstart = (int *)(pc + c_vstart), *onb = (int *)(pc + c_onb);
-    EdgeTable t1;
-    t1.key = (unsigned long long *)(pc + c_key);
-    t1.cnt = (int *)(pc + c_cnt);
-    t1.face = (int *)(pc + c_face);
-    t1.mask = ecap1 - 1;
-    RP_CHECK(hipMemcpyAsync(wf1, wf, (size_t)F0 * 12, hipMemcpyDeviceToDevice, s));
-    if (h_added) hipLaunchKernelGGL(p2s_rp_hole_fill_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, V, nxt, addc, addstart, F0, wf1);
-    RP_CHECK(hipMemsetAsync(ctr, 0, 256, s));
-    rc = rp_build_edges(wf1, F1, t1, ecap1, fmn1, fmx1, s);
+    const RpFillWs C = pool.carve([&](char *b) { return carve_fill(b, (size_t)V, (size_t)F1, ecap1); });
+    if (!C.base) return mesh_oom(who, s);
+    MESH_CHECK(who, hipMemcpyAsync(C.wf, B.wf, (size_t)F0 * 12, hipMemcpyDeviceToDevice, s));
+    if (h_added) hipLaunchKernelGGL(p2s_rp_hole_fill_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, V, nxt, addc, B.addstart, F0, C.wf);
+    MESH_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
+    if ((rc = build_edges(who, C.wf, F1, C.t, C.fmn, C.fmx, s)) != P2S_OK) return rc;
+    hipLaunchKernelGGL(p2s_rp_edge_stats_kernel, dim3(blocks(ecap1, 256)), dim3(256), 0, s, C.t, ctr + RP_BOUNDARY);      // .. RP_INCONSISTENT
+    hipLaunchKernelGGL(p2s_rp_adj_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, C.wf, F1, C.t, C.fmn, C.fmx, C.adj, (unsigned char *)nullptr);
+    hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.parent, F1, 1);
+    hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, B.bparent, V, 1);
+    rc = until_unchanged(who, "the connected components", ctl, s, [&] {
+        hipLaunchKernelGGL(p2s_md_cc_hook_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.adj, C.parent, F1, ctl);
+        hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.parent, F1, 0);
+        hipLaunchKernelGGL(p2s_rp_bhook_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, C.wf, F1, C.t, B.bparent, ctl);
+        hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, B.bparent, V, 0);
+    });
     if (rc != P2S_OK) return rc;
-    hipLaunchKernelGGL(p2s_rp_edge_stats_kernel, dim3(blocks(ecap1, 256)), dim3(256), 0, s, t1, ctr + 0);
-    hipLaunchKernelGGL(p2s_rp_adj_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, wf1, F1, t1, fmn1, fmx1, adj1, (unsigned char *)nullptr);
-    hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, parent, F1, 1);
-    hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, bparent, V, 1);
-    RP_CHECK(hipGetLastError());
-    {
-        int changed = 1;
-        for (int it = 0; it < 100000 && changed; ++it) {
-            RP_CHECK(hipMemsetAsync(ctl, 0, 4, s));
-            hipLaunchKernelGGL(p2s_md_cc_hook_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, adj1, parent, F1, ctl);
-            hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, parent, F1, 0);
-            hipLaunchKernelGGL(p2s_rp_bhook_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, wf1, F1, t1, bparent, ctl);
-            hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, bparent, V, 0);
-            RP_CHECK(hipGetLastError());
-            RP_CHECK(hipMemcpyAsync(&changed, ctl, 4, hipMemcpyDeviceToHost, s));
-            RP_CHECK(hipStreamSynchronize(s));
-        }
-        if (changed) {
-            p2s_set_error("p2s_mesh_repair: the connected components did not converge");
-            return P2S_EHIP;
-        }
-    }
-    RP_CHECK(hipMemsetAsync(flag, 0, (size_t)F1 * 4, s));
-    RP_CHECK(hipMemsetAsync(onb, 0, (size_t)V * 4, s));
-    hipLaunchKernelGGL(p2s_rp_open_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, wf1, F1, t1, parent, flag);
-    hipLaunchKernelGGL(p2s_rp_bmark_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, wf1, F1, t1, onb);
-    hipLaunchKernelGGL(p2s_rp_bcount_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, bparent, onb, V, ctr + 4);
-    hipLaunchKernelGGL(p2s_md_cc_count_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, parent, F1, ctr + 3);
-    hipLaunchKernelGGL(p2s_rp_roots_flag_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, parent, F1, flag);
-    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, flag, F1, rstart);
-    RP_CHECK(hipGetLastError());
+    MESH_CHECK(who, hipMemsetAsync(C.flag, 0, (size_t)F1 * 4, s));
+    MESH_CHECK(who, hipMemsetAsync(C.onb, 0, (size_t)V * 4, s));
+    hipLaunchKernelGGL(p2s_rp_open_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, C.wf, F1, C.t, C.parent, C.flag);
+    hipLaunchKernelGGL(p2s_rp_bmark_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, C.wf, F1, C.t, C.onb);
+    hipLaunchKernelGGL(p2s_rp_bcount_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, B.bparent, C.onb, V, ctr + RP_BGROUPS);
+    hipLaunchKernelGGL(p2s_md_cc_count_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.parent, F1, ctr + RP_COMPONENTS);
+    hipLaunchKernelGGL(p2s_rp_roots_flag_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.parent, F1, C.flag);
+    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, C.flag, F1, C.rstart);
     int n_closed = 0;
-    RP_CHECK(hipMemcpyAsync(&n_closed, rstart + F1, 4, hipMemcpyDeviceToHost, s));
-    RP_CHECK(hipStreamSynchronize(s));
+    MESH_CHECK(who, hipGetLastError());
+    MESH_CHECK(who, hipMemcpyAsync(&n_closed, C.rstart + F1, 4, hipMemcpyDeviceToHost, s));
+    MESH_CHECK(who, hipStreamSynchronize(s));
     if (n_closed > 0) {
-        RpArena D;
-        const size_t d_tri = D.take((size_t)F1 * 72), d_roots = D.take((size_t)n_closed * 4), d_vol = D.take((size_t)n_closed * 8);
-        char *pd = pool.get(D.at);
-        if (!pd) return oom();
-        double *tri = (double *)(pd + d_tri), *vol = (double *)(pd + d_vol);
-        int *roots = (int *)(pd + d_roots);
-        hipLaunchKernelGGL(p2s_rp_roots_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, flag, rstart, F1, roots);
-        hipLaunchKernelGGL(p2s_rp_tri_kernel, dim3(blocks(9 * F1, 256)), dim3(256), 0, s, verts_dev, wf1, F1, tri);
-        hipLaunchKernelGGL(p2s_md_comp_volume_kernel, dim3((unsigned)n_closed), dim3(1024), 0, s, tri, parent, F1, roots, vol);
-        hipLaunchKernelGGL(p2s_rp_invert_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, parent, flag, rstart, vol, F1, wf1, ctr + 5);
-        RP_CHECK(hipGetLastError());
+        const RpVolumeWs D = pool.carve([&](char *b) { return carve_volume(b, (size_t)F1, (size_t)n_closed); });
+        if (!D.base) return mesh_oom(who, s);
+        hipLaunchKernelGGL(p2s_rp_roots_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.flag, C.rstart, F1, D.roots);
+        hipLaunchKernelGGL(p2s_rp_tri_kernel, dim3(blocks(9 * F1, 256)), dim3(256), 0, s, verts_dev, C.wf, F1, D.tri);
+        hipLaunchKernelGGL(p2s_md_comp_volume_kernel, dim3((unsigned)n_closed), dim3(1024), 0, s, D.tri, C.parent, F1, D.roots, D.vol);
+        hipLaunchKernelGGL(p2s_rp_invert_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.parent, C.flag, C.rstart, D.vol, F1, C.wf,
+                           ctr + RP_INVERTED);
     }
     // ---- g. compaction, h. report
-    RP_CHECK(hipMemsetAsync(used, 0, (size_t)V * 4, s));
-    hipLaunchKernelGGL(p2s_rp_used_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, wf1, F1, used);
-    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, used, V, vstart);
-    hipLaunchKernelGGL(p2s_md_volume_kernel, dim3(1), dim3(1024), 0, s, verts_dev, wf1, F1, (double *)(ctr + 8));
-    RP_CHECK(hipGetLastError());
+    MESH_CHECK(who, hipMemsetAsync(C.used, 0, (size_t)V * 4, s));
+    hipLaunchKernelGGL(p2s_rp_used_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, C.wf, F1, C.used);
+    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, C.used, V, C.vstart);
+    hipLaunchKernelGGL(p2s_md_volume_kernel, dim3(1), dim3(1024), 0, s, verts_dev, C.wf, F1, (double *)(ctr + RP_VOLUME));
     int hV1 = 0;
-    RP_CHECK(hipMemcpyAsync(hc, ctr, 256, hipMemcpyDeviceToHost, s));
-    RP_CHECK(hipMemcpyAsync(&hV1, vstart + V, 4, hipMemcpyDeviceToHost, s));
-    RP_CHECK(hipStreamSynchronize(s));          // also: every block of `pool` is idle from here on
+    MESH_CHECK(who, hipGetLastError());
+    MESH_CHECK(who, hipMemcpyAsync(&hV1, C.vstart + V, 4, hipMemcpyDeviceToHost, s));
+    if ((rc = read_counters(who, ctr, hc, -1, nullptr, s)) != P2S_OK) return rc;      // also: every block of `pool` is idle from here on
     double vol6;
-    memcpy(&vol6, &hc[8], 8);
+    memcpy(&vol6, &hc[RP_VOLUME], 8);
     rep_out[1] = hV1;
     rep_out[2] = F1;
-    rep_out[8] = (long long)hc[3];
-    rep_out[10] = (long long)hc[5];
-    rep_out[13] = (long long)hc[4];
-    rep_out[14] = (long long)hc[0] | ((long long)hc[1] << 32);
-    const int watertight = hc[0] == 0 && hc[1] == 0, consistent = hc[2] == 0;
+    rep_out[8] = (long long)hc[RP_COMPONENTS];
+    rep_out[10] = (long long)hc[RP_INVERTED];
+    rep_out[13] = (long long)hc[RP_BGROUPS];
+    rep_out[14] = (long long)hc[RP_BOUNDARY] | ((long long)hc[RP_NONMANIFOLD] << 32);
+    const int watertight = hc[RP_BOUNDARY] == 0 && hc[RP_NONMANIFOLD] == 0, consistent = hc[RP_INCONSISTENT] == 0;
     rep_out[15] = (watertight ? 1 : 0) | (consistent ? 2 : 0) | ((watertight && consistent && vol6 > 0.0) ? 4 : 0);
     publish();
     if (cap_verts < hV1 || cap_faces < F1) {
@@ -727,15 +667,16 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
                       F1, (long long)cap_verts, (long long)cap_faces);
         return P2S_EINVAL;
     }
-    hipLaunchKernelGGL(p2s_rp_write_verts_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, verts_dev, V, used, vstart, verts_out_dev);
-    hipLaunchKernelGGL(p2s_rp_write_faces_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, wf1, src, F1, F0, vstart, faces_out_dev,
+    hipLaunchKernelGGL(p2s_rp_write_verts_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, verts_dev, V, C.used, C.vstart, verts_out_dev);
+    hipLaunchKernelGGL(p2s_rp_write_faces_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.wf, B.src, F1, F0, C.vstart, faces_out_dev,
                        face_src_out_dev);
-    RP_CHECK(hipGetLastError());
-    RP_CHECK(hipStreamSynchronize(s));
+    MESH_CHECK(who, hipGetLastError());
+    MESH_CHECK(who, hipStreamSynchronize(s));
     return P2S_OK;
 }
 
 extern "C" int p2s_mesh_normalize(const float *verts_dev, int64_t n_verts, float *verts_out_dev, double *info_host, int device, void *stream) {
+    static const char *const who = "p2s_mesh_normalize";
     if (!verts_dev || !verts_out_dev || n_verts < 1 || n_verts > (1ll << 27)) {
         p2s_set_error("p2s_mesh_normalize: bad argument (1 <= vertices <= 2^27)");
         return P2S_EINVAL;
@@ -746,28 +687,16 @@ extern "C" int p2s_mesh_normalize(const float *verts_dev, int64_t n_verts, float
     }
     P2S_HIP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
-    RpScratch pool(device);
+    MeshScratch pool(device);
     int *ctl = (int *)pool.get(256);
-    if (!ctl) {
-        p2s_set_error("p2s_mesh_normalize: out of device memory");
-        return P2S_ENOMEM;
-    }
-    const int ctl_init[16] = {0, 0x7f800000, 0x7f800000, 0x7f800000, (int)0x807fffff, (int)0x807fffff, (int)0x807fffff, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int h[16] = {};
-    RP_CHECK(hipMemcpyAsync(ctl, ctl_init, 64, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(p2s_md_validate_kernel, dim3(blocks(n_verts, 256)), dim3(256), 0, s, verts_dev, (long long)n_verts, (const int *)nullptr,
-                       0ll, ctl);
-    RP_CHECK(hipGetLastError());
-    RP_CHECK(hipMemcpyAsync(h, ctl, 64, hipMemcpyDeviceToHost, s));
-    RP_CHECK(hipStreamSynchronize(s));
-    if (h[0]) {
-        p2s_set_error("p2s_mesh_normalize: non-finite vertex");
-        return P2S_EINVAL;
-    }
+    if (!ctl) return mesh_oom(who, s);
+    float box[6];
+    const int rc = mesh_validate(who, verts_dev, (long long)n_verts, (const int *)nullptr, 0ll, ctl, box, s);
+    if (rc != P2S_OK) return rc;
     double c[3], ext = 0.0;
     bool flat = false;
     for (int k = 0; k < 3; ++k) {
-        const double lo = rp_o2f(h[1 + k]), hi = rp_o2f(h[4 + k]);
+        const double lo = box[k], hi = box[3 + k];
         c[k] = (lo + hi) / 2.0;
         ext = std::max(ext, hi - lo);
         flat = flat || !(hi - lo > 0.0);
@@ -779,8 +708,8 @@ extern "C" int p2s_mesh_normalize(const float *verts_dev, int64_t n_verts, float
     const double sc = 1.0 / ext;
     hipLaunchKernelGGL(p2s_rp_normalize_kernel, dim3(blocks(3 * n_verts, 256)), dim3(256), 0, s, verts_dev, (long long)n_verts, c[0], c[1], c[2],
                        sc, verts_out_dev);
-    RP_CHECK(hipGetLastError());
-    RP_CHECK(hipStreamSynchronize(s));
+    MESH_CHECK(who, hipGetLastError());
+    MESH_CHECK(who, hipStreamSynchronize(s));
     if (info_host) {
         info_host[0] = c[0];
         info_host[1] = c[1];
@@ -789,4 +718,3 @@ extern "C" int p2s_mesh_normalize(const float *verts_dev, int64_t n_verts, float
     }
     return P2S_OK;
 }
-#undef RP_CHECK

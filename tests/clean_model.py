@@ -1,5 +1,5 @@
 """CPU model of the mesh repair and the normalisation (include/p2s_hip.h: p2s_mesh_repair, p2s_mesh_normalize;
-points2surf_amd/csrc/p2s_meshrepair.inl): a serial restatement in plain Python / numpy -- a dict of edges, union-find with
+points2surf_amd/csrc/p2s_meshrepair.inl; the shared kernels and build_edges: p2s_meshdist.hip): a serial restatement in plain Python / numpy -- a dict of edges, union-find with
 parity, loop walking.  Everything but the volumes is integer work, so it has one right answer; the float64 volume sums
 repeat the order of the device's kernels (p2s_md_volume_kernel, p2s_md_comp_volume_kernel: 1024 lanes each adding the
 faces f = lane, lane + 1024, ... in turn, an xor butterfly over the 64 lanes of a wave, the 16 waves added in order)."""

@@ -1,4 +1,5 @@
-"""Float64 numpy model of the mesh-distance kernels (points2surf_amd/csrc/p2s_meshdist.hip): the same operations in the
+"""Float64 numpy model of the mesh-distance kernels (points2surf_amd/csrc/p2s_meshdist.hip, the handle's in
+p2s_meshbuild.inl, the octree in p2s_mesh_octree.inl): the same operations in the
 same association, so the device's squared distances are expected to agree to rounding of sqrt / division only.
 
 * ``tri_closest``: closest point of a triangle by Ericson's regions (Real-Time Collision Detection 5.1.5) with the

@@ -1,4 +1,5 @@
-"""Float64 numpy model of the ray-casting kernels (points2surf_amd/csrc/p2s_meshray.inl): the same operations in the same
+"""Float64 numpy model of the ray-casting kernels (points2surf_amd/csrc/p2s_meshray.inl; the octree walk's
+helpers: p2s_mesh_octree.inl): the same operations in the same
 association, contraction off, so the device's t is expected to equal the model's bit for bit.
 
 * ``cast``: brute force, every ray against every triangle (Moeller-Trumbore through the face's own cross product:

@@ -1,6 +1,6 @@
 """numpy float64 model of the winding-number kernels (points2surf_amd/csrc/p2s_meshdist.hip: winding_term,
-p2s_md_winding_kernel, p2s_md_wtree_kernel): the exact generalised winding number (Jacobson et al. 2013, with the solid
-angle of van Oosterom & Strackee 1983), the moments of a set of triangles, the dipole that stands for them and the bound on
+p2s_md_winding_kernel, p2s_md_wtree_kernel; the moments: p2s_meshbuild.inl; the walk's helpers: p2s_mesh_octree.inl):
+the exact generalised winding number (Jacobson et al. 2013, with the solid angle of van Oosterom & Strackee 1983), the moments of a set of triangles, the dipole that stands for them and the bound on
 its error.  No device."""
 import numpy as np
 
