@@ -6,8 +6,10 @@ definitions are in include/p2s_hip.h.  This is the project's own definition of t
 The weld joins vertices with EQUAL float32 coordinates (no rounding to a tolerance: trimesh's 1e-8 is below the float32
 spacing over most of the unit cube).  Torch tensors are containers only; no CPU fallback.
 
-``python -m points2surf_amd.clean --indir DATASET [--stage convert|clean|normalize|all] [--max_faces N]
-[--no_enforce_solid] [--max_hole_edges K]``
+``python -m points2surf_amd.clean --indir DATASET [--stage convert|clean|normalize|all|check] [--max_faces N]
+[--no_enforce_solid] [--max_hole_edges K]``.  ``--stage check`` (not part of ``all``) reads ``03_meshes`` and writes
+``DATASET/check_report.csv``: the self-intersections and non-manifold vertices of every mesh (p2s_mesh_check), which
+the verdict "a volume" of the repair does not see.
 """
 import argparse
 import csv
@@ -30,6 +32,7 @@ REPORT_KEYS = ('verts_in', 'faces_in', 'verts_out', 'faces_out', 'verts_welded',
                'winding_consistent', 'is_volume')
 DIR_BASE, DIR_PLY, DIR_CLEANED, DIR_MESHES = '00_base_meshes', '01_base_meshes_ply', '02_meshes_cleaned', '03_meshes'
 REPORT_FILE = 'clean_report.csv'
+CHECK_REPORT_FILE = 'check_report.csv'
 
 
 class FlatMesh(ValueError):
@@ -201,10 +204,41 @@ def normalize_meshes_dir(indir, device=None):
     return written
 
 
+def check_verdict(rep):
+    """'self-intersecting' (an intersecting or coplanar pair of faces), else 'non-manifold' (a vertex whose faces are not
+    one fan), else 'embedded'; touching pairs are only counted"""
+    if rep['intersecting'] + rep['coplanar'] > 0:
+        return 'self-intersecting'
+    return 'non-manifold' if rep['nonmanifold_vertices'] > 0 else 'embedded'
+
+
+def check_meshes_dir(indir, device=None):
+    """``indir/check_report.csv`` (beside the stage directories, which hold meshes only): one row per ``03_meshes/*.ply`` with the counts of TriMesh.check and the verdict.
+    Returns the rows."""
+    from . import gt_sdf as _gt
+    in_dir = os.path.join(indir, DIR_MESHES)
+    rows = []
+    for name in _files(in_dir):
+        if not name.lower().endswith('.ply'):
+            continue
+        mesh = _gt.load_mesh(os.path.join(in_dir, name), device=device)
+        try:
+            rep = mesh.check()
+        finally:
+            mesh.close()
+        rows.append([name] + [rep[k] for k in _gt.CHECK_KEYS] + [check_verdict(rep)])
+    with open(os.path.join(indir, CHECK_REPORT_FILE), 'w', newline='') as fh:
+        w = csv.writer(fh)
+        w.writerow(['mesh'] + list(_gt.CHECK_KEYS) + ['verdict'])
+        w.writerows(rows)
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='write DATASET/01_base_meshes_ply, 02_meshes_cleaned and 03_meshes from 00_base_meshes')
     ap.add_argument('--indir', required=True)
-    ap.add_argument('--stage', choices=('convert', 'clean', 'normalize', 'all'), default='all')
+    ap.add_argument('--stage', choices=('convert', 'clean', 'normalize', 'all', 'check'), default='all',
+                    help='check (not part of all): DATASET/check_report.csv from 03_meshes, self-intersections and non-manifold vertices')
     ap.add_argument('--max_faces', type=int, default=None, help='reject meshes with this many faces or more')
     ap.add_argument('--no_enforce_solid', action='store_true', help='write meshes that are not a volume too')
     ap.add_argument('--max_hole_edges', type=int, default=4, help='fill holes of at most this many edges (0..64)')
@@ -216,6 +250,9 @@ def main(argv=None):
         files += clean_meshes_dir(opt.indir, opt.max_faces, not opt.no_enforce_solid, opt.max_hole_edges)
     if opt.stage in ('normalize', 'all'):
         files += normalize_meshes_dir(opt.indir)
+    if opt.stage == 'check':
+        check_meshes_dir(opt.indir)
+        files.append(os.path.join(opt.indir, CHECK_REPORT_FILE))
     for f in files:
         print(f)
 

@@ -5,7 +5,8 @@ in float64, positive inside like trimesh.  Torch tensors are containers only; no
 
 ``python -m points2surf_amd.gt_sdf --indir DATASET`` writes ``DATASET/05_query_dist`` from ``03_meshes`` and
 ``05_query_pts``; ``--sign winding`` takes every sign from the generalised winding number (p2s_mesh_winding), which is
-defined for open meshes too, where the default ``--sign pseudonormal`` refuses them.
+defined for open meshes too, where the default ``--sign pseudonormal`` refuses them; ``--sign auto`` checks every mesh for
+self-intersections (p2s_mesh_check) and takes the pseudonormal only where it is valid.
 """
 import argparse
 import ctypes
@@ -21,7 +22,10 @@ from .file_utils import call_necessary as _call_necessary
 
 METHODS = {'index': 0, 'exhaustive': 1}
 WINDING_METHODS = {'tree': 0, 'exhaustive': 1}
-SIGNS = ('pseudonormal', 'winding')
+SIGNS = ('pseudonormal', 'winding', 'auto')
+CHECK_KEYS = ('faces_tested', 'faces_degenerate', 'candidates', 'intersecting', 'coplanar', 'touching', 'duplicate',
+              'faces_flagged', 'pairs_inside_component', 'pairs_across_components', 'nonmanifold_vertices', 'pairs_stored')
+P2S_EINVAL = -1
 
 
 def winding_rounding(n_faces, terms, n_degenerate=0):
@@ -55,6 +59,7 @@ class TriMesh:
                                                    self.device.index, _engine._stream_ptr(self.device),
                                                    ctypes.byref(self.handle)))
         self.n_winding = 0
+        self.n_verts = int(v.shape[0])
 
     def info(self):
         """dict: n_faces, closed, inverted, bad_edges (open or non-manifold), grid (cells per axis), tests (point-triangle
@@ -122,6 +127,42 @@ class TriMesh:
             ((dict(accepted=int(st[0]), triangles=int(st[1]), redecided=int(st[2])),) if want_stats else ())
         return out[0] if len(out) == 1 else out
 
+    def check(self, method='index', want_pairs=False, want_flags=False, cap_pairs=None):
+        """Self-intersections and non-manifold vertices (p2s_mesh_check): the report as a dict (CHECK_KEYS;
+        pairs_inside_component / pairs_across_components are -1 on a mesh that is not closed).  ``want_pairs``: also the
+        pairs [n, 2] int32, (f, g) with f < g ascending, and their classes [n] uint8 (1 intersecting, 2 coplanar,
+        3 touching); ``want_flags``: also the face flags [F] uint8 (bits 1 / 2 / 4: in an intersecting / coplanar / touching
+        pair, 8: degenerate) and the vertex flags [V] uint8 (1: not manifold).  ``cap_pairs`` sizes the pair buffers
+        (default: a first call counts); too small a value raises P2SError with the needed count in its message."""
+        if self.handle is None:
+            raise RuntimeError('TriMesh is closed')
+        rep = (ctypes.c_int64 * 16)()
+        stream = _engine._stream_ptr(self.device)
+
+        def call(cap, pairs, cls, ff, vf):
+            with torch.cuda.device(self.device):
+                return self.lib.p2s_mesh_check(self.handle, METHODS[method], int(cap), _engine._ptr(pairs), _engine._ptr(cls),
+                                               _engine._ptr(ff), _engine._ptr(vf), rep, stream)
+        ff = vf = None
+        if want_flags:
+            n_faces = self.info()['n_faces']
+            ff = torch.empty((n_faces,), dtype=torch.uint8, device=self.device)
+            vf = torch.empty((self.n_verts,), dtype=torch.uint8, device=self.device)
+        if not want_pairs:
+            _lib.check(call(0, None, None, ff, vf))
+            out = (dict(zip(CHECK_KEYS, (int(x) for x in rep))),)
+        else:
+            if cap_pairs is None:
+                _lib.check(call(0, None, None, None, None))
+                cap_pairs = int(rep[11])
+            pairs = torch.empty((max(int(cap_pairs), 1), 2), dtype=torch.int32, device=self.device)
+            cls = torch.empty((max(int(cap_pairs), 1),), dtype=torch.uint8, device=self.device)
+            _lib.check(call(cap_pairs, pairs, cls, ff, vf))
+            n = int(rep[11])
+            out = (dict(zip(CHECK_KEYS, (int(x) for x in rep))), pairs[:n], cls[:n])
+        out = out + ((ff, vf) if want_flags else ())
+        return out[0] if len(out) == 1 else out
+
     def close(self):
         if getattr(self, 'handle', None) is not None and self.handle:
             self.lib.p2s_trimesh_destroy(self.handle)
@@ -134,11 +175,21 @@ class TriMesh:
             pass
 
 
+def auto_sign(mesh):
+    """what ``sign='auto'`` uses for ``mesh``: 'pseudonormal' when it is closed and no intersecting or coplanar pair of
+    faces lies inside one component (pairs across components are signed component by component anyway, and a mesh of more
+    than 16 components by the winding number), else 'winding'.  Returns (sign, the report of mesh.check())."""
+    rep = mesh.check()
+    return ('pseudonormal' if mesh.closed and rep['pairs_inside_component'] == 0 else 'winding'), rep
+
+
 def query_dist(mesh, query_pts, sign='pseudonormal'):
     """make_dataset.py:464-474: the signed distances of ``query_pts`` with NaN -> 0, inf -> 1, clamped to [-1, 1], as a
     float32 numpy array (the content of 05_query_dist/<shape>.npy)"""
     if sign not in SIGNS:
         raise ValueError('sign must be one of %s (got %r)' % (SIGNS, sign))
+    if sign == 'auto':
+        sign = auto_sign(mesh)[0]
     d = mesh.distance(query_pts, signed='winding' if sign == 'winding' else True)
     d = torch.nan_to_num(d, nan=0.0, posinf=1.0, neginf=1.0).clamp_(-1.0, 1.0)
     return d.to(torch.float32).cpu().numpy()
@@ -152,7 +203,9 @@ def load_mesh(path, device=None):
 def write_query_dist_dir(mesh_dir, query_pts_dir, out_dir, device=None, sign='pseudonormal'):
     """05_query_dist/<mesh>.npy for every 03_meshes/<mesh> that has 05_query_pts/<mesh>.npy (get_query_pts_dist_ms of
     make_dataset.py:481-530 without the query-point generation); files that are up to date are skipped.  Returns the
-    list of files written.  ``sign='pseudonormal'`` refuses a mesh that is not closed; ``'winding'`` signs any mesh."""
+    list of files written.  ``sign='pseudonormal'`` refuses a mesh that is not closed; ``'winding'`` signs any mesh;
+    ``'auto'`` takes the pseudonormal where auto_sign allows it and prints one line per mesh it switched to the winding
+    number."""
     if sign not in SIGNS:
         raise ValueError('sign must be one of %s (got %r)' % (SIGNS, sign))
     os.makedirs(out_dir, exist_ok=True)
@@ -170,7 +223,13 @@ def write_query_dist_dir(mesh_dir, query_pts_dir, out_dir, device=None, sign='ps
             if sign == 'pseudonormal' and not mesh.closed:
                 raise ValueError('%s is not closed (%d open or non-manifold edges): no signed distance'
                                  % (f_mesh, mesh.info()['bad_edges']))
-            np.save(f_out, query_dist(mesh, np.load(f_pts).astype(np.float32), sign=sign))
+            use = sign
+            if sign == 'auto':
+                use, rep = auto_sign(mesh)
+                if use == 'winding':
+                    print('%s: signed by the winding number (%s)' % (f_mesh, '%d intersecting and %d coplanar pairs of faces inside '
+                          'one component' % (rep['intersecting'], rep['coplanar']) if mesh.closed else 'not closed'))
+            np.save(f_out, query_dist(mesh, np.load(f_pts).astype(np.float32), sign=use))
         finally:
             mesh.close()
         written.append(f_out)
@@ -181,7 +240,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description='write DATASET/05_query_dist from 03_meshes and 05_query_pts')
     ap.add_argument('--indir', required=True)
     ap.add_argument('--sign', choices=SIGNS, default='pseudonormal',
-                    help='pseudonormal: closed meshes only (the default); winding: the generalised winding number, open meshes too')
+                    help='pseudonormal: closed meshes only (the default); winding: the generalised winding number, open meshes too; '
+                    'auto: the pseudonormal unless the mesh is open or intersects itself inside one component')
     opt = ap.parse_args(argv)
     for f in write_query_dist_dir(os.path.join(opt.indir, '03_meshes'), os.path.join(opt.indir, '05_query_pts'),
                                   os.path.join(opt.indir, '05_query_dist'), sign=opt.sign):

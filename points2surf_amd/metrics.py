@@ -162,7 +162,8 @@ def sdf_error(rec_dir, ref_meshes_dir, report_name, device=None, sign='pseudonor
     mesh ``ref_meshes_dir/<s>.*`` the exact signed distance of every query to the mesh (p2s_mesh_distance, clamped to
     [-1, 1] like the GT files) and, against the prediction, the MSE, the mean and max of |d_pred - d_gt| and the share of
     wrong signs.  One CSV in the style of mesh_comparison; returns its rows.  ``sign='pseudonormal'`` writes -1 for a GT
-    mesh that is not closed; ``sign='winding'`` signs every mesh by the generalised winding number."""
+    mesh that is not closed; ``sign='winding'`` signs every mesh by the generalised winding number; ``sign='auto'`` takes
+    the pseudonormal unless the mesh is open or intersects itself inside one component (gt_sdf.auto_sign)."""
     from . import gt_sdf as _gt
     if sign not in _gt.SIGNS:
         raise ValueError('sign must be one of %s (got %r)' % (_gt.SIGNS, sign))
@@ -178,11 +179,12 @@ def sdf_error(rec_dir, ref_meshes_dir, report_name, device=None, sign='pseudonor
         f_ref = os.path.join(ref_meshes_dir, match[0])
         mesh = _gt.load_mesh(f_ref, device=dev)
         try:
-            if sign == 'pseudonormal' and not mesh.closed:
+            use = _gt.auto_sign(mesh)[0] if sign == 'auto' else sign
+            if use == 'pseudonormal' and not mesh.closed:
                 results.append((os.path.join(dist_dir, name), f_ref, '0', '-1', '-1', '-1', '-1'))
                 continue
             pred = torch.from_numpy(np.load(os.path.join(dist_dir, name)).astype(np.float64).reshape(-1)).to(dev)
-            gt = mesh.distance(np.load(f_pts).astype(np.float32), signed='winding' if sign == 'winding' else True).clamp_(-1.0, 1.0)
+            gt = mesh.distance(np.load(f_pts).astype(np.float32), signed='winding' if use == 'winding' else True).clamp_(-1.0, 1.0)
         finally:
             mesh.close()
         err = (pred - gt).abs()
