@@ -60,7 +60,7 @@ static int screen_init(p2s_model_s *m) {
     const char *dense = getenv("P2S_CONV3_DENSE");
     if (dense && atoi(dense) != 0) return P2S_OK;
     int *flag = nullptr;
-    bool ok = hipMalloc(&m->scr_w3h, (size_t)4 * 2 * P2S_SCR_PIECE * 2) == hipSuccess && hipMalloc(&m->scr_mu, (size_t)4 * 1024 * 4) == hipSuccess &&
+    bool ok = hipMalloc(&m->scr_w3h, (size_t)4 * P2S_SCR_PIECE * 2) == hipSuccess && hipMalloc(&m->scr_mu, (size_t)4 * 1024 * 4) == hipSuccess &&
               hipMalloc(&m->scr_counters, 3 * 8) == hipSuccess && hipMalloc(&flag, 4) == hipSuccess &&
               hipMemset(m->scr_counters, 0, 3 * 8) == hipSuccess && hipMemset(flag, 0, 4) == hipSuccess;
     int rc = P2S_OK, h = 0;

@@ -211,36 +211,32 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-constexpr int SCR_HB = 128 + 8;      // halfs per row of an fp16 piece of the conv2 output tile (the fp16 pair kernel's layout)
+constexpr int SCR_HB = 128 + 8;      // halfs per row of the fp16 copy of the conv2 output tile (the fp16 pair kernel's layout)
 constexpr int SCR_QCAP = 256;        // candidates a wave's queue holds: < 64 left over + what one column tile may add
-constexpr float P2S_SCR_KAPPA = 0x1p-14f;   // k_screen + k_fp32 of the margin (derived in p2s_chain_screen.inl)
-// LDS of the screened kernel (floats): the two fp32 tiles, the h1 piece (h0 lies over bufA), the exact pool E [1024], the four
+constexpr float P2S_SCR_KAPPA = 0x1.1p-10f;   // k_screen + k_fp32 of the margin (derived in p2s_chain_screen.inl)
+// LDS of the screened kernel (floats): the two fp32 tiles (the fp16 copy of h lies over bufA), the exact pool E [1024], the four
 // waves' candidate queues, the reduction scratch
-constexpr int SCR_OFF_H1 = MT * SA + MT * SB;
-constexpr int SCR_OFF_E = SCR_OFF_H1 + MT * SCR_HB / 2;
+constexpr int SCR_OFF_E = MT * SA + MT * SB;
 constexpr int SCR_OFF_Q = SCR_OFF_E + 1024;
 constexpr int SCR_OFF_RED = SCR_OFF_Q + 4 * SCR_QCAP;
 constexpr int SCR_LDS_FLOATS = SCR_OFF_RED + 8;
-static_assert(MT * SCR_HB * 2 <= MT * SA * 4, "the h0 piece fits the 64-channel tile it lies over");
+static_assert(MT * SCR_HB * 2 <= MT * SA * 4, "the fp16 copy fits the 64-channel tile it lies over");
 static_assert(2 * SCR_LDS_FLOATS * 4 <= 160 * 1024, "two workgroups per CU");
 
 __device__ __forceinline__ u32x4 scr_bufld(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
     return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
 }
-// A fragment of rows row0 .. row0+31, k-block kb of one fp16 piece: 8 consecutive k of row l & 31, k = 16 kb + 8 (l >> 5) + [0, 8)
+// A fragment of rows row0 .. row0+31, k-block kb of the fp16 tile: 8 consecutive k of row l & 31, k = 16 kb + 8 (l >> 5) + [0, 8)
 __device__ __forceinline__ u32x4 scr_lds_a(const unsigned short *buf, int row0, int kb, int lane) {
     return *reinterpret_cast<const u32x4 *>(buf + (row0 + (lane & 31)) * SCR_HB + 16 * kb + 8 * (lane >> 5));
 }
 __device__ __forceinline__ f32x16 scr_mfma(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
-// two fp32 values -> their fp16 pairs, packed (a low half): h0 = fp16(x), h1 = fp16((x - h0) * 2^11)
-__device__ __forceinline__ void scr_split(float a, float b, unsigned &p0, unsigned &p1) {
+// two fp32 values -> fp16 (round to nearest even), packed (a low half)
+__device__ __forceinline__ unsigned scr_half2(float a, float b) {
     const f32x2 v = {a, b};
-    const f16x2 h = __builtin_convertvector(v, f16x2);
-    p0 = __builtin_bit_cast(unsigned, h);
-    const f32x2 r = {(a - (float)h[0]) * 2048.0f, (b - (float)h[1]) * 2048.0f};
-    p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
 }
 // One candidate (entry = row << 16 | channel within the wave's 256): the fp32 dot product of row `row` of the conv2 tile with
 // column c of the packed conv3 fragments ([N/32][16][2][32][4]: k = 8 g + 4 kk + t), summed as the dense kernel's MFMA chain
@@ -271,7 +267,7 @@ __device__ __forceinline__ void scr_confirm(unsigned entry, const float *hB, con
     else atomicMin(reinterpret_cast<unsigned *>(E + cw), (unsigned)bits);
 }
 
-// SCREEN (max pool, full chain only): conv3 through p2s_chain_screen.inl, two workgroups per CU (78 KB of LDS); an item the
+// SCREEN (max pool, full chain only): conv3 through p2s_chain_screen.inl, two workgroups per CU (58 KB of LDS); an item the
 // screen cannot decide runs a second time with the dense conv3 below
 template <bool SUM, bool SCREEN = false>
 __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArgs args) {
@@ -357,11 +353,11 @@ __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArg
     const int ntiles = (P + MT - 1) / MT;
     float nx0, nx1, nx2;
     // screened conv3: the state of p2s_chain_screen.inl
-    float *scr_h1 = smem + SCR_OFF_H1, *scr_E = smem + SCR_OFF_E + 256 * wave, *scr_red = smem + SCR_OFF_RED;
+    float *scr_E = smem + SCR_OFF_E + 256 * wave, *scr_red = smem + SCR_OFF_RED;
     unsigned *scr_q = reinterpret_cast<unsigned *>(smem + SCR_OFF_Q) + SCR_QCAP * wave;
     const float *__restrict__ scr_mu = args.w3mu[bsel];
     const __amdgpu_buffer_rsrc_t rs3h = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(args.w3h[bsel]), 0,
-                                                                           (int)(P2S_SCR_PIECE * 4), 0x00020000);
+                                                                           (int)(P2S_SCR_PIECE * 2), 0x00020000);
     float sr0 = -INFINITY, sr1 = -INFINITY, sr2 = -INFINITY, sr3 = -INFINITY, sr4 = -INFINITY, sr5 = -INFINITY, sr6 = -INFINITY,
           sr7 = -INFINITY;                     // running maxima of the screen values of this lane's column of the 8 column tiles
     bool undec = false;                        // the screen cannot decide this item (wave-uniform)
@@ -640,10 +636,8 @@ __global__ void p2s_screen_mu_kernel(const float *__restrict__ w3, float *__rest
 }
 
 int p2s_launch_screen_prepare(const float *w32, unsigned short *dst, float *mu, hipStream_t stream, int *range_flag) {
-    for (int piece = 0; piece < 2; ++piece) {
-        const int rc = p2s_launch_pack_bf16(w32, dst + piece * P2S_SCR_PIECE, 128, 1024, 0, 0, 1, piece, 1, stream, range_flag);
-        if (rc) return rc;
-    }
+    const int rc = p2s_launch_pack_bf16(w32, dst, 128, 1024, 0, 0, 1, 0, 1, stream, range_flag);
+    if (rc) return rc;
     hipLaunchKernelGGL(p2s_screen_mu_kernel, dim3(4), dim3(256), 0, stream, w32, mu);
     P2S_LAUNCH_CHECK("p2s_screen_mu_kernel");
     return P2S_OK;

@@ -2,9 +2,8 @@
 // p2s_chain_kernel<false, true> (the same reason as p2s_chain_conv3.inl: the pooled state stays in registers / LDS).
 //
 // conv3 feeds only a max over the item's points: of the P x 1024 dot products 1024 reach the output.  This path decides on
-// the fp16-pair MFMA which products can be the maximum and computes only those in fp32:
-//   screen   t[p][c] = acc0 + acc1 * 2^-11 on v_mfma_f32_32x32x16_f16, h and w as fp16 pairs (the arithmetic of
-//            p2s_chain_bf16_kernel<2, true>: 3 MFMAs per product at 1/16 of the fp32 MFMA's cost each);
+// ONE fp16 MFMA per product block which products can be the maximum and computes only those in fp32:
+//   screen   t[p][c] = sum_k fp16(h_pk) fp16(w_ck) on v_mfma_f32_32x32x16_f16, fp32 accumulate, one accumulator set;
 //   margin   mu_c = 2 (k_screen + k_fp32) (|w_c| + 2^-10) (H + 2^-10),  H >= |h_p| for every row of every tile of the item so
 //            far, this one included (a running maximum: the margin only grows from tile to tile);
 //   select   (p, c) is a candidate iff t[p][c] >= R_c - mu_c, R_c = the running maximum of t[.][c] over the tiles so far,
@@ -12,50 +11,59 @@
 //   confirm  each candidate at once, while its fp32 row h[p] is still in LDS: one chain of 128 fmaf in the k order of the
 //            32x32x2 MFMA chain of p2s_chain_conv3.inl (k-groups ascending, t = 0..3, 8g+t then 8g+4+t; rows of the 16-row
 //            tail: the two half chains, then one add), one lane per candidate;  E_c = max of the confirmed values.
+// The pooled value never comes from the screen: the screen only has to say safely which products cannot win.
 //
 // Exactness.  Write s*_x for the real-number dot product of row x, fl(s_x) for the fp32 chain, d_x >= |t_x - s*_x| and
 // g_x >= |fl(s_x) - s*_x|; both scale with |w_c| |h_x|: d_x + g_x <= (k_screen + k_fp32) (|w_c| + 2^-10) (|h_x| + 2^-10).  A
 // dismissed p had t_p < R - mu_c at its tile, with R = t_q of a row q of THAT OR AN EARLIER tile that was a candidate when it
 // set the record (t_q = R >= R - mu_c; if q is a padding row, the item's last point, which it replicates, has the same
-// operands and lies within d of it).  mu_c is built from H >= max(|h_p|, |h_q|) -- the running maximum over the tiles so
+// operands and the same t).  mu_c is built from H >= max(|h_p|, |h_q|) -- the running maximum over the tiles so
 // far, not this tile's alone: the record holder may be a row of larger norm than any of the current tile -- so
 // (d_p + g_p) + (d_q + g_q) <= mu_c and
 //     fl(s_p) <= s*_p + g_p <= t_p + d_p + g_p < t_q - mu_c + d_p + g_p <= t_q - d_q - g_q <= s*_q - g_q <= fl(s_q):
 // p cannot hold the maximum over all P fp32 values and E_c is that maximum: the value p2s_chain_kernel<false> pools.
 //
-// The two k, per unit |w_c| |h_p| (>= sum |w| |h|):
-//   operands    an fp16 pair keeps |x - (h0 + h1 2^-11)| <= 2^-22 |x| + 2^-36 (the second term: pieces below fp16's normal
-//               range).  Both operands: 2 * 2^-22; the absolute parts are what the + 2^-10 of the margin's two factors pay for
-//               (2^-22 * 2^-10 >= 2^-36 * sqrt(128));
-//   h1 h1'      the dropped piece product: 2^-22;
+// The two k.  S = sum_k |w_k| |h_k| <= |w_c| |h_p| (Cauchy-Schwarz), N1 = sum_k |x_k| <= sqrt(128) |x|.
+//   operands    each is rounded ONCE to fp16: |fp16(x) - x| <= 2^-11 |x| in the normal range, <= 2^-25 below 2^-14 (half a
+//               subnormal step), so always <= 2^-11 |x| + 2^-25 (values beyond the range never get here: `undec`).  Per product
+//               |fp16(h) fp16(w) - h w| <= (2^-10 + 2^-22) |h| |w| + 2^-25 (1 + 2^-11) (|h| + |w|) + 2^-50; over the 128 k:
+//                   (2^-10 + 2^-22) S   +   2^-21.5 (1 + 2^-11) (|h_p| + |w_c|) + 2^-43.
+//               The second part is what the + 2^-10 of the margin's two factors pay for: k 2^-10 (|w_c| + |h_p|) + k 2^-20 with
+//               k >= 2^-10 is 2^-20 (|w_c| + |h_p|) + 2^-30, 2.8 times what is needed -- the floor of the pair screen
+//               (2^-36 sqrt(128) against 2^-22 2^-10) was tighter than this one, the terms stay as they are;
 //   screen sum  8 MFMAs of 16 exact products each into an fp32 accumulator; allowing every one of the 136 additions a
-//               truncation (2^-23, twice round-to-nearest) of a partial sum <= sum |w| |h|: 136 * 2^-23 = 2^-15.9;
-//               the second accumulator enters times 2^-11, the final fma adds 2^-24;
-//   fp32 chain  128 roundings of a partial sum <= sum |w| |h|, again allowing truncation: 128 * 2^-23 = 2^-16 (the tail
+//               truncation (2^-23, twice round-to-nearest) of a partial sum <= sum |fp16(w)| |fp16(h)| <= (1 + 2^-9) S + the
+//               absolute part above: 136 * 2^-23 (1 + 2^-9) < 2^-15.9;
+//   fp32 chain  128 roundings of a partial sum <= S, again allowing truncation: 128 * 2^-23 = 2^-16 (the tail
 //               rows' extra add included in the slack).
-//   k_screen + k_fp32 <= 2^-15.8 + 2^-16 < 2^-14 = P2S_SCR_KAPPA, the constant the coefficients are built with (1.8 x slack).
+//   k_screen + k_fp32 <= 2^-10 (1 + 2^-12 + 2^-5.9 + 2^-6) < 1.0326 * 2^-10  <=  1.0625 * 2^-10 = P2S_SCR_KAPPA (0x1.1p-10,
+//   2.9 % slack; the candidate count grows with the constant -- about twice per doubling -- so it is not rounded up further).
+//   The threshold R - mu is one more fp32 rounding (2^-24 |R|, |R| <= about |w_c| H): the two factors (1 + 2^-10) with which
+//   mu_c and H are rounded up add 2^-9 mu >= 2^-19 |w_c| H and pay for it and for the roundings of the norms.
 //
 // What the screen cannot decide runs densely: an item with an activation beyond the half range, or with more candidates
 // in one column tile than the wave's queue holds (a patch of identical points: every product ties), sets `undec`, and the
 // workgroup runs the item again through the dense conv3 (p2s_chain_kernel's own) when its screened pass ends.
+//
+// Schedule.  With one MFMA per fragment pair (64 matrix-pipe cycles per k-block of the two row tiles) every operand byte
+// counts: the A fragments of the tile (the fp16 rows, the same for all 8 column tiles) are read from LDS ONCE into 64
+// registers -- re-reading them per column tile (2 x ds_read_b128 per k-block and wave) alone would take the LDS port of the
+// CU for as long as the MFMAs take -- and the weight stream is one ring of 8 slots over the tile's 8 x 8 k-blocks, 7
+// requests (7 KB per wave) in flight: k-block j + 7 is requested between the two MFMAs of k-block j, across the select, the
+// queue and the confirm of a column tile too.
 {
-            unsigned short *hp0 = reinterpret_cast<unsigned short *>(bufA);      // h0 [64][SCR_HB] over the conv2 input tile
-            unsigned short *hp1 = reinterpret_cast<unsigned short *>(scr_h1);    // h1 [64][SCR_HB]
+            unsigned short *hp0 = reinterpret_cast<unsigned short *>(bufA);      // fp16(h) [64][SCR_HB] over the conv2 input tile
             // ---- the weight stream: ONE ring over the tile's 8 column tiles x 8 k-blocks ---------------------------------
-            // A wave's fragments of consecutive k-blocks and column tiles are consecutive KBs of the packed pieces, so the
-            // stream does not know column tiles: the fragments of k-block j + 3 are requested while the MFMAs of k-block j
-            // issue (4 slots of 2 x 4 registers, 3 in flight), across the select, the queue and the confirm of a column tile
-            // too.  The first three are requested here and land during the split.  (The last three requests of a tile run
-            // past the wave's own fragments: they read the next wave's, or, past the end of the buffer, zeros; nothing uses them.)
+            // A wave's fragments of consecutive k-blocks and column tiles are consecutive KBs of the packed fragments, so the
+            // stream does not know column tiles.  The first seven are requested here and land during the conversion.  (The
+            // last seven requests of a tile run past the wave's own fragments: they read the next wave's, or, past the end of
+            // the buffer, zeros; nothing uses them.)
             const int soff0 = wave * 8 * 8 * 1024;          // bytes: 8 k-blocks of 64 lanes x 16 B per column tile
-            u32x4 rb0[4], rb1[4];
+            u32x4 rb[8];
 #pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                rb0[s] = scr_bufld(rs3h, lane16, soff0 + s * 1024);
-                rb1[s] = scr_bufld(rs3h, lane16, (int)(P2S_SCR_PIECE * 2) + soff0 + s * 1024);
-            }
+            for (int s = 0; s < 7; ++s) rb[s] = scr_bufld(rs3h, lane16, soff0 + s * 1024);
             float mu_c = scr_mu[256 * wave + (lane & 31)];                       // margin coefficient of column tile 0
-            // ---- h -> fp16 pair beside the fp32 tile; row norms --------------------------------------------------------
+            // ---- h -> fp16 beside the fp32 tile; row norms -------------------------------------------------------------
             if (scr_abl != 5) {
                 const int p = tid >> 2, q = tid & 3;
                 const float *src = bufB + p * SB + 32 * q;
@@ -64,13 +72,7 @@
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const f32x4 v0 = lds4(src + 8 * i), v1 = lds4(src + 8 * i + 4);
-                    unsigned q0[4], q1[4];
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        scr_split(v0[2 * u], v0[2 * u + 1], q0[u], q1[u]);
-                        scr_split(v1[2 * u], v1[2 * u + 1], q0[2 + u], q1[2 + u]);
-                    }
-                    const u32x4 w0 = {q0[0], q0[1], q0[2], q0[3]}, w1 = {q1[0], q1[1], q1[2], q1[3]};
+                    const u32x4 w0 = {scr_half2(v0[0], v0[1]), scr_half2(v0[2], v0[3]), scr_half2(v1[0], v1[1]), scr_half2(v1[2], v1[3])};
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         ss = fmaf(v0[u], v0[u], ss);
@@ -78,7 +80,6 @@
                         oor = oor || p2s_f16_out_of_range(v0[u]) || p2s_f16_out_of_range(v1[u]);
                     }
                     *reinterpret_cast<u32x4 *>(hp0 + p * SCR_HB + 32 * q + 8 * i) = w0;
-                    *reinterpret_cast<u32x4 *>(hp1 + p * SCR_HB + 32 * q + 8 * i) = w1;
                 }
                 ss += __shfl_xor(ss, 1);
                 ss += __shfl_xor(ss, 2);
@@ -106,78 +107,45 @@
                     vmask |= (row < nvalid || (replica && row == 32) ? 1u : 0u) << j;
                 }
             }
-            // A fragments one k-block ahead of their MFMAs; they are the same for every column tile, so k-block 7 fetches
-            // k-block 0 of the next one
-            u32x4 fa[2][2];
+            // the tile's A fragments, once: both row tiles x 8 k-blocks
+            u32x4 fa[8][2];
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                fa[r][0] = scr_lds_a(hp0, 32 * r, 0, lane);
-                fa[r][1] = scr_lds_a(hp1, 32 * r, 0, lane);
+            for (int kb = 0; kb < 8; ++kb) {
+                fa[kb][0] = scr_lds_a(hp0, 0, kb, lane);
+                fa[kb][1] = scr_lds_a(hp0, 32, kb, lane);
             }
             int qn = 0;                                                          // entries in this wave's queue (wave-uniform)
 #pragma unroll 1
             for (int ct = 0; ct < 8; ++ct) {
                 const int soff = soff0 + ct * 8 * 1024;
-                f32x16 acc[2][2];
-                // per accumulator the order of the products is a1 b0, a0 b1 (acc1) and a0 b0 (acc0), k-blocks ascending; the two
-                // row tiles alternate so that no MFMA follows one it depends on.  One memory instruction per MFMA shadow.
+                f32x16 acc[2];
+                // k-blocks ascending; the two row tiles alternate so that no MFMA follows the one it depends on, the ring's
+                // request sits between them
 #pragma unroll
                 for (int kb = 0; kb < 8; ++kb) {
-                    const int use = kb & 3, req = (kb + 3) & 3;
-                    const u32x4 b0 = rb0[use], b1 = rb1[use];
-                    rb0[req] = scr_bufld(rs3h, lane16, soff + (kb + 3) * 1024);
-                    rb1[req] = scr_bufld(rs3h, lane16, (int)(P2S_SCR_PIECE * 2) + soff + (kb + 3) * 1024);
-                    u32x4 na[2][2];
-                    // the h1 fragments first: their registers are free after the first two MFMAs
-                    na[0][1] = scr_lds_a(hp1, 0, (kb + 1) & 7, lane);
-                    na[1][1] = scr_lds_a(hp1, 32, (kb + 1) & 7, lane);
-                    na[0][0] = scr_lds_a(hp0, 0, (kb + 1) & 7, lane);
-                    na[1][0] = scr_lds_a(hp0, 32, (kb + 1) & 7, lane);
+                    const u32x4 b = rb[kb];
+                    rb[(kb + 7) & 7] = scr_bufld(rs3h, lane16, soff + (kb + 7) * 1024);
                     if (kb == 0) {
-                        acc[0][1] = scr_mfma(fa[0][1], b0, zero16());
-                        acc[1][1] = scr_mfma(fa[1][1], b0, zero16());
+                        acc[0] = scr_mfma(fa[0][0], b, zero16());
+                        acc[1] = scr_mfma(fa[0][1], b, zero16());
                     } else {
-                        acc[0][1] = scr_mfma(fa[0][1], b0, acc[0][1]);
-                        acc[1][1] = scr_mfma(fa[1][1], b0, acc[1][1]);
+                        acc[0] = scr_mfma(fa[kb][0], b, acc[0]);
+                        acc[1] = scr_mfma(fa[kb][1], b, acc[1]);
                     }
-                    acc[0][1] = scr_mfma(fa[0][0], b1, acc[0][1]);
-                    acc[1][1] = scr_mfma(fa[1][0], b1, acc[1][1]);
-                    if (kb == 0) {
-                        acc[0][0] = scr_mfma(fa[0][0], b0, zero16());
-                        acc[1][0] = scr_mfma(fa[1][0], b0, zero16());
-                    } else {
-                        acc[0][0] = scr_mfma(fa[0][0], b0, acc[0][0]);
-                        acc[1][0] = scr_mfma(fa[1][0], b0, acc[1][0]);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 2; ++r) {
-                        fa[r][0] = na[r][0];
-                        fa[r][1] = na[r][1];
-                    }
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 }
                 if (scr_abl == 3) {       // MFMAs and their loads only: one value of each accumulator, pooled, keeps them live
-                    sr0 = fmaxf(sr0, (acc[0][0][0] + acc[0][1][0]) + (acc[1][0][0] + acc[1][1][0]));
+                    sr0 = fmaxf(sr0, acc[0][0] + acc[1][0]);
                     if (ct == 7) scr_E[lane] = sr0;
                     continue;
                 }
                 const float mu = mu_c * Heff;
                 mu_c = scr_mu[256 * wave + 32 * (ct < 7 ? ct + 1 : 7) + (lane & 31)];   // the next column tile's, behind the ring's requests
-                float tv[32];
+                float m = fmaxf(acc[0][0], acc[0][1]);
 #pragma unroll
-                for (int j = 0; j < 32; ++j) tv[j] = fmaf(acc[j >> 4][1][j & 15], 0x1p-11f, acc[j >> 4][0][j & 15]);
-                float m = fmaxf(tv[0], tv[1]);
-#pragma unroll
-                for (int j = 2; j < 32; j += 2) m = fmaxf(fmaxf(m, tv[j]), tv[j + 1]);
+                for (int j = 2; j < 32; j += 2) m = fmaxf(fmaxf(m, acc[j >> 4][j & 15]), acc[j >> 4][(j & 15) + 1]);
                 m = half_max(m);
                 float R;
                 if (ct == 0) R = sr0 = fmaxf(sr0, m);
@@ -191,7 +159,7 @@
                 const float thr = R - mu;
                 unsigned mask = 0;
 #pragma unroll
-                for (int j = 0; j < 32; ++j) mask |= (tv[j] >= thr ? 1u : 0u) << j;
+                for (int j = 0; j < 32; ++j) mask |= (acc[j >> 4][j & 15] >= thr ? 1u : 0u) << j;
                 mask &= vmask;
                 // candidates -> this wave's queue, one per lane and round (ballot / mbcnt compaction)
                 while (!undec) {
@@ -230,5 +198,5 @@
                 }
                 __builtin_amdgcn_wave_barrier();
             }
-            __syncthreads();          // h0 lies over the next tile's first-layer output
+            __syncthreads();          // fp16(h) lies over the next tile's first-layer output
 }

@@ -85,15 +85,15 @@ struct ChainArgs {
     int *bad_items;          // fp16 pair mode: [items per branch] flag of every item (= query of the chunk) an activation of
                              // which left the half range -- the query is re-run through the fp32 kernels (p2s_forward.hip: fallback)
     // fp32 kernel, screened conv3 (p2s_chain_screen.inl): 1 = both branches are full-chain max-pool passes of a model that holds
-    // the screen operands.  Per branch: conv3 as fp16 pair fragments ([N/32][K/16][64 lanes][8], piece 1 P2S_SCR_PIECE halfs
-    // behind piece 0) and the per-channel margin coefficient [1024]
+    // the screen operands.  Per branch: conv3 rounded to fp16 as fragments ([N/32][K/16][64 lanes][8], contiguous in the order
+    // the kernel's ring reads them) and the per-channel margin coefficient [1024]
     int screen;
     const unsigned short *w3h[2];
     const float *w3mu[2];
     unsigned long long *scr_counters;     // [3] fp32 chains run, items re-run densely, items
 };
 constexpr long long P2S_SCR_PIECE = 128 * 1024;
-// the screen operands of one 128 x 1024 layer: fp16 pair fragments dst [2][P2S_SCR_PIECE] and margin coefficients mu [1024] from
+// the screen operands of one 128 x 1024 layer: fp16 fragments dst [P2S_SCR_PIECE] and margin coefficients mu [1024] from
 // the packed fp32 fragments; *range_flag is raised when a weight does not fit the half range
 int p2s_launch_screen_prepare(const float *w32, unsigned short *dst, float *mu, hipStream_t stream, int *range_flag);
 int p2s_launch_chain(const ChainArgs &args, hipStream_t stream);

@@ -81,13 +81,13 @@ struct p2s_model_s {
     const unsigned short *w16(P2sLayer layer, int z) const { return blob_h + h_off[layer][z]; }
     uint64_t offset(size_t member) const { return *reinterpret_cast<const uint64_t *>(reinterpret_cast<const char *>(&offs) + member); }
     // screened conv3 of the fp32 kernel (p2s_chain_screen.inl; mode 0 only): the conv3
-    // layers of the STN and main trunks (layer = L_S3 / L_M3, encoder z) as fp16 pair fragments [2][2][2 pieces][P2S_SCR_PIECE] and
+    // layers of the STN and main trunks (layer = L_S3 / L_M3, encoder z) rounded to fp16, as fragments [2][2][P2S_SCR_PIECE], and
     // their margin coefficients [2][2][1024], built at creation; NULL: the dense conv3 (P2S_CONV3_DENSE=1, a sym_op='sum' main
     // trunk keeps it for that pass, a conv3 weight beyond the half range for the model)
     unsigned short *scr_w3h = nullptr;
     float *scr_mu = nullptr;
     unsigned long long *scr_counters = nullptr;     // device [3]: fp32 chains run, items re-run densely, items -- per call
-    const unsigned short *screen_w(P2sLayer layer, int z) const { return scr_w3h + ((layer == L_M3 ? 2 : 0) + z) * 2 * P2S_SCR_PIECE; }
+    const unsigned short *screen_w(P2sLayer layer, int z) const { return scr_w3h + ((layer == L_M3 ? 2 : 0) + z) * P2S_SCR_PIECE; }
     const float *screen_mu(P2sLayer layer, int z) const { return scr_mu + ((layer == L_M3 ? 2 : 0) + z) * 1024; }
     // fp16 pair mode: queries with an activation beyond the half range are flagged by the 16-bit kernels, collected per
     // chunk (inputs copied aside) and re-run through the fp32 kernels at the end of the same call (ModelCall::finish)
