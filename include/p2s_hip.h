@@ -613,6 +613,61 @@ int p2s_mesh_check(p2s_trimesh_t m, int method, int64_t cap_pairs, int32_t *pair
                    uint8_t *face_flags_out_dev, uint8_t *vert_flags_out_dev, int64_t *report_host, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * "next" row: inside / outside of a CLOSED mesh on the volume's grid, and the reductions of the
+ * reconstruction-quality report (volumetric IoU, F-score, normal consistency: points2surf_amd/metrics.py, mesh_quality).
+ * The project's own definition; every result is a function of the input alone.
+ * Grid: grid_res = R in 2..1024; voxel (i, j, k) has the centre (c(i), c(j), c(k)), c(i) = the float32 nearest to
+ * ((i + 0.5) / R) * 2.0 - 1.0 evaluated in float64 (volume_space_to_model_space of the reference's source/sdf.py:78, rounded as
+ * its query grids are): a float32 value held exactly in float64, like every mesh coordinate.  occ_out_dev is [R][R][R]
+ * uint8, x-major with z fastest (the layout of p2s_sdf_volume): 1 inside, 0 outside.  The handle must be closed (info[1]),
+ * else P2S_EINVAL and nothing written; an inward-oriented closed mesh is stored flipped and voxelised as stored.
+ * Arithmetic: float64, contraction off, orient3 and the filter bounds of p2s_mesh_check with S' = max(S, 1) in the place
+ * of S (S the mesh's largest |coordinate|; |c| < 1): 2^-47 S'^2 in the plane, 2^-43 S'^3 in space (why the proof carries
+ * over: csrc/p2s_meshvoxel.inl).  orient2(a, b, c) = (bx - ax)(cy - ay) - (by - ay)(cx - ax) ALWAYS on x and y, z dropped.
+ * A column is the line x = c(i), y = c(j).  For a face T = (a, b, c) of the handle and P = (c(i), c(j)):
+ *     sigma = sign orient2(a, b, c);   s0, s1, s2 = sign orient2(b, c, P), orient2(c, a, P), orient2(a, b, P),
+ * each a sign only beyond 2^-47 S'^2, else 0.
+ *  - The column MISSES T when P lies outside T's closed xy bounding box (exact comparisons), or when some s is > 0 and
+ *    another is < 0.
+ *  - The column CROSSES T with the direction sigma when sigma != 0 and s0 = s1 = s2 = sigma: all four signs are then
+ *    exact and P lies strictly inside the projected triangle.
+ *  - Anything else makes the COLUMN UNDECIDED: P within rounding of an edge or a vertex, or the face seen edge-on with P
+ *    not strictly clear of it.  Degenerate faces get no rule of their own; they can never be crossed.
+ * For a decided column and a crossing (T, sigma), the voxel with the centre p lies below the crossing when
+ * sign(orient3(a, b, c, p), beyond 2^-43 S'^3) * sigma < 0 and above it when > 0; the sign 0 makes the VOXEL UNDECIDED.  The
+ * winding number of a decided voxel is w = the sum of sigma over the crossings it lies below -- every predicate that
+ * decided it is exact, so w is the exact integer winding number -- and occ = (w != 0): a cavity (an inward shell inside an
+ * outward one) is empty, the overlap of two solids is inside.
+ * The undecided voxels (every voxel of an undecided column and the singly undecided ones, U in all) are decided by the
+ * exact winding sum of p2s_mesh_winding, method 1, on their centres: inside iff |w| > 0.5.  flags_out_dev [R][R][R] (may be
+ * NULL) is 1 for them, 0 otherwise.  U * n_faces is what they cost: U > max_fallback returns P2S_ECAPACITY with the
+ * report filled ([0] then counts the decided voxels only) and NO output written.
+ * method 0 = one column per thread walks the handle's octree, a node being opened when its closed xy rectangle contains
+ * P (every face sits in exactly one leaf, so none is met twice; a stack overflow fails the call as in the other walks);
+ * method 1 = every column against every face (the yardstick): identical arrays and reports except report [4].
+ * report_host [8] int64: [0] voxels inside   [1] undecided columns   [2] singly undecided voxels (in decided columns)
+ *   [3] U = R * [1] + [2]   [4] (column, face) tests made (method 1: R^2 n_faces)   [5] crossings, over all columns
+ *   [6], [7] 0.
+ * Scratch comes from the device's block cache and returns to it before the call ends.  Synchronises `stream`.
+ * ------------------------------------------------------------------------------------------ */
+int p2s_mesh_voxelize(p2s_trimesh_t m, int grid_res, int method, int64_t max_fallback, uint8_t *occ_out_dev,
+                      uint8_t *flags_out_dev, int64_t *report_host, void *stream);
+/* n surface samples of the mesh `from` measured against the mesh `to`: dist_dev [n] float64 (unsigned, p2s_mesh_distance
+ * on `to`), face_from_dev [n] the sample's own face (p2s_mesh_sample_surface), face_to_dev [n] the nearest face on `to`.
+ * out_host [4 + n_taus]: sum d, sum d^2, max d, sum |n_from . n_to| (the handles' stored unit normals), then the count of
+ * d <= taus_host[t] for each of the n_taus <= 8 thresholds.  *nc_pairs_host = the pairs in the normal sum: a pair with a
+ * face under the degenerate rule (its stored normal is 0), or with a face id out of range (-1: a non-finite query), is
+ * left out.  float64 sums in an order that depends on n alone (csrc/p2s_meshvoxel.inl): two runs give the same bits.
+ * Both handles on one device.  Synchronises `stream`. */
+int p2s_surface_stats(p2s_trimesh_t from, p2s_trimesh_t to, const double *dist_dev, const int32_t *face_from_dev,
+                      const int32_t *face_to_dev, int64_t n, const double *taus_host, int n_taus, double *out_host,
+                      int64_t *nc_pairs_host, void *stream);
+/* counts_host [3] = |A|, |B|, |A and B| of two occupancy arrays of n bytes (a byte that is not 0 is occupied).
+ * Synchronises `stream`. */
+int p2s_occupancy_counts(const uint8_t *occ_a_dev, const uint8_t *occ_b_dev, int64_t n, int64_t *counts_host, int device,
+                         void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * "next" row: the per-shape text / debug files of save_evaluation and implicit_surface_to_mesh, written
  * by native HOST code (no device is touched; all pointers are host pointers).  Byte-identical to what the reference's
  * numpy / Python calls write.

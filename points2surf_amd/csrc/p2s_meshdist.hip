@@ -35,6 +35,8 @@
 //  5. p2s_meshray.inl: first-hit ray casting, the time-of-flight scan and the query points on the same handle
 //  6. p2s_meshrepair.inl: repair and normalisation of a raw mesh with the same edge table, components, scan and volume sums
 //  7. p2s_meshcheck.inl: the pairs of faces that intersect and the non-manifold vertices, by a fourth walk of the octree
+//  8. p2s_meshvoxel.inl: the occupancy of a closed mesh on the volume's grid, by a fifth walk (one column of voxels per
+//     lane), and the reductions of the reconstruction-quality report
 //
 // The pseudonormal sign holds for ONE closed surface that does not intersect itself.  A closed mesh of several connected
 // components may be a union of overlapping solids (the reference's 00011084 is: 170 of its 2,000 GT queries lie just outside
@@ -1090,3 +1092,5 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
 #include "p2s_meshrepair.inl"
 // ---- 7. self-intersections and non-manifold vertices of the handle's mesh
 #include "p2s_meshcheck.inl"
+// ---- 8. occupancy on the volume's grid and the reductions of the quality report
+#include "p2s_meshvoxel.inl"

@@ -25,6 +25,7 @@ WINDING_METHODS = {'tree': 0, 'exhaustive': 1}
 SIGNS = ('pseudonormal', 'winding', 'auto')
 CHECK_KEYS = ('faces_tested', 'faces_degenerate', 'candidates', 'intersecting', 'coplanar', 'touching', 'duplicate',
               'faces_flagged', 'pairs_inside_component', 'pairs_across_components', 'nonmanifold_vertices', 'pairs_stored')
+VOXEL_KEYS = ('inside', 'undecided_columns', 'undecided_voxels', 'fallback', 'tests', 'crossings')
 P2S_EINVAL = -1
 
 
@@ -161,6 +162,30 @@ class TriMesh:
             n = int(rep[11])
             out = (dict(zip(CHECK_KEYS, (int(x) for x in rep))), pairs[:n], cls[:n])
         out = out + ((ff, vf) if want_flags else ())
+        return out[0] if len(out) == 1 else out
+
+    def voxelize(self, res, method='index', max_fallback=None, want_flags=False, want_report=False):
+        """Occupancy of this CLOSED mesh on the volume's grid (p2s_mesh_voxelize): ``occ`` [res, res, res] uint8 device
+        tensor, x-major with z fastest, 1 where the voxel centre (the float32 nearest to ((i + 0.5) / res) * 2 - 1) lies
+        inside (winding number != 0).  Voxels whose column meets an edge, a vertex or an edge-on face within rounding go
+        to the exact winding sum, O(faces) each: more than ``max_fallback`` of them (default 4 * res * res) raises P2SError
+        with the code P2S_ECAPACITY.  ``want_flags``: also [res, res, res] uint8, 1 for those voxels; ``want_report``:
+        also a dict (VOXEL_KEYS).  A mesh that is not closed raises P2SError (P2S_EINVAL)."""
+        if self.handle is None:
+            raise RuntimeError('TriMesh is closed')
+        res = int(res)
+        if max_fallback is None:
+            max_fallback = 4 * res * res
+        shape = (max(res, 0),) * 3
+        occ = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        flags = torch.empty(shape, dtype=torch.uint8, device=self.device) if want_flags else None
+        rep = (ctypes.c_int64 * 8)()
+        with torch.cuda.device(self.device):
+            rc = self.lib.p2s_mesh_voxelize(self.handle, res, METHODS[method], int(max_fallback), _engine._ptr(occ),
+                                            _engine._ptr(flags), rep, _engine._stream_ptr(self.device))
+        self.voxel_report = dict(zip(VOXEL_KEYS, (int(x) for x in rep)))
+        _lib.check(rc)
+        out = (occ,) + ((flags,) if want_flags else ()) + ((self.voxel_report,) if want_report else ())
         return out[0] if len(out) == 1 else out
 
     def close(self):

@@ -101,13 +101,11 @@ def mesh_distances(file_in, file_ref, samples_per_model=10000, seed=0, device=No
     return h_nr, h_rn, max(h_nr, h_rn), s_nr + s_rn
 
 
-def mesh_comparison(new_meshes_dir_abs, ref_meshes_dir_abs, num_processes, report_name, samples_per_model=10000,
-                    dataset_file_abs=None, seed=0):
-    """reference source/base/evaluation.py:307-392: the same pairing rules and the same CSV; the distances come from the
-    device.  ``num_processes`` is accepted and ignored (one mesh pair takes milliseconds; HIP contexts do not fork)."""
-    if not os.path.isdir(new_meshes_dir_abs):
-        print('Warning: dir to check doesn\'t exist'.format(new_meshes_dir_abs))
-        return
+def _pairing(new_meshes_dir_abs, ref_meshes_dir_abs, dataset_file_abs):
+    """the pairing rules of reference source/base/evaluation.py:307-392, shared by mesh_comparison and quality_comparison:
+    rows (new file, ref file, code) in the order the reference appends them -- code 0: compare the two; -2: a
+    reconstruction outside the set to compare that has a reference (no data set file only); -1: in the set to compare,
+    never reconstructed.  No row of code 0: ValueError('Results are empty!')."""
     new_mesh_files = sorted(f for f in os.listdir(new_meshes_dir_abs) if os.path.isfile(os.path.join(new_meshes_dir_abs, f)))
     ref_mesh_files = sorted(f for f in os.listdir(ref_meshes_dir_abs) if os.path.isfile(os.path.join(ref_meshes_dir_abs, f)))
     if dataset_file_abs is None:
@@ -122,15 +120,13 @@ def mesh_comparison(new_meshes_dir_abs, ref_meshes_dir_abs, num_processes, repor
         stem = new_mesh_file.split('.')[0]
         return sorted(set(f for f in ref_mesh_files if f.split('.')[0] == stem))
 
-    results = []
+    rows = []
     for new_mesh_file in new_mesh_files:
         if new_mesh_file.split('.')[0] in to_compare:
             match = ref_for(new_mesh_file)
             if match:
-                a, b = os.path.join(new_meshes_dir_abs, new_mesh_file), os.path.join(ref_meshes_dir_abs, match[0])
-                h_nr, h_rn, h, ch = mesh_distances(a, b, samples_per_model, seed=seed)
-                results.append((a, b, str(h_nr), str(h_rn), str(h), str(ch)))
-    if len(results) == 0:
+                rows.append((os.path.join(new_meshes_dir_abs, new_mesh_file), os.path.join(ref_meshes_dir_abs, match[0]), 0))
+    if len(rows) == 0:
         raise ValueError('Results are empty!')
     for new_mesh_file in new_mesh_files:          # no reference but reconstruction
         stem = new_mesh_file.split('.')[0]
@@ -138,21 +134,36 @@ def mesh_comparison(new_meshes_dir_abs, ref_meshes_dir_abs, num_processes, repor
             if dataset_file_abs is None:
                 match = ref_for(new_mesh_file)
                 if match:
-                    results.append((os.path.join(new_meshes_dir_abs, new_mesh_file),
-                                    os.path.join(ref_meshes_dir_abs, match[0]), str(-2), str(-2), str(-2), str(-2)))
+                    rows.append((os.path.join(new_meshes_dir_abs, new_mesh_file),
+                                 os.path.join(ref_meshes_dir_abs, match[0]), -2))
         else:
             to_compare.remove(stem)
     for missing in sorted(to_compare):            # no reconstruction but reference
-        results.append((os.path.join(new_meshes_dir_abs, missing), os.path.join(ref_meshes_dir_abs, missing),
-                        str(-1), str(-1), str(-1), str(-1)))
-    results = sorted(results, key=lambda x: x[0])
+        rows.append((os.path.join(new_meshes_dir_abs, missing), os.path.join(ref_meshes_dir_abs, missing), -1))
+    return rows
+
+
+def _write_csv(report_name, header, results):
     if os.path.dirname(report_name):
         os.makedirs(os.path.dirname(report_name), exist_ok=True)
-    csv_lines = ['in mesh,ref mesh,Hausdorff dist new-ref,Hausdorff dist ref-new,Hausdorff dist,'
-                 'Chamfer dist(-1: no input; -2: no reference)']
-    csv_lines += [','.join(item) for item in results]
     with open(report_name, 'w') as text_file:
-        text_file.write('\n'.join(csv_lines))
+        text_file.write('\n'.join([header] + [','.join(item) for item in results]))
+
+
+def mesh_comparison(new_meshes_dir_abs, ref_meshes_dir_abs, num_processes, report_name, samples_per_model=10000,
+                    dataset_file_abs=None, seed=0):
+    """reference source/base/evaluation.py:307-392: the same pairing rules and the same CSV; the distances come from the
+    device.  ``num_processes`` is accepted and ignored (one mesh pair takes milliseconds; HIP contexts do not fork)."""
+    if not os.path.isdir(new_meshes_dir_abs):
+        print('Warning: dir to check doesn\'t exist'.format(new_meshes_dir_abs))
+        return
+    results = []
+    for a, b, code in _pairing(new_meshes_dir_abs, ref_meshes_dir_abs, dataset_file_abs):
+        values = mesh_distances(a, b, samples_per_model, seed=seed) if code == 0 else (code,) * 4
+        results.append((a, b) + tuple(str(x) for x in values))
+    results = sorted(results, key=lambda x: x[0])
+    _write_csv(report_name, 'in mesh,ref mesh,Hausdorff dist new-ref,Hausdorff dist ref-new,Hausdorff dist,'
+               'Chamfer dist(-1: no input; -2: no reference)', results)
     return results
 
 
@@ -200,3 +211,164 @@ def sdf_error(rec_dir, ref_meshes_dir, report_name, device=None, sign='pseudonor
     with open(report_name, 'w') as text_file:
         text_file.write('\n'.join(csv_lines))
     return results
+
+
+# ---- reconstruction quality: accuracy / completeness, F-score, normal consistency, volumetric IoU
+QUALITY_NOTES = ('', 'new mesh not closed', 'ref mesh not closed', 'empty union', 'too many undecided voxels')
+
+
+def _read_mesh(path, dev):
+    """(verts, faces) device tensors of a mesh file, or None: missing, empty or malformed (the -1 convention of
+    mesh_distances; out-of-range indices never reach the device)"""
+    try:
+        v, f = _ply.read_ply(path)
+    except Exception:
+        return None
+    f = np.asarray(f)
+    if v.shape[0] == 0 or f.shape[0] == 0 or f.ndim != 2 or f.shape[1] != 3 or f.min() < 0 or f.max() >= v.shape[0] or \
+            not np.isfinite(v).all():
+        return None
+    return (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev),
+            torch.from_numpy(np.ascontiguousarray(f, dtype=np.int32)).to(dev))
+
+
+def surface_stats(mesh_from, mesh_to, dist, face_from, face_to, taus):
+    """p2s_surface_stats: dict(sum, sum_sq, max, sum_nc, nc_pairs, counts [len(taus)]) of n samples of ``mesh_from``
+    (``face_from``: their own faces) with the unsigned distances ``dist`` and the nearest faces ``face_to`` on ``mesh_to``"""
+    n, t = int(dist.shape[0]), len(taus)
+    d = dist.to(mesh_from.device, torch.float64).contiguous()
+    ff = face_from.to(mesh_from.device, torch.int32).contiguous()
+    ft = face_to.to(mesh_from.device, torch.int32).contiguous()
+    out, pairs = (ctypes.c_double * (4 + t))(), ctypes.c_int64(0)
+    with torch.cuda.device(mesh_from.device):
+        _lib.check(mesh_from.lib.p2s_surface_stats(mesh_from.handle, mesh_to.handle, _engine._ptr(d), _engine._ptr(ff), _engine._ptr(ft),
+                                                   n, (ctypes.c_double * max(t, 1))(*[float(x) for x in taus]), t, out,
+                                                   ctypes.byref(pairs), _engine._stream_ptr(mesh_from.device)))
+    return dict(sum=out[0], sum_sq=out[1], max=out[2], sum_nc=out[3], nc_pairs=int(pairs.value),
+                counts=[int(out[4 + k]) for k in range(t)])
+
+
+def occupancy_counts(occ_a, occ_b):
+    """p2s_occupancy_counts: (|A|, |B|, |A and B|) of two uint8 occupancy tensors of one shape"""
+    if occ_a.shape != occ_b.shape or occ_a.dtype != torch.uint8 or occ_b.dtype != torch.uint8:
+        raise ValueError('two uint8 tensors of one shape')
+    a, b = occ_a.contiguous(), occ_b.to(occ_a.device).contiguous()
+    c = (ctypes.c_int64 * 3)()
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.load().p2s_occupancy_counts(_engine._ptr(a), _engine._ptr(b), int(a.numel()), c, a.device.index,
+                                                    _engine._stream_ptr(a.device)))
+    return int(c[0]), int(c[1]), int(c[2])
+
+
+def quality_keys(taus):
+    """the keys of mesh_quality's dict, in the order of the CSV columns"""
+    per_tau = [k + '@%g' % t for t in taus for k in ('precision', 'recall', 'fscore')]
+    return ['accuracy_mean', 'accuracy_rms', 'accuracy_max', 'completeness_mean', 'completeness_rms', 'completeness_max',
+            'chamfer_l1', 'hausdorff'] + per_tau + ['normal_consistency', 'iou', 'note', 'samples', 'iou_res']
+
+
+def mesh_quality(file_in, file_ref, samples_per_model=100000, taus=(0.005, 0.01), iou_res=128, seed=0, device=None):
+    """How good the reconstructed mesh ``file_in`` is against ``file_ref``, as later papers report it.  From each mesh
+    ``samples_per_model`` area-weighted samples with their faces (one seeded Rng, ``file_in`` first), and the EXACT
+    distance of each set to the other mesh's surface (p2s_mesh_distance, unsigned):
+    accuracy_* = mean / RMS / max of new -> ref, completeness_* = of ref -> new, chamfer_l1 = the mean of the two means,
+    hausdorff = the larger max; per threshold tau precision = the share of new samples with d <= tau, recall = of ref
+    samples, fscore = 2 P R / (P + R) (0 when P + R = 0); normal_consistency = the mean of the two mean |n . n| between a
+    sample's own face and the nearest face of the other mesh (stored unit normals; pairs with a degenerate face left
+    out); iou = |A and B| / |A or B| of the two voxelisations at ``iou_res`` (TriMesh.voxelize), or -1 with ``note`` saying
+    why: a mesh is not closed, the union is empty, or a voxelisation has more undecided voxels than its default
+    max_fallback.  The defaults are definitions (0.01 = 1 % of the unit cube's side).  A missing, empty or malformed mesh:
+    every number -1."""
+    from . import gt_sdf as _gt
+    dev = _dev(device)
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    taus = tuple(float(t) for t in taus)
+    keys = quality_keys(taus)
+    out = dict((k, -1.0) for k in keys)
+    out.update(note='', samples=int(samples_per_model), iou_res=int(iou_res))
+    rng = _engine.Rng(seed, device=dev)
+    loaded = [_read_mesh(path, dev) for path in (file_in, file_ref)]
+    if loaded[0] is None or loaded[1] is None:
+        out['note'] = 'no input'
+        return out
+    meshes = [_gt.TriMesh(v, f, device=dev) for v, f in loaded]
+    try:
+        samples = [sample_surface(v, f, samples_per_model, rng, want_faces=True) for v, f in loaded]
+        stats = []
+        for src, dst in ((0, 1), (1, 0)):                      # new -> ref (accuracy), ref -> new (completeness)
+            d, face_to = meshes[dst].distance(samples[src][0], signed=False, want_face=True)
+            stats.append(surface_stats(meshes[src], meshes[dst], d, samples[src][2], face_to, taus))
+        n = float(samples_per_model)
+        for name, st in zip(('accuracy', 'completeness'), stats):
+            out[name + '_mean'], out[name + '_rms'], out[name + '_max'] = st['sum'] / n, float(np.sqrt(st['sum_sq'] / n)), st['max']
+        out['chamfer_l1'] = (out['accuracy_mean'] + out['completeness_mean']) / 2.0
+        out['hausdorff'] = max(out['accuracy_max'], out['completeness_max'])
+        for k, t in enumerate(taus):
+            p, r = stats[0]['counts'][k] / n, stats[1]['counts'][k] / n
+            out['precision@%g' % t], out['recall@%g' % t] = p, r
+            out['fscore@%g' % t] = 2.0 * p * r / (p + r) if p + r > 0.0 else 0.0
+        nc = [st['sum_nc'] / st['nc_pairs'] if st['nc_pairs'] > 0 else -1.0 for st in stats]
+        out['normal_consistency'] = (nc[0] + nc[1]) / 2.0 if min(nc) >= 0.0 else -1.0
+        closed = [m.closed for m in meshes]
+        if not closed[0] or not closed[1]:
+            out['note'] = QUALITY_NOTES[1 if not closed[0] else 2]
+        else:
+            try:
+                na, nb, nab = occupancy_counts(meshes[0].voxelize(iou_res), meshes[1].voxelize(iou_res))
+                if na + nb - nab == 0:
+                    out['note'] = QUALITY_NOTES[3]
+                else:
+                    out['iou'] = nab / float(na + nb - nab)
+            except _lib.P2SError as e:
+                if e.code != _lib.P2S_ECAPACITY:
+                    raise
+                out['note'] = QUALITY_NOTES[4]
+    finally:
+        for m in meshes:
+            m.close()
+    return out
+
+
+def quality_comparison(new_meshes_dir_abs, ref_meshes_dir_abs, report_name, dataset_file_abs=None, **kw):
+    """mesh_quality for every pair that mesh_comparison would compare (the same pairing rules, -1 for a mesh of the set that
+    was never reconstructed, -2 for a reconstruction outside it): one CSV row per pair under a header naming every column,
+    each row with the samples and the IoU resolution used.  ``kw``: samples_per_model, taus, iou_res, seed, device.
+    Returns the rows."""
+    if not os.path.isdir(new_meshes_dir_abs):
+        print('Warning: dir to check doesn\'t exist'.format(new_meshes_dir_abs))
+        return
+    keys = quality_keys(tuple(float(t) for t in kw.get('taus', (0.005, 0.01))))
+    results = []
+    for a, b, code in _pairing(new_meshes_dir_abs, ref_meshes_dir_abs, dataset_file_abs):
+        if code == 0:
+            q = mesh_quality(a, b, **kw)
+        else:
+            q = dict((k, code) for k in keys)
+            q.update(note='no input' if code == -1 else 'no reference', samples=int(kw.get('samples_per_model', 100000)),
+                     iou_res=int(kw.get('iou_res', 128)))
+        results.append((a, b) + tuple(q[k] if k == 'note' else repr(q[k]) for k in keys))
+    results = sorted(results, key=lambda x: x[0])
+    _write_csv(report_name, ','.join(['in mesh', 'ref mesh'] + keys) + '(-1: no input or not defined; -2: no reference)', results)
+    return results
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(description='reconstruction quality of the meshes in --new against those in --ref: one CSV')
+    ap.add_argument('--new', required=True, help='directory of the reconstructed meshes')
+    ap.add_argument('--ref', required=True, help='directory of the reference meshes')
+    ap.add_argument('--report', required=True, help='the CSV to write')
+    ap.add_argument('--samples', type=int, default=100000, help='surface samples per mesh')
+    ap.add_argument('--tau', type=float, action='append', help='F-score threshold (repeatable; default 0.005 and 0.01)')
+    ap.add_argument('--iou_res', type=int, default=128, help='voxels per axis of the IoU grid')
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--dataset', default=None, help='file with the names of the shapes to compare')
+    opt = ap.parse_args(argv)
+    for row in quality_comparison(opt.new, opt.ref, opt.report, dataset_file_abs=opt.dataset, samples_per_model=opt.samples,
+                                  taus=tuple(opt.tau) if opt.tau else (0.005, 0.01), iou_res=opt.iou_res, seed=opt.seed) or ():
+        print(','.join(row))
+
+
+if __name__ == '__main__':
+    main()
