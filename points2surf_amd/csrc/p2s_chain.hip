@@ -242,29 +242,49 @@ __device__ __forceinline__ unsigned scr_half2(float a, float b) {
 // column c of the packed conv3 fragments ([N/32][16][2][32][4]: k = 8 g + 4 kk + t), summed as the dense kernel's MFMA chain
 // sums it -- g ascending, t = 0..3, k = 8g+t then 8g+4+t into one accumulator; a row of the 16-row tail (SPLIT): the kk = 0
 // and the kk = 1 chain apart, then their sum (tail_colmax) -- and pooled into E[channel] by an order-preserving integer max.
-// The form is a template parameter, chosen per batch: a per-lane choice cost 16 selects beside the 8 fmaf of every k-group
+// The form is a template parameter, chosen per batch: a per-lane choice cost 16 selects beside the 8 fmaf of every k-group.
+// The w3 loads are issued ahead of their use, SCR_CDEPTH k-groups at a time (2 x 4 registers per k-group): a pass requests the
+// 2 SCR_CDEPTH fragments of its k-groups back to back and only then starts its 8 SCR_CDEPTH fmaf, so a batch waits for
+// 16 / SCR_CDEPTH L1/L2 round trips and not for one per k-group.  The depth is what the register file leaves: during a
+// confirm the A fragments (64 registers) and the weight ring (32) are live, and beside the kernel's per-tile state 8 k-groups
+// (64 registers) spilled 15 VGPRs, 6 k-groups one, 4 none (profiles/r10/kernel_resources.txt).  The passes are a loop:
+// unrolled into one block of 16 k-groups the kernel spilled at every depth.  The loads go through the buffer descriptor of
+// the dense conv3 (32-bit offsets, no 64-bit address per fragment).  The order of the 128 products and additions is the one above
+constexpr int SCR_CDEPTH = 4;
+static_assert(16 % SCR_CDEPTH == 0, "whole passes");
 template <bool SPLIT>
-__device__ __forceinline__ void scr_confirm(unsigned entry, const float *hB, const float *__restrict__ w3, int wave, float *E) {
+__device__ __forceinline__ void scr_confirm(unsigned entry, const float *hB, __amdgpu_buffer_rsrc_t w3rsrc, int wave, unsigned *E) {
     const int row = (int)(entry >> 16), cw = (int)(entry & 0xffffu);
     const int c = 256 * wave + cw;
     const float *hrow = hB + row * SB;
-    const float *wcol = w3 + ((long long)(c >> 5) * (16 * 64) + (c & 31)) * 4;
+    const int wcol = ((c >> 5) * (16 * 64) + (c & 31)) * 16;       // bytes; k-group g, half kk: + (2 g + kk) * 512
     float s0 = 0.0f, s1 = 0.0f;
-#pragma unroll 4
-    for (int g = 0; g < 16; ++g) {
-        const f32x4 ha = lds4(hrow + 8 * g), hb = lds4(hrow + 8 * g + 4);
-        const f32x4 wa = ldg4(wcol + g * 256), wb = ldg4(wcol + g * 256 + 128);
+#pragma unroll 1
+    for (int g0 = 0; g0 < 16; g0 += SCR_CDEPTH) {
+        f32x4 wa[SCR_CDEPTH], wb[SCR_CDEPTH];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            s0 = fmaf(ha[t], wa[t], s0);
-            if constexpr (SPLIT) s1 = fmaf(hb[t], wb[t], s1);
-            else s0 = fmaf(hb[t], wb[t], s0);
+        for (int j = 0; j < SCR_CDEPTH; ++j) {
+            wa[j] = bufld4(w3rsrc, wcol + j * 1024, g0 * 1024);
+            wb[j] = bufld4(w3rsrc, wcol + j * 1024 + 512, g0 * 1024);
+        }
+        // the requests above stay ahead of the first fmaf, whatever the scheduler would like to do with their registers
+        __builtin_amdgcn_sched_barrier(0);
+        const float *hh = hrow + 8 * g0;
+#pragma unroll
+        for (int j = 0; j < SCR_CDEPTH; ++j) {
+            const f32x4 ha = lds4(hh + 8 * j), hb = lds4(hh + 8 * j + 4);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                s0 = fmaf(ha[t], wa[j][t], s0);
+                if constexpr (SPLIT) s1 = fmaf(hb[t], wb[j][t], s1);
+                else s0 = fmaf(hb[t], wb[j][t], s0);
+            }
         }
     }
     const float s = SPLIT ? s0 + s1 : s0;
     const int bits = (int)__float_as_uint(s);
     if (bits >= 0) atomicMax(reinterpret_cast<int *>(E + cw), bits);
-    else atomicMin(reinterpret_cast<unsigned *>(E + cw), (unsigned)bits);
+    else atomicMin(E + cw, (unsigned)bits);
 }
 
 // SCREEN (max pool, full chain only): conv3 through p2s_chain_screen.inl, two workgroups per CU (58 KB of LDS); an item the
@@ -283,8 +303,9 @@ __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArg
     float *bufA = smem;
     float *bufB = smem + MT * SA;
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
+    // (not const: the screened instantiation renews them per tile, below)
+    int tid = threadIdx.x;
+    int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     int item = blockIdx.x;
@@ -322,7 +343,7 @@ __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArg
     bool bad = false;
 
     // buffer descriptors of the layer weights (wave-uniform): SGPR base + scalar offset + 16 * lane
-    const int lane16 = lane * 16;
+    int lane16 = lane * 16;
     const __amdgpu_buffer_rsrc_t rs0b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(br.w0b), 0, 4096 * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(w1), 0, 4096 * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(br.w2), 0, 8192 * 4, 0x00020000);
@@ -353,7 +374,9 @@ __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArg
     const int ntiles = (P + MT - 1) / MT;
     float nx0, nx1, nx2;
     // screened conv3: the state of p2s_chain_screen.inl
-    float *scr_E = smem + SCR_OFF_E + 256 * wave, *scr_red = smem + SCR_OFF_RED;
+    // the exact pool: float bits, held as the unsigned the confirm's integer atomics work on -- every access has that type
+    unsigned *scr_E = reinterpret_cast<unsigned *>(smem + SCR_OFF_E) + 256 * wave;
+    float *scr_red = smem + SCR_OFF_RED;
     unsigned *scr_q = reinterpret_cast<unsigned *>(smem + SCR_OFF_Q) + SCR_QCAP * wave;
     const float *__restrict__ scr_mu = args.w3mu[bsel];
     const __amdgpu_buffer_rsrc_t rs3h = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(args.w3h[bsel]), 0,
@@ -366,11 +389,20 @@ __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArg
     bool dense_pass = !SCREEN;
     if constexpr (SCREEN) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) scr_E[64 * i + lane] = -INFINITY;
+        for (int i = 0; i < 4; ++i) scr_E[64 * i + lane] = __float_as_uint(-INFINITY);
     }
     for (;;) {
     load_point(0, nx0, nx1, nx2);
     for (int tile = 0; tile < ntiles; ++tile) {
+      // screened kernel: the thread's index is made opaque at the top of every tile, so that the per-lane addresses of the tile's
+      // layers are built in the tile and are not kept in registers across the screen and its confirm (hoisted out of the
+      // item's loops they were what spilled: profiles/r10/kernel_resources.txt; tests/test_chain_kernel_resources.py holds the
+      // budget).  The values are the same; the other instantiations have no code here
+      if constexpr (SCREEN) {
+          asm volatile("" : "+v"(tid));
+          lane = tid & 63;
+          lane16 = lane * 16;
+      }
       f32x4 bA0, bA1, aA0, aA1, bB0, bB1, aB0, aB1;   // conv3 operand register sets
       if (ablate != 1) {
         float x0 = nx0, x1 = nx1, x2 = nx2;
@@ -490,8 +522,10 @@ __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArg
                 continue;
             }
             __builtin_amdgcn_wave_barrier();
-            rm0 = scr_E[(lane & 31)];       rm1 = scr_E[32 + (lane & 31)];  rm2 = scr_E[64 + (lane & 31)];  rm3 = scr_E[96 + (lane & 31)];
-            rm4 = scr_E[128 + (lane & 31)]; rm5 = scr_E[160 + (lane & 31)]; rm6 = scr_E[192 + (lane & 31)]; rm7 = scr_E[224 + (lane & 31)];
+            rm0 = __uint_as_float(scr_E[(lane & 31)]);       rm1 = __uint_as_float(scr_E[32 + (lane & 31)]);
+            rm2 = __uint_as_float(scr_E[64 + (lane & 31)]);  rm3 = __uint_as_float(scr_E[96 + (lane & 31)]);
+            rm4 = __uint_as_float(scr_E[128 + (lane & 31)]); rm5 = __uint_as_float(scr_E[160 + (lane & 31)]);
+            rm6 = __uint_as_float(scr_E[192 + (lane & 31)]); rm7 = __uint_as_float(scr_E[224 + (lane & 31)]);
         }
     }
     break;

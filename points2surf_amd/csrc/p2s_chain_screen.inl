@@ -6,8 +6,9 @@
 //   screen   t[p][c] = sum_k fp16(h_pk) fp16(w_ck) on v_mfma_f32_32x32x16_f16, fp32 accumulate, one accumulator set;
 //   margin   mu_c = 2 (k_screen + k_fp32) (|w_c| + 2^-10) (H + 2^-10),  H >= |h_p| for every row of every tile of the item so
 //            far, this one included (a running maximum: the margin only grows from tile to tile);
-//   select   (p, c) is a candidate iff t[p][c] >= R_c - mu_c, R_c = the running maximum of t[.][c] over the tiles so far,
-//            this one included -- every record-breaker is a candidate;
+//   select   (p, c) is a candidate iff t[p][c] >= max(R_c - mu_c, E_c - mu_c / 2), R_c = the running maximum of t[.][c] over
+//            the tiles so far, this one included -- every record-breaker passes the first term -- and E_c = the exact pool
+//            of the EARLIER tiles (below; -inf in an item's first tile, where the rule is the first term alone);
 //   confirm  each candidate at once, while its fp32 row h[p] is still in LDS: one chain of 128 fmaf in the k order of the
 //            32x32x2 MFMA chain of p2s_chain_conv3.inl (k-groups ascending, t = 0..3, 8g+t then 8g+4+t; rows of the 16-row
 //            tail: the two half chains, then one add), one lane per candidate;  E_c = max of the confirmed values.
@@ -22,6 +23,42 @@
 // (d_p + g_p) + (d_q + g_q) <= mu_c and
 //     fl(s_p) <= s*_p + g_p <= t_p + d_p + g_p < t_q - mu_c + d_p + g_p <= t_q - d_q - g_q <= s*_q - g_q <= fl(s_q):
 // p cannot hold the maximum over all P fp32 values and E_c is that maximum: the value p2s_chain_kernel<false> pools.
+//
+// The pool bound (r10).  R is a screen value with an error of its own, which is why the R rule needs both halves of mu_c.  E_c,
+// read from scr_E when a column tile is selected, has none: it is the maximum of fl(s_q) over the rows q confirmed in the
+// EARLIER tiles of the item (the candidates of this column tile are queued after the read, and the last column tile of every
+// tile empties the queue; scr_E of a wave is written by that wave's own confirms only, in program order).  Every value that
+// can sit in E_c is a value the dense kernel pools for that channel:
+//   plain chains     a row of a full tile, or a row < 32 of a tail tile: the 32x32x2 chain of that row, bit for bit;
+//   tail rows        a row >= 32 of the 16-row tail that is a point of the item: the two half chains and their sum, which is
+//                    what tail_colmax pools for it;
+//   row 32 of a short tail (at most 32 points left): the two-chain sum over the operands of the item's last point -- the dense
+//                    kernel pools exactly that value for its replicas in rows 32 .. 47, beside the plain chain of the point's
+//                    own row -- so it stands for values the dense kernel pools, and for no other.
+// Padding rows are never queued (vmask), so E_c <= M_c, the maximum the dense kernel pools, at every moment.  A row p with
+//     t_p + (d_p + g_p) < E_c     has     fl(s_p) <= s*_p + g_p <= t_p + d_p + g_p < E_c <= M_c
+// in either of its forms (g_p covers the extra add of the two-chain form, and row 32 has the t of the point it replicates):
+// it does not hold the maximum, and dismissing it leaves max(confirmed) = M_c, because a holder of M_c itself has
+// t >= M_c - (d + g) >= E_c - (d + g) and passes.  With d_p + g_p <= kappa (|w_c| + 2^-10) (|h_p| + 2^-10) <= kappa (|w_c| +
+// 2^-10) (H + 2^-10) = mu_c / 2 (H bounds |h_p|: p is of the current tile; the row that set E_c needs no bound), the second
+// term of the select is E_c - mu_c / 2.  The argument never uses R: the two terms dismiss independently, and a row has to pass
+// both.  Once a record holder q has been confirmed, E_c >= fl(s_q) >= t_q - mu_c / 2, so the new term is the stronger one for
+// every later tile whose record is still t_q.
+//   rounding   mu_c / 2 is exact (a power of two; mu_c >= 2^-29 is far from the subnormals); fl(E - mu/2) errs by at most
+//              2^-24 (|E| + mu/2) <= 2^-24 (1 + 2^-9) |w_c| H + 2^-24 mu/2 (|E| = |fl(s_q)| <= (1 + 2^-16) |w_c| |h_q| and H, a
+//              running maximum, bounds |h_q| too).  The slack is the same as for R - mu: mu_c and Heff are each rounded up
+//              by (1 + 2^-10), which makes mu/2 larger than kappa (|w_c| + 2^-10)(H + 2^-10) by 2^-9 of itself, >= 2^-19 |w_c| H
+//              -- 32 times the rounding above; the roundings of the two norms (2^-20 on |w_c|, about 2^-21 on H: 36 fmaf
+//              and a square root) and of the product mu_c * Heff (2^-24) take less than a tenth of it.  Checked, not copied:
+//              the bound on |E| is by the row's own norm, the one on |R| was by the screen value.
+//   -inf, NaN  E_c = -inf (an item's first tile: nothing is confirmed before its first select) gives -inf for the second
+//              term and fmaxf leaves R - mu.  A NaN in E_c (a chain over a non-finite activation) is dropped by fmaxf in the
+//              same way and dismisses nothing; the item is poisoned by `bad` as before.  E_c = +inf can only come from an
+//              fp32 chain that overflowed: every later row is then dismissed unless its t is +inf too, and the pool is
+//              +inf either way.
+// The candidate set stays a function of the item alone (E_c depends on the earlier tiles' candidates only, never on timing).
+// Not built: the per-row form |h_p| + H of the margin (CPU model: 6.27 instead of 7.33 candidates per channel; 32 more live
+// values per lane in the select).
 //
 // The two k.  S = sum_k |w_k| |h_k| <= |w_c| |h_p| (Cauchy-Schwarz), N1 = sum_k |x_k| <= sqrt(128) |x|.
 //   operands    each is rounded ONCE to fp16: |fp16(x) - x| <= 2^-11 |x| in the normal range, <= 2^-25 below 2^-14 (half a
@@ -138,10 +175,14 @@
                 }
                 if (scr_abl == 3) {       // MFMAs and their loads only: one value of each accumulator, pooled, keeps them live
                     sr0 = fmaxf(sr0, acc[0][0] + acc[1][0]);
-                    if (ct == 7) scr_E[lane] = sr0;
+                    if (ct == 7) scr_E[lane] = __float_as_uint(sr0);
                     continue;
                 }
                 const float mu = mu_c * Heff;
+                // the exact pool of this lane's channel over the EARLIER tiles: candidates of this column tile are queued
+                // below and confirmed after that, and every batch of an earlier tile has run (ct == 7 empties the queue);
+                // scr_E of a wave is written by that wave's own confirms only, the wave barriers order them before this read
+                const float Ec = __uint_as_float(scr_E[32 * ct + (lane & 31)]);
                 mu_c = scr_mu[256 * wave + 32 * (ct < 7 ? ct + 1 : 7) + (lane & 31)];   // the next column tile's, behind the ring's requests
                 float m = fmaxf(acc[0][0], acc[0][1]);
 #pragma unroll
@@ -156,7 +197,8 @@
                 else if (ct == 5) R = sr5 = fmaxf(sr5, m);
                 else if (ct == 6) R = sr6 = fmaxf(sr6, m);
                 else R = sr7 = fmaxf(sr7, m);
-                const float thr = R - mu;
+                // -inf (nothing confirmed yet) leaves the R rule; fmaxf drops a NaN operand, so a NaN in E dismisses nothing
+                const float thr = fmaxf(R - mu, Ec - 0.5f * mu);
                 unsigned mask = 0;
 #pragma unroll
                 for (int j = 0; j < 32; ++j) mask |= (acc[j >> 4][j & 15] >= thr ? 1u : 0u) << j;
@@ -189,9 +231,9 @@
                     const int n = qn < 64 ? qn : 64;
                     const unsigned entry = scr_q[qn - n + (lane < n ? lane : 0)];
                     const bool split = tail && (entry >> 16) >= 32u;
-                    if (lane < n && !split) scr_confirm<false>(entry, bufB, w3, wave, scr_E);
+                    if (lane < n && !split) scr_confirm<false>(entry, bufB, w3rsrc, wave, scr_E);
                     if (tail && __ballot(lane < n && split) != 0ull) {
-                        if (lane < n && split) scr_confirm<true>(entry, bufB, w3, wave, scr_E);
+                        if (lane < n && split) scr_confirm<true>(entry, bufB, w3rsrc, wave, scr_E);
                     }
                     qn -= n;
                     nconf += n;

@@ -1,7 +1,8 @@
 #!/bin/bash
 # timing of the chain kernel of the library that is loaded (development aid).  The timing-only ablations are build variants,
 # -DP2S_DEV_ABLATE=<variant> (1 = conv3 only, 2 = all but conv3; of the screened conv3: 3 = its MFMAs and their loads only,
-# 4 = everything but the confirm, 5 = everything but the fp16 conversion of the tile; the results of such a build are wrong).  Build one beside the
+# 4 = everything but the confirm -- its select reads the pool bound E, which then stays -inf --, 5 = everything but the fp16
+# conversion of the tile; the results of such a build are wrong).  Build one beside the
 # shipped library and point P2S_LIB_PATH at it; this script builds nothing and replaces nothing:
 #   P2S_LIB_PATH=/path/to/variant/libp2s_hip.so tools/ablate.sh [queries per launch, default 4096]
 python tools/quick_bench.py --B "${1:-4096}" --iters 3 2>/dev/null | tail -1 | python -c '
