@@ -668,6 +668,52 @@ int p2s_occupancy_counts(const uint8_t *occ_a_dev, const uint8_t *occ_b_dev, int
                          void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Screened Poisson baseline: an oriented cloud -> mesh, without the network.  The reference runs
+ * MeshLab's Screened Poisson filter here (eval_dataset.py, poisson.mlx); this is the project's OWN definition of the
+ * stage -- regular grids, trilinear elements, a cascade of levels -- and is not pinned against MeshLab.
+ *
+ * Box: centre = midpoint of the cloud's bounding box, side = scale * its largest extent (float64).  Level d = 3 .. depth
+ * has R = 2^d + 1 nodes per axis, h = side / 2^d, node (i, j, k) at lo + h (i, j, k), C order with axis 0 = x.  Per level,
+ * with W [n][R^3] the trilinear weights (cell = clamp(floor((p - lo) / h), 0, R - 2) per axis), n_occ the distinct cells
+ * that hold a point, a = n_occ h^2 / n and lambda = point_weight a / h:
+ *     A = s(x)m(x)m + m(x)s(x)m + m(x)m(x)s + lambda W^T W,    b = (g(x)m(x)m) v_x + (m(x)g(x)m) v_y + (m(x)m(x)g) v_z,
+ *     v = (a / h^3) W^T (-N),   m / s / g the 1-D mass / stiffness / derivative matrices with natural ends,
+ * solved by CG preconditioned with diag(A) from the trilinear prolongation of the level below (zero at level 3) until
+ * |r| <= cg_tol |b| -- tested after every iteration, so a level makes at least one -- or max_iters (reported, no error).
+ * iso = the mean of (W chi)_p (float64); volume = chi - iso, float32 [R]^3, every node of the six border faces then set
+ * to -|value|; surface = p2s_marching_cubes of it at 0 (inside: value > 0, fix_inversion), vertices mapped to lo + h v.
+ * Vectors are float32, every sum over points and every reduction float64, no floating-point atomics: equal inputs give
+ * equal bytes.
+ *
+ * info_host [P2S_POISSON_INFO] (may be NULL): [0..2] lo, [3] h of the finest level made, [4] iso, [5] levels made, then
+ * per level d at [8 + 5 (d - 3)]: lambda, n_occ, iterations, final |r| / |b|, milliseconds.
+ * P2S_EINVAL before anything is written: n < 1 (or > 2^24), a non-finite point or normal, all normals zero, a cloud of
+ * zero extent, point_weight <= 0, scale < 1, cg_tol <= 0, max_iters < 1, depth outside 3..9.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct p2s_poisson_params_t {
+    int32_t depth;            /* 3..9 */
+    int32_t max_iters;        /* CG iterations per level, >= 1 */
+    double point_weight;      /* alpha > 0 (MeshLab's pointWeight; 4) */
+    double scale;             /* >= 1 (1.1) */
+    double cg_tol;            /* > 0 (1e-3) */
+} p2s_poisson_params_t;
+#define P2S_POISSON_INFO 48
+/* points_dev / normals_dev [n][3] float32 (normals outward, any length).  vol_out_dev (may be NULL) [R]^3 float32 of the
+ * finest level.  verts_out_dev [cap_verts][3], faces_out_dev [cap_faces][3]: *n_verts / *n_faces receive the full counts;
+ * too small a capacity is P2S_ECAPACITY as in p2s_marching_cubes (capacities 0 size the buffers; the volume and the info
+ * are written either way).  Scratch comes from the device's block cache.  Synchronises `stream`. */
+int p2s_poisson_reconstruct(const float *points_dev, const float *normals_dev, int64_t n, const p2s_poisson_params_t *params,
+                            float *vol_out_dev, float *verts_out_dev, int64_t cap_verts, int32_t *faces_out_dev,
+                            int64_t cap_faces, int64_t *n_verts, int64_t *n_faces, double *info_host, int device, void *stream);
+/* The system of ONE level (3 <= level <= params->depth; the box is that of the cloud, whatever the level), the yardstick
+ * of the solver: b_out_dev, diag_out_dev [R^3] (each may be NULL) and, when ax_out_dev is given, A . x_in_dev through the
+ * kernels the CG runs.  info_host as above with lo, h and the slot of `level` (lambda, n_occ) filled.  Synchronises
+ * `stream`. */
+int p2s_poisson_system(const float *points_dev, const float *normals_dev, int64_t n, const p2s_poisson_params_t *params,
+                       int level, const float *x_in_dev, float *b_out_dev, float *ax_out_dev, float *diag_out_dev,
+                       double *info_host, int device, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * "next" row: the per-shape text / debug files of save_evaluation and implicit_surface_to_mesh, written
  * by native HOST code (no device is touched; all pointers are host pointers).  Byte-identical to what the reference's
  * numpy / Python calls write.

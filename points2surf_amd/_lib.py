@@ -104,6 +104,10 @@ PROTOTYPES = {
     'p2s_surface_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, ctypes.POINTER(ctypes.c_double), c_int,
                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int64), c_void_p]),
     'p2s_occupancy_counts': (c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_int, c_void_p]),
+    'p2s_poisson_reconstruct': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                        ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_double), c_int, c_void_p]),
+    'p2s_poisson_system': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   ctypes.POINTER(ctypes.c_double), c_int, c_void_p]),
     'p2s_mesh_normalize':(c_int, [c_void_p, c_int64, c_void_p, ctypes.POINTER(ctypes.c_double), c_int, c_void_p]),
     'p2s_set_profiling': (c_int, [c_void_p, c_int]),
     'p2s_get_counters': (c_int, [c_void_p, ctypes.POINTER(Counters)]),
