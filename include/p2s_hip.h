@@ -714,6 +714,32 @@ int p2s_poisson_system(const float *points_dev, const float *normals_dev, int64_
                        double *info_host, int device, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Point normals from the cloud alone: what the Poisson baseline needs where no mesh exists (the
+ * reference's 06_poisson_rec / normals_poisson.mlx variant, and real_world).  4 <= k <= 64, k <= n, else P2S_EINVAL; so is
+ * a NULL cloud or normal array.  Scratch comes from the device's block cache; no floating-point atomics: equal inputs give
+ * equal bytes.  Both synchronise `stream`.
+ *
+ * p2s_normals_estimate: the neighbourhood of point i is its k nearest points of the cloud as p2s_knn_patch ranks them
+ * (float64 distances, ties by id, the point itself and duplicates included).  In float64: centroid c, covariance
+ * C = sum (p - c)(p - c)^T, cyclic Jacobi with a fixed number of sweeps, the eigenvector of the smallest eigenvalue
+ * (of equal ones the first axis in the order the iteration leaves them), normalised, rounded once to float32 ->
+ * normals_out_dev [n][3].  variation_out_dev [n] (may be NULL) = lambda_0 / (lambda_0 + lambda_1 + lambda_2).  C = 0: normal
+ * (0, 0, 0), variation 0.  The sign of a normal is unspecified but deterministic.
+ *
+ * p2s_normals_orient: Hoppe's propagation, made unique.  Graph: the undirected edges {i, j}, i != j, with j among the k
+ * nearest of i or the reverse.  d = (a_x b_x + a_y b_y) + a_z b_z in float64 from the float32 normals, w = 1 - |d|.  Tree:
+ * the minimum spanning forest under the total order (w, min(i, j), max(i, j)) -- for w >= 0 the order of its bit pattern.
+ * Crossing a tree edge flips iff d < 0.  Per component the seed is the point of largest z (of equal ones the smallest id);
+ * the component is negated as a whole iff the seed's oriented n_z < 0.  normals_out_dev (may be normals_in_dev) = the input
+ * with only sign bits changed (all three of a flipped normal); component_out_dev [n] (may be NULL) = the smallest point id
+ * of the point's component; info_host [8] (may be NULL) = components, undirected edges, Boruvka rounds that joined
+ * components, normals flipped, 0 ....  A non-finite normal: P2S_EINVAL, nothing written.
+ * ------------------------------------------------------------------------------------------ */
+int p2s_normals_estimate(p2s_cloud_t c, int k, float *normals_out_dev, float *variation_out_dev, void *stream);
+int p2s_normals_orient(p2s_cloud_t c, int k, const float *normals_in_dev, float *normals_out_dev, int32_t *component_out_dev,
+                       int64_t *info_host, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * "next" row: the per-shape text / debug files of save_evaluation and implicit_surface_to_mesh, written
  * by native HOST code (no device is touched; all pointers are host pointers).  Byte-identical to what the reference's
  * numpy / Python calls write.

@@ -108,6 +108,8 @@ PROTOTYPES = {
                                         ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_double), c_int, c_void_p]),
     'p2s_poisson_system': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    ctypes.POINTER(ctypes.c_double), c_int, c_void_p]),
+    'p2s_normals_estimate': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'p2s_normals_orient': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     'p2s_mesh_normalize':(c_int, [c_void_p, c_int64, c_void_p, ctypes.POINTER(ctypes.c_double), c_int, c_void_p]),
     'p2s_set_profiling': (c_int, [c_void_p, c_int]),
     'p2s_get_counters': (c_int, [c_void_p, ctypes.POINTER(Counters)]),
