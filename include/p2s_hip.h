@@ -775,6 +775,51 @@ typedef struct {
 int p2s_set_profiling(p2s_model_t m, int enabled);
 int p2s_get_counters(p2s_model_t m, p2s_counters *out);
 
+/* ------------------------------------------------------------------------------------------
+ * Training step  (replaces one iteration of the reference's train loop: model.train(); pred = model(batch);
+ *                 loss = sum(compute_loss(...)); loss.backward(); optimizer.step() -- reference
+ *                 source/points_to_surf_train.py:400-440, :537-563, source/sdf_nn.py:30-40)
+ * p2s_max and p2s_max_no_feat_stn only, fp32 throughout; every other configuration is refused at creation with
+ * P2S_EINVAL and a message that names the reason (QSTN, shared encoder / transformer, sum pooling, regression, fixed
+ * patch radius, a net size other than 1024).  No floating-point atomics: equal inputs and equal state give equal bytes.
+ *
+ * Parameters (every .weight / .bias), buffers (every .running_mean / .running_var) and gradients are flat float arrays
+ * in the order of the reference's state_dict (points2surf_amd/model_spec.py state_shapes); num_batches_tracked is one
+ * counter, equal for every batch-norm.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct p2s_trainer_s *p2s_trainer_t;
+
+/* cfg: points_per_patch / sub_sample_size fix the two point counts; use_feat_stn: 1 = p2s_max, 0 = without the 64 x 64
+ * feature transforms.  n_params / n_buffers must match the model (checked). */
+int p2s_trainer_create(const p2s_model_cfg *cfg, int use_feat_stn, const float *params_host, int64_t n_params,
+                       const float *buffers_host, int64_t n_buffers, int64_t num_batches_tracked, int device,
+                       p2s_trainer_t *out);
+int p2s_trainer_destroy(p2s_trainer_t t);
+/* sizes of the flat arrays, the number of recorded max-pools (4 with feature transforms: feat_local.stn2, feat_local,
+ * feat_global.stn2, feat_global; else 2) and the device bytes the trainer holds (any may be NULL) */
+int p2s_trainer_sizes(p2s_trainer_t t, int64_t *n_params, int64_t *n_buffers, int64_t *n_pools, int64_t *resident_bytes);
+/* Train-mode forward (batch statistics), both losses, backward.  The three network inputs follow p2s_encode_decode
+ * (patch in patch space, sub-sample and query in model space; nothing is modified); per item dist_abs_dev [B] = |d|,
+ * sign01_dev [B] = the 0 / 1 sign target, radius_dev [B] = the patch radius (the magnitude target is tanh(|d| / r)).
+ * losses_host[0] = magnitude loss, [1] = sign loss (both weights 1, the total is their sum).  Blocking: returns after
+ * the losses have reached the host.  On success the gradients are ready, the running statistics have been updated
+ * (momentum 0.1, unbiased variance) and num_batches_tracked has been incremented.  B < 2: P2S_EINVAL.  A non-finite loss
+ * or gradient: P2S_EINVAL, parameters and running statistics unchanged.  All activations stay resident until the next call. */
+int p2s_trainer_forward_backward(p2s_trainer_t t, const float *patch_ps_dev, const float *sub_ms_dev, const float *query_dev,
+                                 const float *dist_abs_dev, const float *sign01_dev, const float *radius_dev, int B,
+                                 double *losses_host, void *stream);
+/* torch.optim.SGD(lr, momentum) without dampening, weight decay or Nesterov, one launch over the flat arrays; needs the
+ * gradients of a successful p2s_trainer_forward_backward since the last step */
+int p2s_trainer_sgd_step(p2s_trainer_t t, double lr, double momentum, void *stream);
+/* what: 0 parameters, 1 buffers, 2 gradients of the last step -> host (blocking); num_batches_tracked may be NULL */
+int p2s_trainer_copy_out(p2s_trainer_t t, int what, float *host, int64_t n_floats, int64_t *num_batches_tracked);
+/* the argmax every max-pool of the last step recorded (lowest index on exact ties): [n_pools][B][1024] int32 */
+int p2s_trainer_pool_indices(p2s_trainer_t t, int32_t *host, int64_t n);
+/* family_ms (may be NULL) receives the HIP-event milliseconds of the last step per kernel family -- [0] GEMM, [1] column
+ * sums, [2] batch-norm apply / backward, [3] max-pool, [4] the small kernels; [5..7] unused -- measured only while
+ * profiling is enabled; `enabled` switches it for the following steps */
+int p2s_trainer_profile(p2s_trainer_t t, int enabled, double *family_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,17 @@ PROTOTYPES = {
     'p2s_write_txt_f32': (c_int, [ctypes.c_char_p, c_void_p, c_int64]),
     'p2s_write_query_vis_ply': (c_int, [ctypes.c_char_p, c_void_p, c_void_p, c_int64]),
     'p2s_write_coff_samples': (c_int, [ctypes.c_char_p, c_void_p, c_void_p, c_int64]),
+    'p2s_trainer_create': (c_int, [ctypes.POINTER(ModelCfg), c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int,
+                                   ctypes.POINTER(c_void_p)]),
+    'p2s_trainer_destroy': (c_int, [c_void_p]),
+    'p2s_trainer_sizes': (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
+                                  ctypes.POINTER(c_int64)]),
+    'p2s_trainer_forward_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                             ctypes.POINTER(ctypes.c_double), c_void_p]),
+    'p2s_trainer_sgd_step': (c_int, [c_void_p, ctypes.c_double, ctypes.c_double, c_void_p]),
+    'p2s_trainer_copy_out': (c_int, [c_void_p, c_int, c_void_p, c_int64, ctypes.POINTER(c_int64)]),
+    'p2s_trainer_pool_indices': (c_int, [c_void_p, c_void_p, c_int64]),
+    'p2s_trainer_profile': (c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_double)]),
 }
 
 
