@@ -820,6 +820,41 @@ int p2s_trainer_pool_indices(p2s_trainer_t t, int32_t *host, int64_t n);
  * profiling is enabled; `enabled` switches it for the following steps */
 int p2s_trainer_profile(p2s_trainer_t t, int enabled, double *family_ms);
 
+/* The two losses of given predictions pred_dev [B][2] against the targets of p2s_trainer_forward_backward, without
+ * gradients: what a validation pass reports for the logits of the inference path.  The same kernel and the same fixed
+ * summation tree as the training step.  B >= 1.  Blocking. */
+int p2s_train_losses(const float *pred_dev, const float *dist_abs_dev, const float *sign01_dev, const float *radius_dev,
+                     int B, double *losses_host, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A set of clouds behind one handle: batches whose items come from many clouds, one call each
+ * (the training loader: a batch of 501 items touches about as many shapes).
+ *
+ * The set BORROWS its clouds: it copies no points, uploads the table of their descriptors once and keeps their point
+ * counts on the host.  The clouds must live on `device` and must outlive the set.  The set notes the streams it is used
+ * on and drains them in p2s_cloudset_destroy, as a cloud handle does.
+ *
+ * cloud_of_host [Q] (HOST memory): item i belongs to clouds[cloud_of_host[i]].  Every call checks it on the host and
+ * uploads it into a buffer of the set; P2S_EINVAL with a message that names the item and the cloud for an id outside
+ * [0, n_clouds), for k (n) greater than that cloud's point count, and for k beyond the limit of p2s_knn_patch.  The
+ * shuffle-and-pad branch of clouds smaller than the sub-sample stays with the per-cloud call.  Q = 0: P2S_OK, no launch.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct p2s_cloudset_s *p2s_cloudset_t;
+int p2s_cloudset_create(const p2s_cloud_t *clouds, int n_clouds, int device, p2s_cloudset_t *out);
+int p2s_cloudset_destroy(p2s_cloudset_t s);
+int p2s_cloudset_size(p2s_cloudset_t s, int32_t *n_clouds, int32_t *min_points);      /* either may be NULL */
+/* item i receives exactly what p2s_knn_patch(clouds[cloud_of_host[i]], query i) writes: ids local to its cloud in
+ * ascending distance, the patch in patch space, the radius (any of the three outputs may be NULL) */
+int p2s_cloudset_knn_patch(p2s_cloudset_t s, const int32_t *cloud_of_host, const float *query_dev, int64_t n_queries, int k,
+                           int32_t *ids_out_dev, float *patch_ps_out_dev, float *radius_out_dev, void *stream);
+/* No new random-number definition: the ids are what the ONE stream of `r` gives when item after item, in the order
+ * given, draws n ids by numpy's masked rejection for its own cloud -- byte for byte what p2s_subsample_uniform(r,
+ * clouds[cloud_of_host[i]], 1, n, ...) for i = 0 .. Q-1 leaves in the outputs and in the generator.  An open session of
+ * `r` is closed first.  ids_out_dev [Q][n] (NULL, together with pts_out_dev = NULL: only advance the stream),
+ * pts_out_dev [Q][n][3] the points of each item's own cloud (may be NULL). */
+int p2s_cloudset_subsample_uniform(p2s_rng_t r, p2s_cloudset_t s, const int32_t *cloud_of_host, int64_t n_queries, int n,
+                                   int32_t *ids_out_dev, float *pts_out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

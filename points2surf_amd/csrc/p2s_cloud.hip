@@ -249,7 +249,7 @@ int p2s_cloud_create(const float *pts_dev, int n, int device, void *stream, p2s_
 
 // Drain the streams a handle has noted.  Only the complaint about a caller's stream that no longer exists is dropped; a
 // genuine asynchronous fault (of this or of unrelated work) is recorded and stays pending for the next launch check.
-static void drain_noted_streams(p2s_cloud_s *c, const char *who) {
+static void drain_streams(const hipStream_t *streams, int n_streams, bool many_streams, const char *who) {
     hipError_t fault = hipSuccess;
     bool stale = false;
     auto look = [&](hipError_t e) {
@@ -257,12 +257,13 @@ static void drain_noted_streams(p2s_cloud_s *c, const char *who) {
         if (e == hipErrorInvalidHandle || e == hipErrorInvalidResourceHandle || e == hipErrorContextIsDestroyed) stale = true;
         else fault = e;
     };
-    if (c->many_streams) look(hipDeviceSynchronize());
+    if (many_streams) look(hipDeviceSynchronize());
     else
-        for (int i = 0; i < c->n_streams; ++i) look(hipStreamSynchronize(c->streams[i]));
+        for (int i = 0; i < n_streams; ++i) look(hipStreamSynchronize(streams[i]));
     if (fault != hipSuccess) p2s_set_error("%s: asynchronous HIP error while draining the handle's streams: %s", who, hipGetErrorString(fault));
     else if (stale) (void)hipGetLastError();
 }
+static void drain_noted_streams(p2s_cloud_s *c, const char *who) { drain_streams(c->streams, c->n_streams, c->many_streams, who); }
 
 int p2s_cloud_destroy(p2s_cloud_t c) {
     if (!c) return P2S_OK;
@@ -734,3 +735,5 @@ int p2s_subsample_uniform(p2s_rng_t r, p2s_cloud_t c, int64_t nq, int n, int32_t
 }
 
 }  // extern "C"
+
+#include "p2s_cloud_set.inl"

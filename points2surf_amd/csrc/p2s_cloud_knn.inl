@@ -220,8 +220,86 @@ __device__ void knn_scan(const CloudDev &c, KnnList &L, const int lo[3], const i
     }
 }
 
-// SORTED: ids / patch rows in ascending distance (the API's contract).  !SORTED (the per-shape pipeline): the same k
-// points in list order, selected without sorting (knn_select).
+// One query of one wave: the k nearest points of cloud `c` to query `qi`, its radius and its patch.  SORTED: ids / patch
+// rows in ascending distance (the API's contract).  !SORTED (the per-shape pipeline): the same k points in list order,
+// selected without sorting (knn_select).  keys / lids [KNN_CAP], run_start / run_off [64]: the block's LDS.
+template <bool SORTED>
+__device__ __forceinline__ void knn_query(const CloudDev &c, long long qi, const float *__restrict__ queries, int k,
+                                          int *__restrict__ ids_out, float *__restrict__ patch_out,
+                                          float *__restrict__ radius_out, unsigned long long *keys, int *lids, int *run_start,
+                                          int *run_off, int lane) {
+    const int G = c.G;
+    const float qxf = queries[3 * qi + 0], qyf = queries[3 * qi + 1], qzf = queries[3 * qi + 2];
+    const double qx = qxf, qy = qyf, qz = qzf;
+    const int cq[3] = {cell_coord(qxf, c.lo[0], c.inv_cell, G), cell_coord(qyf, c.lo[1], c.inv_cell, G),
+                       cell_coord(qzf, c.lo[2], c.inv_cell, G)};
+    // smallest cube of cells around the query's cell that holds >= k points (O(1) per try via the SAT)
+    int lo[3], hi[3];
+    for (int rho = 0;; ++rho) {
+        bool all = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = max(cq[a] - rho, 0);
+            hi[a] = min(cq[a] + rho, G - 1);
+            all = all && lo[a] == 0 && hi[a] == G - 1;
+        }
+        if (all || box_count(c, lo, hi) >= k) break;
+    }
+    KnnList L{keys, lids, 0, INFINITY, k};
+    __syncthreads();
+    knn_scan(c, L, lo, hi, false, lo, hi, qx, qy, qz, lane, run_start, run_off);
+    // exact k-th distance among the cube's points (or a value just above it): an upper bound of the true one
+    if (SORTED) knn_prune(L, lane);
+    else knn_select(L, lane);
+    // every point within sqrt(thr2) of q lies in cells [lo2, hi2] (conservative: radius rounded up, and
+    // cell_coord is monotone)
+    const float r = (float)sqrt(L.thr2) * 1.00001f + 1e-30f;
+    int lo2[3], hi2[3];
+    const float qf[3] = {qxf, qyf, qzf};
+    bool grow = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        lo2[a] = min(lo[a], cell_coord(qf[a] - r, c.lo[a], c.inv_cell, G));
+        hi2[a] = max(hi[a], cell_coord(qf[a] + r, c.lo[a], c.inv_cell, G));
+        grow = grow || lo2[a] != lo[a] || hi2[a] != hi[a];
+    }
+    if (grow) {
+        const int before = L.len;
+        knn_scan(c, L, lo2, hi2, true, lo, hi, qx, qy, qz, lane, run_start, run_off);
+        if (L.len != before) {
+            if (SORTED) knn_prune(L, lane);
+            else knn_select(L, lane);
+        }
+    }
+    __syncthreads();
+    // ---- outputs: ids (ascending distance), r = max ||q - p||_2 (fp32, numpy op order), (p - q) / r ----
+    float smax = 0.0f;
+    for (int j = lane; j < k; j += 64) {
+        int id = lids[j];
+        if ((unsigned)id >= (unsigned)c.n) id = 0;      // a non-finite query finds no candidates: stay inside the cloud
+        if (ids_out) ids_out[qi * k + j] = id;
+        const float dx = qxf - c.pts[3 * id + 0];
+        const float dy = qyf - c.pts[3 * id + 1];
+        const float dz = qzf - c.pts[3 * id + 2];
+        const float s = (dx * dx + dy * dy) + dz * dz;      // contraction is off: three roundings + two
+        smax = fmaxf(smax, s);
+    }
+    for (int d = 32; d > 0; d >>= 1) smax = fmaxf(smax, __shfl_xor(smax, d));
+    const float rad = sqrtf(smax);   // sqrt is monotone: max_i sqrt(s_i) == sqrt(max_i s_i)
+    if (radius_out && lane == 0) radius_out[qi] = rad;
+    if (patch_out) {
+        for (int j = lane; j < k; j += 64) {
+            int id = lids[j];
+            if ((unsigned)id >= (unsigned)c.n) id = 0;
+            float *dst = patch_out + (qi * k + j) * 3;
+            dst[0] = (c.pts[3 * id + 0] - qxf) / rad;
+            dst[1] = (c.pts[3 * id + 1] - qyf) / rad;
+            dst[2] = (c.pts[3 * id + 2] - qzf) / rad;
+        }
+    }
+    __syncthreads();
+}
+
 template <bool SORTED>
 __global__ __launch_bounds__(64) void p2s_knn_kernel(CloudDev c, const float *__restrict__ queries, long long nq,
                                                      int k, int *__restrict__ ids_out,
@@ -231,76 +309,23 @@ __global__ __launch_bounds__(64) void p2s_knn_kernel(CloudDev c, const float *__
     __shared__ int lids[KNN_CAP];
     __shared__ int run_start[64], run_off[64];
     const int lane = threadIdx.x;
-    const int G = c.G;
+    for (long long qi = blockIdx.x; qi < nq; qi += gridDim.x)
+        knn_query<SORTED>(c, qi, queries, k, ids_out, patch_out, radius_out, keys, lids, run_start, run_off, lane);
+}
+
+// The same query by query over a SET of clouds (p2s_cloudset_knn_patch): item qi searches table[cloud_of[qi]].  qi is
+// uniform over the block, so the descriptor is a scalar load and stays in scalar registers.  The host has checked every
+// cloud_of[qi] against the table and k against that cloud.
+__global__ __launch_bounds__(64) void p2s_knn_set_kernel(const CloudDev *__restrict__ table, const int *__restrict__ cloud_of,
+                                                         const float *__restrict__ queries, long long nq, int k,
+                                                         int *__restrict__ ids_out, float *__restrict__ patch_out,
+                                                         float *__restrict__ radius_out) {
+    __shared__ unsigned long long keys[KNN_CAP];
+    __shared__ int lids[KNN_CAP];
+    __shared__ int run_start[64], run_off[64];
+    const int lane = threadIdx.x;
     for (long long qi = blockIdx.x; qi < nq; qi += gridDim.x) {
-        const float qxf = queries[3 * qi + 0], qyf = queries[3 * qi + 1], qzf = queries[3 * qi + 2];
-        const double qx = qxf, qy = qyf, qz = qzf;
-        const int cq[3] = {cell_coord(qxf, c.lo[0], c.inv_cell, G), cell_coord(qyf, c.lo[1], c.inv_cell, G),
-                           cell_coord(qzf, c.lo[2], c.inv_cell, G)};
-        // smallest cube of cells around the query's cell that holds >= k points (O(1) per try via the SAT)
-        int lo[3], hi[3];
-        for (int rho = 0;; ++rho) {
-            bool all = true;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = max(cq[a] - rho, 0);
-                hi[a] = min(cq[a] + rho, G - 1);
-                all = all && lo[a] == 0 && hi[a] == G - 1;
-            }
-            if (all || box_count(c, lo, hi) >= k) break;
-        }
-        KnnList L{keys, lids, 0, INFINITY, k};
-        __syncthreads();
-        knn_scan(c, L, lo, hi, false, lo, hi, qx, qy, qz, lane, run_start, run_off);
-        // exact k-th distance among the cube's points (or a value just above it): an upper bound of the true one
-        if (SORTED) knn_prune(L, lane);
-        else knn_select(L, lane);
-        // every point within sqrt(thr2) of q lies in cells [lo2, hi2] (conservative: radius rounded up, and
-        // cell_coord is monotone)
-        const float r = (float)sqrt(L.thr2) * 1.00001f + 1e-30f;
-        int lo2[3], hi2[3];
-        const float qf[3] = {qxf, qyf, qzf};
-        bool grow = false;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo2[a] = min(lo[a], cell_coord(qf[a] - r, c.lo[a], c.inv_cell, G));
-            hi2[a] = max(hi[a], cell_coord(qf[a] + r, c.lo[a], c.inv_cell, G));
-            grow = grow || lo2[a] != lo[a] || hi2[a] != hi[a];
-        }
-        if (grow) {
-            const int before = L.len;
-            knn_scan(c, L, lo2, hi2, true, lo, hi, qx, qy, qz, lane, run_start, run_off);
-            if (L.len != before) {
-                if (SORTED) knn_prune(L, lane);
-                else knn_select(L, lane);
-            }
-        }
-        __syncthreads();
-        // ---- outputs: ids (ascending distance), r = max ||q - p||_2 (fp32, numpy op order), (p - q) / r ----
-        float smax = 0.0f;
-        for (int j = lane; j < k; j += 64) {
-            int id = lids[j];
-            if ((unsigned)id >= (unsigned)c.n) id = 0;      // a non-finite query finds no candidates: stay inside the cloud
-            if (ids_out) ids_out[qi * k + j] = id;
-            const float dx = qxf - c.pts[3 * id + 0];
-            const float dy = qyf - c.pts[3 * id + 1];
-            const float dz = qzf - c.pts[3 * id + 2];
-            const float s = (dx * dx + dy * dy) + dz * dz;      // contraction is off: three roundings + two
-            smax = fmaxf(smax, s);
-        }
-        for (int d = 32; d > 0; d >>= 1) smax = fmaxf(smax, __shfl_xor(smax, d));
-        const float rad = sqrtf(smax);   // sqrt is monotone: max_i sqrt(s_i) == sqrt(max_i s_i)
-        if (radius_out && lane == 0) radius_out[qi] = rad;
-        if (patch_out) {
-            for (int j = lane; j < k; j += 64) {
-                int id = lids[j];
-                if ((unsigned)id >= (unsigned)c.n) id = 0;
-                float *dst = patch_out + (qi * k + j) * 3;
-                dst[0] = (c.pts[3 * id + 0] - qxf) / rad;
-                dst[1] = (c.pts[3 * id + 1] - qyf) / rad;
-                dst[2] = (c.pts[3 * id + 2] - qzf) / rad;
-            }
-        }
-        __syncthreads();
+        const CloudDev c = table[cloud_of[qi]];
+        knn_query<true>(c, qi, queries, k, ids_out, patch_out, radius_out, keys, lids, run_start, run_off, lane);
     }
 }

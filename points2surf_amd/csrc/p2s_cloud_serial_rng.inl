@@ -177,6 +177,149 @@ __global__ void p2s_gather_kernel(const float *__restrict__ pts, const int32_t *
     out[3 * i + 2] = pts[3 * id + 2];
 }
 
+// The same walk over SEGMENTS of one stream (p2s_cloudset_subsample_uniform): segment g draws segs[g].count values with
+// its own (rng, mask) into out[segs[g].out_begin ..], and the next segment goes on at the word behind the one that
+// completed it -- what consecutive randint calls on one RandomState do.  A segment may end inside a 624-word block: the
+// consumer wave then runs its temper / reject / compact pass again over the rest of the SAME block with the next
+// segment's mask (no twist in between; the tempered words are still in its registers).  A segment that ends at word 624
+// leaves the rest to the next block, i.e. behind a twist.  The twister wave, the one barrier per block and the
+// parity-indexed s_done flags are those of p2s_mt_randint_kernel: the inner loop over segments is the consumer's own
+// business between two barriers, and both waves leave the outer loop on the same flag.  n_segs >= 1, every count >= 1.
+__global__ __launch_bounds__(128) void p2s_mt_randint_seg_kernel(uint32_t *__restrict__ state,
+                                                                 const P2sRandSeg *__restrict__ segs, int n_segs,
+                                                                 int32_t *__restrict__ out) {
+    __shared__ uint32_t st[2][624];
+    __shared__ uint32_t stage[640];
+    __shared__ int s_done[2];
+    __shared__ int s_pos;
+    __builtin_amdgcn_s_setprio(3);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (int i = tid; i < 624; i += 128) st[0][i] = state[i];
+    int pos = (int)state[624];
+    if (tid == 0) {
+        s_done[0] = 0;
+        s_done[1] = 0;
+        s_pos = 624;
+    }
+    __syncthreads();
+    int cur = 0, start = pos;
+    if (pos >= 624) {                       // numpy: "needs twist before the first draw"
+        if (wave == 0) mt_twist_wave(st[0], st[1], lane);
+        __syncthreads();
+        cur = 1;
+        start = 0;
+    }
+    // consumer wave only: the segment in work, the one behind it (fetched a segment ahead), values produced of the first
+    int si = 0;
+    P2sRandSeg seg = segs[0], nxt = segs[n_segs > 1 ? 1 : 0];
+    long long produced = 0;
+    for (int iter = 0;; ++iter) {
+        if (wave == 0) {
+            mt_twist_wave(st[cur], st[cur ^ 1], lane);
+        } else {
+            // lane l owns words 10l .. 10l+9, as in p2s_mt_randint_kernel; tempered once per block
+            const uint32_t *src = st[cur];
+            uint32_t t[10];
+#pragma unroll
+            for (int j = 0; j < 10; ++j) {
+                const int idx = 10 * lane + j;
+                t[j] = src[idx < 624 ? idx : 623];
+            }
+#pragma unroll
+            for (int j = 0; j < 10; ++j) t[j] = mt_temper(t[j]);
+            int from = start;                                   // first word of the block the segment in work may use
+            for (;;) {
+                const uint32_t mask = seg.mask, rng = seg.rng;
+                uint32_t w[10];
+                unsigned okmask = 0;
+#pragma unroll
+                for (int j = 0; j < 10; ++j) {
+                    const int idx = 10 * lane + j;
+                    w[j] = t[j] & mask;
+                    const unsigned ok = (idx < 624) & (idx >= from) & (w[j] <= rng);
+                    okmask |= ok << j;
+                }
+                const int c = __popc(okmask);
+                int excl = 0, total = 0;
+#pragma unroll
+                for (int bit = 0; bit < 4; ++bit) {
+                    const unsigned long long m = __ballot((c >> bit) & 1);
+                    excl += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) << bit;
+                    total += __popcll(m) << bit;
+                }
+                const long long need = seg.count - produced;       // > 0
+                int r = excl;
+#pragma unroll
+                for (int j = 0; j < 10; ++j) {
+                    if (okmask & (1u << j)) stage[r] = w[j];
+                    r += (okmask >> j) & 1u;
+                }
+                const int lim = (total < need) ? total : (int)need;
+                {
+                    uint32_t sv[10];
+#pragma unroll
+                    for (int it = 0; it < 10; ++it) sv[it] = stage[64 * it + lane];      // batched LDS reads
+                    const long long o = seg.out_begin + produced;
+#pragma unroll
+                    for (int it = 0; it < 10; ++it)
+                        if (out && 64 * it + lane < lim) out[o + 64 * it + lane] = (int32_t)sv[it];
+                }
+                if (total < need) {                                 // the block is used up; the segment goes on in the next
+                    produced += total;
+                    break;
+                }
+                // the stream resumes behind the word holding the need-th accepted value: one lane owns it
+                const bool mine = excl < need && need <= excl + c;
+                int pos_end = 0;
+                if (mine) {
+                    int left = (int)need - excl;
+#pragma unroll
+                    for (int j = 0; j < 10; ++j) {
+                        if ((okmask >> j) & 1u) {
+                            if (--left == 0) pos_end = 10 * lane + j + 1;
+                        }
+                    }
+                }
+                const int owner = __ffsll((unsigned long long)__ballot(mine)) - 1;
+                pos_end = __shfl(pos_end, owner);
+                if (++si == n_segs) {
+                    if (lane == 0) {
+                        s_pos = pos_end;
+                        s_done[iter & 1] = 1;
+                    }
+                    break;
+                }
+                seg = nxt;
+                if (si + 1 < n_segs) nxt = segs[si + 1];
+                produced = 0;
+                from = pos_end;
+                if (from >= 624) break;                             // the next segment starts behind a twist
+            }
+        }
+        // LDS-only synchronisation (see p2s_mt_randint_kernel)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (s_done[iter & 1]) break;        // parity-indexed: the consumer may already be one block ahead
+        cur ^= 1;
+        start = 0;
+    }
+    for (int i = tid; i < 624; i += 128) state[i] = st[cur][i];
+    if (tid == 0) state[624] = (uint32_t)s_pos;
+}
+
+// points of the ids an item drew from ITS cloud: item i / n of the set call -> table[cloud_of[item]].pts
+__global__ void p2s_gather_set_kernel(const CloudDev *__restrict__ table, const int *__restrict__ cloud_of,
+                                      const int32_t *__restrict__ ids, long long total, int n, float *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const CloudDev &c = table[cloud_of[i / n]];
+    const int id = min(max(ids[i], 0), c.n - 1);
+    out[3 * i + 0] = c.pts[3 * id + 0];
+    out[3 * i + 1] = c.pts[3 * id + 1];
+    out[3 * i + 2] = c.pts[3 * id + 2];
+}
+
 // ---------------------------------------------------------------------------------------------
 // a6, clouds with FEWER points than the sub-sample size (reference source/base/utils.py:221-226):
 //     pts_shuffled = pts_ms[:, :3]; rng.shuffle(pts_shuffled); pad with zeros

@@ -235,6 +235,32 @@ struct p2s_cloud_s {
     int kd_leaves = 0;
 };
 
+// one run of items of a cloud-set sub-sample that draw from clouds of the same size, as the serial generator walks it
+// (p2s_mt_randint_seg_kernel): `count` values in [0, rng] by masked rejection, written from out[out_begin] on
+struct P2sRandSeg {
+    uint32_t rng, mask;
+    long long out_begin, count;
+};
+
+// a set of clouds behind one handle (p2s_cloudset_*): borrows the clouds, owns the descriptor table and the per-call buffers
+struct p2s_cloudset_s {
+    int device = 0;
+    std::vector<int> n_points;     // per cloud (host)
+    int min_points = 0;
+    CloudDev *table = nullptr;     // device [n_clouds]
+    // per-call inputs: filled in pinned host memory, copied on the call's stream; `copied` is recorded behind the copies
+    // and waited for before the pinned side is written again
+    int32_t *cloud_of_pin = nullptr, *cloud_of_dev = nullptr;
+    P2sRandSeg *seg_pin = nullptr, *seg_dev = nullptr;
+    int64_t cap_items = 0;
+    hipEvent_t copied = nullptr;
+    hipStream_t last = nullptr;    // stream of the last call: a call on another one waits for it (the buffers are shared)
+    bool used = false;
+    hipStream_t streams[4] = {};   // as p2s_cloud_s: drained by destroy
+    int n_streams = 0;
+    bool many_streams = false;
+};
+
 struct p2s_rng_s {
     int device = 0;
     uint32_t *state = nullptr;     // [624] mt + [1] pos

@@ -358,7 +358,8 @@ __global__ __launch_bounds__(256) void p2s_train_fc4_bwd_kernel(const float *__r
     }
 }
 
-// both losses and dL/dpred, one block; the items are summed in a fixed tree.  out[0] = magnitude loss, out[1] = sign loss
+// both losses and dL/dpred (NULL: the losses alone), one block; the items are summed in a fixed tree.  out[0] = magnitude
+// loss, out[1] = sign loss
 //   magnitude: mse(tanh|p0|, tanh(|d| / r));  sign: mean BCE-with-logits of p1 against the 0/1 target
 __global__ __launch_bounds__(256) void p2s_train_loss_kernel(const float *__restrict__ pred, const float *__restrict__ dist,
                                                              const float *__restrict__ sign01, const float *__restrict__ radius,
@@ -374,11 +375,11 @@ __global__ __launch_bounds__(256) void p2s_train_loss_kernel(const float *__rest
         const double d = a - t;
         lm += d * d;
         const double sg = (p0 > 0.0) ? 1.0 : ((p0 < 0.0) ? -1.0 : (p0 == 0.0 ? 0.0 : p0));
-        dpred[2 * i] = (float)(2.0 * d * (1.0 - a * a) * sg * invB);
+        if (dpred) dpred[2 * i] = (float)(2.0 * d * (1.0 - a * a) * sg * invB);
         const double y = sign01[i];
         ls += fmax(p1, 0.0) - p1 * y + log1p(exp(-fabs(p1)));
         const double sig = 1.0 / (1.0 + exp(-p1));
-        dpred[2 * i + 1] = (float)((sig - y) * invB);
+        if (dpred) dpred[2 * i + 1] = (float)((sig - y) * invB);
     }
     sh[0][tid] = lm;
     sh[1][tid] = ls;
@@ -1042,6 +1043,41 @@ int p2s_trainer_pool_indices(p2s_trainer_t t, int32_t *host, int64_t n) {
         if (t->stn) P2S_HIP_CHECK(hipMemcpy(host + one * k++, t->fa[e].tidx, one * 4, hipMemcpyDeviceToHost));
         P2S_HIP_CHECK(hipMemcpy(host + one * k++, t->fa[e].idx, one * 4, hipMemcpyDeviceToHost));
     }
+    return P2S_OK;
+}
+
+int p2s_train_losses(const float *pred_dev, const float *dist_abs_dev, const float *sign01_dev, const float *radius_dev,
+                     int B, double *losses_host, void *stream) {
+    if (!pred_dev || !dist_abs_dev || !sign01_dev || !radius_dev || !losses_host) {
+        p2s_set_error("p2s_train_losses: null argument");
+        return P2S_EINVAL;
+    }
+    if (B < 1) {
+        p2s_set_error("p2s_train_losses: B = %d; at least one item is needed", B);
+        return P2S_EINVAL;
+    }
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, pred_dev) != hipSuccess) {
+        (void)hipGetLastError();
+        p2s_set_error("p2s_train_losses: pred_dev is not device memory");
+        return P2S_EINVAL;
+    }
+    P2S_HIP_CHECK(hipSetDevice(at.device));
+    hipStream_t s = (hipStream_t)stream;
+    P2sScratchLock scratch(at.device);
+    double *out = (double *)scratch.get(2 * sizeof(double));
+    if (!out) {
+        p2s_set_error("p2s_train_losses: device allocation failed");
+        return P2S_ENOMEM;
+    }
+    hipLaunchKernelGGL(p2s_train_loss_kernel, dim3(1), dim3(256), 0, s, pred_dev, dist_abs_dev, sign01_dev, radius_dev,
+                       (float *)nullptr, out, B);
+    P2S_LAUNCH_CHECK("p2s_train_loss_kernel");
+    double lh[2];
+    P2S_HIP_CHECK(hipMemcpyAsync(lh, out, sizeof(lh), hipMemcpyDeviceToHost, s));
+    P2S_HIP_CHECK(hipStreamSynchronize(s));
+    losses_host[0] = lh[0];
+    losses_host[1] = lh[1];
     return P2S_OK;
 }
 

@@ -360,6 +360,83 @@ class Rng:
         return ids, pts
 
 
+def _cloud_of(cloud_of):
+    """any integer sequence or array -> contiguous int32 on the host"""
+    a = np.asarray(cloud_of)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise TypeError('cloud_of must hold integers (got %s)' % a.dtype)
+    return np.ascontiguousarray(a.reshape(-1), dtype=np.int32)
+
+
+class CloudSet:
+    """Several ``Cloud`` objects behind one handle (p2s_cloudset_*): batches whose items come from many clouds, one call
+    each.  The set borrows the clouds (it keeps references to them, so they outlive it) and copies no points.  ``cloud_of``
+    names the cloud of every item: any integer sequence or array."""
+
+    def __init__(self, clouds):
+        self.clouds = list(clouds)
+        if not self.clouds:
+            raise ValueError('CloudSet: no clouds')
+        self.lib = self.clouds[0].lib
+        self.device = self.clouds[0].device
+        if any(c.device != self.device for c in self.clouds):
+            raise ValueError('CloudSet: the clouds live on different devices')
+        arr = (ctypes.c_void_p * len(self.clouds))(*[c.handle.value for c in self.clouds])
+        self.handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.p2s_cloudset_create(ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p)), len(self.clouds),
+                                                    self.device.index, ctypes.byref(self.handle)))
+        n, m = ctypes.c_int32(0), ctypes.c_int32(0)
+        _lib.check(self.lib.p2s_cloudset_size(self.handle, ctypes.byref(n), ctypes.byref(m)))
+        self.n_clouds, self.min_points = int(n.value), int(m.value)
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            self.lib.p2s_cloudset_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def knn_patch(self, cloud_of, queries, k, want_ids=True, want_patch=True):
+        """a4+a5, item i in cloud ``cloud_of[i]`` -> (ids [Q,k] int32 local to that cloud, patch_ps [Q,k,3], radius [Q]):
+        per item what ``Cloud.knn_patch`` gives"""
+        co = _cloud_of(cloud_of)
+        q = _f32c(queries, self.device).reshape(-1, 3)
+        Q = int(q.shape[0])
+        if co.shape[0] != Q:
+            raise ValueError('%d cloud ids for %d queries' % (co.shape[0], Q))
+        ids = torch.empty((Q, k), dtype=torch.int32, device=self.device) if want_ids else None
+        patch = torch.empty((Q, k, 3), dtype=torch.float32, device=self.device) if want_patch else None
+        rad = torch.empty((Q,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.p2s_cloudset_knn_patch(self.handle, co.ctypes.data_as(ctypes.c_void_p), _ptr(q), Q, int(k),
+                                                       _ptr(ids), _ptr(patch), _ptr(rad), _stream_ptr(self.device)))
+        return ids, patch, rad
+
+    def subsample_uniform(self, rng, cloud_of, n, want_pts=True):
+        """a6 (uniform), item after item from the one stream of ``rng``, each from its own cloud: ids [Q,n] int32
+        (+ gathered points [Q,n,3]) -- what ``rng.subsample_uniform(clouds[cloud_of[i]], 1, n)`` gives for i = 0 .. Q-1"""
+        co = _cloud_of(cloud_of)
+        Q = int(co.shape[0])
+        ids = torch.empty((Q, n), dtype=torch.int32, device=self.device)
+        pts = torch.empty((Q, n, 3), dtype=torch.float32, device=self.device) if want_pts else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.p2s_cloudset_subsample_uniform(rng.handle, self.handle, co.ctypes.data_as(ctypes.c_void_p), Q,
+                                                               int(n), _ptr(ids), _ptr(pts), _stream_ptr(self.device)))
+        return ids, pts
+
+    def skip(self, rng, cloud_of, n):
+        """advance ``rng`` past the draws of these items without producing them"""
+        co = _cloud_of(cloud_of)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.p2s_cloudset_subsample_uniform(rng.handle, self.handle, co.ctypes.data_as(ctypes.c_void_p),
+                                                               int(co.shape[0]), int(n), None, None, _stream_ptr(self.device)))
+
+
 class WorkerStreams:
     """The reference's sub-sample streams under ``--workers W --batchSize B`` (points2surf_amd/streams.py): every
     DataLoader worker holds its own copies of both ``RandomState(seed)`` generators, and the query at dataset position g

@@ -5,7 +5,9 @@ all fp32.  Tensors are containers; nothing here computes on the CPU or in torch,
 ``python -m points2surf_amd.train --indir DATASET --name NAME --outdir DIR`` replaces the loop of the reference's
 source/points_to_surf_train.py for the hyper-parameters listed in ``parse_arguments``: it writes NAME_model.pth and
 NAME_params.pth, the two files the evaluation loads.  The ORDER of shapes and patches is this project's own seeded
-definition (``epoch_order``), not the reference's DataLoader worker streams.
+definition (``epoch_order``), not the reference's DataLoader worker streams.  ``--loader set`` assembles every batch
+over all its clouds in one call each (engine.CloudSet; the same bytes as the default per-shape loop, far fewer launches);
+``--testset FILE`` adds a validation pass per epoch (``validate``).
 """
 import argparse
 import ctypes
@@ -214,6 +216,10 @@ def parse_arguments(args=None):
     p.add_argument('--seed', type=int, default=3627473)
     p.add_argument('--save_interval', type=int, default=10, help='write the checkpoint every this many epochs (and at the end)')
     p.add_argument('--gpu_idx', type=int, default=0)
+    p.add_argument('--loader', choices=('per_shape', 'set'), default='per_shape',
+                   help="how a batch is assembled: 'per_shape' one upload, kNN and sub-sample call per shape of the batch; 'set' one "
+                        "of each per batch over all clouds (the same bytes, far fewer launches: use it)")
+    p.add_argument('--testset', default='', help="shape list inside --indir to validate on after every epoch ('' = no validation)")
     return p.parse_args(args=args)
 
 
@@ -242,22 +248,148 @@ def params_namespace(opt):
         net_size=1024, use_point_stn=0, use_feat_stn=int(bool(opt.use_feat_stn)), sym_op='max', single_transformer=0,
         shared_transformer=0, batchSize=int(opt.batchSize), nepoch=int(opt.nepoch), lr=float(opt.lr), momentum=float(opt.momentum),
         scheduler_steps=list(opt.scheduler_steps), patches_per_shape=int(opt.patches_per_shape), seed=int(opt.seed),
-        name=opt.name, indir=opt.indir, trainset=opt.trainset)
+        name=opt.name, indir=opt.indir, trainset=opt.trainset, testset=getattr(opt, 'testset', ''),
+        loader=getattr(opt, 'loader', 'per_shape'))
+
+
+class TrainData:
+    """One data set on the device: the shape names, their clouds, the set over them (made on first use), and all query
+    points and distances concatenated, shape s at rows ``offsets[s] .. offsets[s + 1]``.  ``points_per_patch`` and
+    ``sub_sample_size`` are the two point counts of every batch it assembles."""
+
+    def __init__(self, names, clouds, queries, dists, points_per_patch, sub_sample_size):
+        self.names, self.clouds = list(names), list(clouds)
+        self.P, self.S = int(points_per_patch), int(sub_sample_size)
+        for n, q, d in zip(self.names, queries, dists):
+            if q.shape[0] != d.shape[0]:
+                raise ValueError('%s: %d query points, %d distances' % (n, q.shape[0], d.shape[0]))
+        self.n_queries = [int(q.shape[0]) for q in queries]
+        self.offsets = np.concatenate([[0], np.cumsum(self.n_queries)]).astype(np.int64)
+        self.queries = np.ascontiguousarray(np.concatenate(queries, axis=0), dtype=np.float32).reshape(-1, 3)
+        self.dists = np.ascontiguousarray(np.concatenate(dists, axis=0), dtype=np.float32).reshape(-1)
+        self.device = self.clouds[0].device
+        self._set = None
+
+    @classmethod
+    def load(cls, indir, list_file, points_per_patch, sub_sample_size, dev):
+        """04_pts, 05_query_pts and 05_query_dist of the shapes ``list_file`` (inside ``indir``) names"""
+        from . import engine
+        with open(os.path.join(indir, list_file)) as f:
+            names = [l.strip() for l in f if l.strip()]
+        clouds, queries, dists = [], [], []
+        for n in names:
+            pts = np.load(os.path.join(indir, '04_pts', n + '.xyz.npy'))
+            clouds.append(engine.Cloud(np.ascontiguousarray(pts[:, :3], dtype=np.float32), dev))
+            queries.append(np.ascontiguousarray(np.load(os.path.join(indir, '05_query_pts', n + '.ply.npy')), dtype=np.float32))
+            dists.append(np.ascontiguousarray(np.load(os.path.join(indir, '05_query_dist', n + '.ply.npy')), dtype=np.float32).reshape(-1))
+        return cls(names, clouds, queries, dists, points_per_patch, sub_sample_size)
+
+    def cloudset(self):
+        """the set over the clouds; a cloud with fewer points than the patch or the sub-sample is named and refused (the
+        shuffle-and-pad branch of such clouds exists per cloud only: loader 'per_shape')"""
+        if self._set is None:
+            from . import engine
+            for n, c in zip(self.names, self.clouds):
+                if c.n < max(self.P, self.S):
+                    raise ValueError("loader 'set': shape %s has %d points, fewer than points_per_patch %d or sub_sample_size %d"
+                                     % (n, c.n, self.P, self.S))
+            self._set = engine.CloudSet(self.clouds)
+        return self._set
+
+    def close(self):
+        if self._set is not None:
+            self._set.close()
+            self._set = None
+
+    def assemble(self, items, loader, rng):
+        """the batch of ``items`` (int64 [n, 2]: shape, query index) -> the six tensors of ``Trainer.forward_backward``.  The
+        items are sorted by shape (stably) first; ``rng`` draws the sub-samples in that order.  Both loaders give the same
+        bytes and leave ``rng`` in the same state: 'per_shape' makes one upload, one kNN call and one sub-sample call per
+        shape of the batch, 'set' one of each per batch (engine.CloudSet)."""
+        from . import engine
+        dev = self.device
+        items = np.asarray(items, dtype=np.int64).reshape(-1, 2)
+        items = items[np.argsort(items[:, 0], kind='stable')]
+        if loader == 'set':
+            cs = self.cloudset()
+            rows = self.offsets[items[:, 0]] + items[:, 1]
+            q_all, d = self.queries[rows], self.dists[rows]
+            q_dev = engine.upload(q_all, dev)
+            _, patch, rad = cs.knn_patch(items[:, 0], q_dev, self.P, want_ids=False)
+            sub = cs.subsample_uniform(rng, items[:, 0], self.S)[1]
+            return (patch, sub, q_dev, engine.upload(np.abs(d), dev), engine.upload((d >= 0).astype(np.float32), dev), rad)
+        if loader != 'per_shape':
+            raise ValueError("loader must be 'per_shape' or 'set' (got %r)" % (loader,))
+        queries = [self.queries[self.offsets[s]:self.offsets[s + 1]] for s in range(len(self.clouds))]
+        dists = [self.dists[self.offsets[s]:self.offsets[s + 1]] for s in range(len(self.clouds))]
+        clouds = self.clouds
+        patch, sub, rad = [], [], []
+        for s in np.unique(items[:, 0]):
+            q = engine.upload(queries[s][items[items[:, 0] == s, 1]], dev)
+            _, p, r = clouds[s].knn_patch(q, self.P, want_ids=False)
+            patch.append(p)
+            rad.append(r)
+            sub.append(rng.subsample_uniform(clouds[s], q.shape[0], self.S)[1])
+        d = np.concatenate([dists[s][items[items[:, 0] == s, 1]] for s in np.unique(items[:, 0])])
+        q_all = np.concatenate([queries[s][items[items[:, 0] == s, 1]] for s in np.unique(items[:, 0])])
+        return (torch.cat(patch), torch.cat(sub), engine.upload(q_all, dev), engine.upload(np.abs(d), dev),
+                engine.upload((d >= 0).astype(np.float32), dev), torch.cat(rad))
+
+
+def losses(pred, dist_abs, sign01, radius):
+    """(magnitude loss, sign loss) of given predictions [B, 2] on the device (p2s_train_losses): the training step's loss
+    kernel without gradients"""
+    dev = pred.device
+    pred = _f32c(pred, dev)
+    B = int(pred.shape[0])
+    if pred.shape != (B, 2):
+        raise ValueError('predictions must be [B, 2] (got %s)' % (tuple(pred.shape),))
+    per_item = [_f32c(t.reshape(-1), dev) for t in (dist_abs, sign01, radius)]
+    if any(t.shape != (B,) for t in per_item):
+        raise ValueError('dist_abs, sign01 and radius must hold one value per item')
+    out = (ctypes.c_double * 2)()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().p2s_train_losses(_ptr(pred), _ptr(per_item[0]), _ptr(per_item[1]), _ptr(per_item[2]), B, out,
+                                                _stream_ptr(dev)))
+    return float(out[0]), float(out[1])
+
+
+def validate(state_dict, opt, data, dev):
+    """One validation pass over ``data`` -> (magnitude loss, sign loss), each the mean over the batches.  This project's
+    own definition: the order is ``epoch_order(..., epoch=-1)`` and the sub-samples come from a fresh ``Rng(seed + 1)``,
+    so every pass sees identical batches of ``--batchSize`` items (the last may be short) and the training stream is not
+    touched.  The forward is the inference path (engine.Model, running statistics, fp32) with the configuration the
+    evaluation derives from the saved parameters."""
+    from . import engine
+    from .dropin.source import points_to_surf_eval as ev
+    train_opt = params_namespace(opt)
+    cfg = dict(ev._engine_cfg(train_opt, ev.get_output_dimensions(train_opt)), encoder_bf16=0)
+    sd = model_spec.strip_module_prefix(state_dict)
+    model = engine.Model({k: (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in sd.items()}, cfg, dev)
+    rng = engine.Rng(int(opt.seed) + 1, dev)
+    order = epoch_order(data.n_queries, opt.patches_per_shape, opt.seed, -1)
+    total, batches = np.zeros(2), 0
+    try:
+        for b0 in range(0, order.shape[0], opt.batchSize):
+            patch, sub, q, dist_abs, sign01, rad = data.assemble(order[b0:b0 + opt.batchSize], opt.loader, rng)
+            logits, _ = model.forward(patch, sub, q)
+            total += losses(logits, dist_abs, sign01, rad)
+            batches += 1
+    finally:
+        rng.close()
+        model.close()
+    return total[0] / max(batches, 1), total[1] / max(batches, 1)
 
 
 def train(opt):
     from . import engine
     dev = engine.select_device(opt.gpu_idx)
-    with open(os.path.join(opt.indir, opt.trainset)) as f:
-        names = [l.strip() for l in f if l.strip()]
-    clouds, queries, dists = [], [], []
-    for n in names:
-        pts = np.load(os.path.join(opt.indir, '04_pts', n + '.xyz.npy'))
-        clouds.append(engine.Cloud(np.ascontiguousarray(pts[:, :3], dtype=np.float32), dev))
-        queries.append(np.ascontiguousarray(np.load(os.path.join(opt.indir, '05_query_pts', n + '.ply.npy')), dtype=np.float32))
-        dists.append(np.ascontiguousarray(np.load(os.path.join(opt.indir, '05_query_dist', n + '.ply.npy')), dtype=np.float32).reshape(-1))
-        if queries[-1].shape[0] != dists[-1].shape[0]:
-            raise ValueError('%s: %d query points, %d distances' % (n, queries[-1].shape[0], dists[-1].shape[0]))
+    data = TrainData.load(opt.indir, opt.trainset, opt.points_per_patch, opt.sub_sample_size, dev)
+    test = TrainData.load(opt.indir, opt.testset, opt.points_per_patch, opt.sub_sample_size, dev) if opt.testset else None
+    if opt.loader == 'set':
+        for d in (data, test):
+            if d is not None:
+                d.cloudset()                                     # a cloud too small for the set fails here, by name
     cfg = dict(use_feat_stn=bool(opt.use_feat_stn), points_per_patch=opt.points_per_patch, sub_sample_size=opt.sub_sample_size,
                net_size=1024, output_dim=2)
     trainer = Trainer(cfg, seed=opt.seed, device=dev)
@@ -267,32 +399,26 @@ def train(opt):
     torch.save(params_namespace(opt), os.path.join(opt.outdir, opt.name + '_params.pth'))
     for epoch in range(opt.nepoch):
         lr = learning_rate(opt.lr, opt.scheduler_steps, epoch)
-        order = epoch_order([q.shape[0] for q in queries], opt.patches_per_shape, opt.seed, epoch)
+        order = epoch_order(data.n_queries, opt.patches_per_shape, opt.seed, epoch)
         total, batches = np.zeros(2), 0
         for b0 in range(0, order.shape[0], opt.batchSize):
             items = order[b0:b0 + opt.batchSize]
             if items.shape[0] < 2:
                 continue                                     # batch-norm needs a batch
-            items = items[np.argsort(items[:, 0], kind='stable')]
-            patch, sub, rad = [], [], []
-            for s in np.unique(items[:, 0]):
-                q = engine.upload(queries[s][items[items[:, 0] == s, 1]], dev)
-                _, p, r = clouds[s].knn_patch(q, opt.points_per_patch, want_ids=False)
-                patch.append(p)
-                rad.append(r)
-                sub.append(rng.subsample_uniform(clouds[s], q.shape[0], opt.sub_sample_size)[1])
-            d = np.concatenate([dists[s][items[items[:, 0] == s, 1]] for s in np.unique(items[:, 0])])
-            q_all = np.concatenate([queries[s][items[items[:, 0] == s, 1]] for s in np.unique(items[:, 0])])
-            loss = trainer.forward_backward(torch.cat(patch), torch.cat(sub), engine.upload(q_all, dev),
-                                            engine.upload(np.abs(d), dev), engine.upload((d >= 0).astype(np.float32), dev),
-                                            torch.cat(rad))
+            loss = trainer.forward_backward(*data.assemble(items, opt.loader, rng))
             trainer.step(lr, opt.momentum)
             total += loss
             batches += 1
-        print('epoch %d: lr %g, %d batches, magnitude loss %.6f, sign loss %.6f' %
-              (epoch, lr, batches, total[0] / max(batches, 1), total[1] / max(batches, 1)), flush=True)
+        line = 'epoch %d: lr %g, %d batches, magnitude loss %.6f, sign loss %.6f' % (
+            epoch, lr, batches, total[0] / max(batches, 1), total[1] / max(batches, 1))
+        if test is not None:
+            line += '; validation: magnitude loss %.6f, sign loss %.6f' % validate(trainer.state_dict(), opt, test, dev)
+        print(line, flush=True)
         if (epoch + 1) % max(opt.save_interval, 1) == 0 or epoch == opt.nepoch - 1:
             torch.save(trainer.state_dict(), model_file)
+    for d in (data, test):
+        if d is not None:
+            d.close()
     return model_file
 
 
