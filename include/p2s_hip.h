@@ -855,6 +855,65 @@ int p2s_cloudset_knn_patch(p2s_cloudset_t s, const int32_t *cloud_of_host, const
 int p2s_cloudset_subsample_uniform(p2s_rng_t r, p2s_cloudset_t s, const int32_t *cloud_of_host, int64_t n_queries, int n,
                                    int32_t *ids_out_dev, float *pts_out_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Raw scans -> 04_pts (the project's own definitions, stricter than the reference's
+ * make_pc_dataset.py): drop non-finite points, crop gross strays, remove statistical outliers, thin to a budget,
+ * normalise to the unit cube.  All selection logic is float64 with contraction off; tests/prepare_model.py performs the
+ * same operations in numpy.  No floating-point atomics: equal inputs give equal bytes.
+ *
+ * Common to the five selecting calls: pts_dev [n][3]; pts_out_dev [n][3] and ids_out_dev [n] int32 (neither may be NULL,
+ * pts_out_dev must not alias pts_dev) receive the *n_out_host survivors in input order and their ids into the input (one
+ * stable compaction: flags, prefix scan, scatter).  0 <= n <= 2^27; n = 0 is legal and gives 0.  Except for
+ * p2s_prepare_finite a non-finite coordinate is P2S_EINVAL.  A stage that is switched off copies its input bit for bit.
+ * Arguments are checked before the device is touched; the message names the offending argument.  Scratch comes from the
+ * device's block cache and returns to it before the call ends.  All synchronise `stream`.
+ *
+ * p2s_prepare_finite: keeps the points whose three coordinates are finite.
+ *
+ * p2s_prepare_crop: per axis, on the float32 coordinates (-0 counts as +0), the order statistics of rank
+ * floor(q (n - 1)) and ceil((1 - q) (n - 1)) (float64 arithmetic for the ranks), found exactly by bisection on the
+ * ordered bit pattern: 32 counting passes.  The box [lo, hi] is widened to [lo - m (hi - lo), hi + m (hi - lo)] in float64;
+ * a point is kept iff all three coordinates lie inside (bounds included).  0 <= quantile < 0.5 (0: off), margin >= 0.
+ * bounds_host [12] (may be NULL): lo[3], hi[3] (the order statistics), box lo[3], box hi[3].
+ *
+ * p2s_prepare_outliers: d_i = (sum of the distances from point i to its k + 1 nearest points of the cloud, itself
+ * included, in the order of p2s_knn_patch) / k, each distance sqrt((dx dx + dy dy) + dz dz) in float64 from the float32
+ * coordinates.  mean and std (population form, two passes) are double sums in a fixed tree.  Point i is kept iff
+ * d_i <= mean + std_ratio * std.  1 <= k <= 64, clamped to n - 1; std_ratio >= 0 (0: off); n < 2 keeps everything.
+ * d_out_dev [n] float64 (may be NULL) receives d_i (not written when the stage is off or n < 2).  info_host [4] (may be
+ * NULL): mean, std, threshold, the k used.
+ *
+ * p2s_prepare_voxel_thin: at most one point per cell of an R^3 grid over the cube [lo, lo + ext]^3, lo the bounding box's
+ * minimum, ext its largest extent.  Cell index per axis min(R - 1, floor((p - lo) (R / ext))) (ext = 0: cell 0); the cell
+ * keeps the point of smallest (dx dx + dy dy) + dz dz to its centre lo + (i + 0.5) (ext / R), of equal ones the lowest
+ * id (integer atomic minima over the distance's bit pattern, then over the id).  resolution in 1 .. 1024: R given.
+ * resolution = 0: n <= max_points copies the input; otherwise R is what this search leaves in lo:
+ *   lo = 1, hi = 1024; while lo < hi: mid = (lo + hi + 1) / 2; if occupied(mid) <= max_points: lo = mid; else hi = mid - 1
+ * (max_points >= 1).  info_host [2] (may be NULL): R (0 where the input was copied), occupied cells.
+ *
+ * p2s_prepare_normalize: c = (lo + hi) * 0.5, s = 1 / max extent of the bounding box, p' = (p - c) * s in float64,
+ * rounded once to float32.  pts_out_dev may be pts_dev here.  info_host [4] (may be NULL): c, s.  n < 1: P2S_EINVAL; an
+ * extent of 0 on every axis: P2S_EFLAT ("extent 0"), nothing written.  A zero extent on one or two axes is legal.
+ *
+ * p2s_prepare_gather: out row i = src row ids_dev[i], rows of `width` 32-bit words (points: 3, ids: 1); an id outside
+ * [0, n_src) is P2S_EINVAL, nothing usable written.  The random thinning gathers a host-drawn permutation with it.
+ *
+ * p2s_prepare_restore: out [n][3] float64 = double(v) / scale + centre: a reconstruction back in the scan's own frame.
+ * ------------------------------------------------------------------------------------------ */
+int p2s_prepare_finite(const float *pts_dev, int64_t n, float *pts_out_dev, int32_t *ids_out_dev, int64_t *n_out_host, int device,
+                       void *stream);
+int p2s_prepare_crop(const float *pts_dev, int64_t n, double quantile, double margin, float *pts_out_dev, int32_t *ids_out_dev,
+                     int64_t *n_out_host, double *bounds_host, int device, void *stream);
+int p2s_prepare_outliers(const float *pts_dev, int64_t n, int k, double std_ratio, double *d_out_dev, float *pts_out_dev,
+                         int32_t *ids_out_dev, int64_t *n_out_host, double *info_host, int device, void *stream);
+int p2s_prepare_voxel_thin(const float *pts_dev, int64_t n, int64_t max_points, int resolution, float *pts_out_dev,
+                           int32_t *ids_out_dev, int64_t *n_out_host, int64_t *info_host, int device, void *stream);
+int p2s_prepare_normalize(const float *pts_dev, int64_t n, float *pts_out_dev, double *info_host, int device, void *stream);
+int p2s_prepare_gather(const void *src_dev, int64_t n_src, int width, const int32_t *ids_dev, int64_t n_ids, void *out_dev, int device,
+                       void *stream);
+int p2s_prepare_restore(const float *verts_dev, int64_t n, const double *centre_host, double scale, double *out_dev, int device,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

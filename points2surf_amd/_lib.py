@@ -139,6 +139,16 @@ PROTOTYPES = {
     'p2s_cloudset_size': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     'p2s_cloudset_knn_patch': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'p2s_cloudset_subsample_uniform': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    'p2s_prepare_finite': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p]),
+    'p2s_prepare_crop': (c_int, [c_void_p, c_int64, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+                                 ctypes.POINTER(ctypes.c_double), c_int, c_void_p]),
+    'p2s_prepare_outliers': (c_int, [c_void_p, c_int64, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+                                     ctypes.POINTER(ctypes.c_double), c_int, c_void_p]),
+    'p2s_prepare_voxel_thin': (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+                                       ctypes.POINTER(c_int64), c_int, c_void_p]),
+    'p2s_prepare_normalize': (c_int, [c_void_p, c_int64, c_void_p, ctypes.POINTER(ctypes.c_double), c_int, c_void_p]),
+    'p2s_prepare_gather': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    'p2s_prepare_restore': (c_int, [c_void_p, c_int64, ctypes.POINTER(ctypes.c_double), ctypes.c_double, c_void_p, c_int, c_void_p]),
 }
 
 
