@@ -826,6 +826,30 @@ int p2s_trainer_profile(p2s_trainer_t t, int enabled, double *family_ms);
 int p2s_train_losses(const float *pred_dev, const float *dist_abs_dev, const float *sign01_dev, const float *radius_dev,
                      int B, double *losses_host, void *stream);
 
+/* Test hooks: single layers of the training step on caller-supplied shapes, through the host functions and kernels the
+ * trainer itself runs (the same slab decisions, the K = 3 path included), with scratch of their own.  All arrays are device
+ * memory of one device; blocking (`stream` is synchronised).  Non-positive sizes, arrays that are not device memory and
+ * scratch that cannot be allocated are refused with a message.  Training does not call them.
+ *
+ * One linear layer, M rows: y_dev [M][N] = X W^T + b;  dW = dY^T X, db = column sums of dY, dx_dev [M][K] = dY W, or
+ * += dY W with accum = 1.  params_dev and grads_dev share the layout of the trainer's flat arrays: W / dW [N][K] at 0,
+ * b / db [N] at b_offset >= N * K (a test may leave a gap between the two). */
+int p2s_debug_train_linear(const float *x_dev, const float *params_dev, int64_t b_offset, const float *dy_dev, float *y_dev,
+                           float *dx_dev, float *grads_dev, int M, int N, int K, int accum, void *stream);
+/* One batch-norm over y_dev [M][C], M >= 2, on batch statistics (eps 1e-5): z_dev [M][C] = gamma xhat + beta, through a
+ * ReLU when relu != 0; mean_dev [C], invstd_dev [C]; then its backward: d_dev [M][C] holds dL/dz on entry and dL/dy on
+ * return.  params_dev: gamma [C] at 0, beta [C] at second_offset >= C; grads_dev: d gamma and d beta, pending_dev: the batch
+ * mean and the unbiased batch variance (what the running statistics are updated with), both laid out like params_dev. */
+int p2s_debug_train_bn(const float *y_dev, const float *params_dev, int64_t second_offset, float *z_dev, float *mean_dev,
+                       float *invstd_dev, float *pending_dev, float *d_dev, float *grads_dev, int M, int C, int relu, void *stream);
+/* Which units the ReLUs of the last p2s_trainer_forward_backward let through (1: output > 0), so that a float64
+ * restatement can differentiate the same piece of the piecewise-linear network where a pre-activation lies within fp32
+ * rounding of zero -- the counterpart of p2s_trainer_pool_indices.  host [n] bytes: the layers in the order of the
+ * reference's forward (feat_global: conv0a, conv0b, with feature transforms stn2.conv1 .. conv3, stn2.fc1, stn2.fc2, then
+ * conv1, conv2; fc1_global; the same for feat_local and fc1_local; fc2; fc3), each [rows][channels] as the activations
+ * are stored.  n must be the total number of such units (named in the message otherwise).  Blocking. */
+int p2s_debug_train_relu_masks(p2s_trainer_t t, uint8_t *host, int64_t n);
+
 /* ------------------------------------------------------------------------------------------
  * A set of clouds behind one handle: batches whose items come from many clouds, one call each
  * (the training loader: a batch of 501 items touches about as many shapes).

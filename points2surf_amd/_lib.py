@@ -134,6 +134,11 @@ PROTOTYPES = {
     'p2s_trainer_pool_indices': (c_int, [c_void_p, c_void_p, c_int64]),
     'p2s_trainer_profile': (c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_double)]),
     'p2s_train_losses': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_double), c_void_p]),
+    'p2s_debug_train_linear': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                       c_int, c_void_p]),
+    'p2s_debug_train_bn': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                   c_int, c_int, c_void_p]),
+    'p2s_debug_train_relu_masks': (c_int, [c_void_p, c_void_p, c_int64]),
     'p2s_cloudset_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, ctypes.POINTER(c_void_p)]),
     'p2s_cloudset_destroy': (c_int, [c_void_p]),
     'p2s_cloudset_size': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),

@@ -17,6 +17,7 @@
 #include "p2s_common.h"
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 namespace {
@@ -610,8 +611,8 @@ int linear_bwd(T *t, const LinP &l, const float *X, const float *dY, float *dX, 
     return P2S_OK;
 }
 
-int blk_fwd(T *t, Blk &b) {
-    TRY(linear_fwd(t, b.lin, b.X, b.Y, b.M));
+// batch statistics of b.Y, then Z = batch-norm(Y) (+ReLU)
+int bn_fwd(T *t, Blk &b) {
     ColArgs a{}; a.a = b.Y; a.M = b.M; a.C = b.bn.C; a.mode = CS_STATS;
     ColFinish f{}; f.o0 = b.mean; f.o1 = b.invstd; f.g0 = t->pend + b.bn.rm; f.g1 = t->pend + b.bn.rv;
     TRY(colsum(t, a, f));
@@ -623,19 +624,28 @@ int blk_fwd(T *t, Blk &b) {
     return P2S_OK;
 }
 
-// d: dL/dZ on entry (overwritten with dL/dY); dX (may be null) receives dL/dX
-int blk_bwd(T *t, Blk &b, float *d, float *dX, int accum) {
+int blk_fwd(T *t, Blk &b) {
+    TRY(linear_fwd(t, b.lin, b.X, b.Y, b.M));
+    return bn_fwd(t, b);
+}
+
+// d: dL/dZ on entry, overwritten with dL/dY; d beta and d gamma
+int bn_bwd(T *t, Blk &b, float *d) {
     ColArgs a{}; a.a = d; a.y = b.Y; a.z = b.Z; a.mean = b.mean; a.invstd = b.invstd; a.M = b.M; a.C = b.bn.C; a.mode = CS_BNBWD;
     a.relu = b.relu;
     ColFinish f{}; f.o0 = b.m1; f.o1 = b.m2; f.g0 = t->grads + b.bn.be; f.g1 = t->grads + b.bn.g;
     TRY(colsum(t, a, f));
-    {
-        Prof p(t, FAM_BN);
-        const long long n = (long long)b.M * b.bn.C;
-        hipLaunchKernelGGL(p2s_train_bn_bwd_kernel, g1(n), dim3(256), 0, t->s, d, b.Y, b.Z, b.mean, b.invstd, t->params + b.bn.g, b.m1,
-                           b.m2, n, b.bn.C, b.relu);
-        P2S_LAUNCH_CHECK("p2s_train_bn_bwd_kernel");
-    }
+    Prof p(t, FAM_BN);
+    const long long n = (long long)b.M * b.bn.C;
+    hipLaunchKernelGGL(p2s_train_bn_bwd_kernel, g1(n), dim3(256), 0, t->s, d, b.Y, b.Z, b.mean, b.invstd, t->params + b.bn.g, b.m1,
+                       b.m2, n, b.bn.C, b.relu);
+    P2S_LAUNCH_CHECK("p2s_train_bn_bwd_kernel");
+    return P2S_OK;
+}
+
+// d: dL/dZ on entry (overwritten with dL/dY); dX (may be null) receives dL/dX
+int blk_bwd(T *t, Blk &b, float *d, float *dX, int accum) {
+    TRY(bn_bwd(t, b, d));
     return linear_bwd(t, b.lin, b.X, d, dX, b.M, accum);
 }
 
@@ -1078,6 +1088,149 @@ int p2s_train_losses(const float *pred_dev, const float *dist_abs_dev, const flo
     P2S_HIP_CHECK(hipStreamSynchronize(s));
     losses_host[0] = lh[0];
     losses_host[1] = lh[1];
+    return P2S_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// A trainer context for the test hooks: the caller's flat arrays in place of the model's, scratch of exactly the size the
+// shape needs (what plan() provides for the network's layers), freed when the hook returns.
+struct DebugCtx {
+    p2s_trainer_s t;
+    ~DebugCtx() {
+        if (t.wpart) (void)hipFree(t.wpart);
+        if (t.cpart) (void)hipFree(t.cpart);
+        if (t.arena) (void)hipFree(t.arena);
+    }
+    // every pointer must be device memory of one device, which becomes current
+    int open(const char *who, std::initializer_list<const void *> ptrs, void *stream) {
+        int dev = -1;
+        for (const void *p : ptrs) {
+            hipPointerAttribute_t at;
+            if (!p || hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || (dev >= 0 && at.device != dev)) {
+                (void)hipGetLastError();
+                p2s_set_error("%s: every array must be device memory of one device", who);
+                return P2S_EINVAL;
+            }
+            dev = at.device;
+        }
+        P2S_HIP_CHECK(hipSetDevice(dev));
+        t.device = dev;
+        t.s = (hipStream_t)stream;
+        return P2S_OK;
+    }
+    // column-sum partials for M rows of C channels, slab partials for a weight gradient of n values over M rows
+    int scratch(const char *who, int M, int C, long long n) {
+        const size_t cbytes = (size_t)colsum_slabs(M) * C * 3 * sizeof(double);
+        const int slabs = dw_slabs(M);
+        t.wpart_floats = slabs > 1 ? slabs * n : 0;
+        if (hipMalloc((void **)&t.cpart, cbytes) != hipSuccess ||
+            (t.wpart_floats > 0 && hipMalloc((void **)&t.wpart, (size_t)t.wpart_floats * 4) != hipSuccess)) {
+            (void)hipGetLastError();
+            p2s_set_error("%s: cannot allocate %zu + %lld bytes of scratch", who, cbytes, t.wpart_floats * 4);
+            return P2S_ENOMEM;
+        }
+        return P2S_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int p2s_debug_train_linear(const float *x_dev, const float *params_dev, int64_t b_offset, const float *dy_dev, float *y_dev,
+                           float *dx_dev, float *grads_dev, int M, int N, int K, int accum, void *stream) {
+    const char *who = "p2s_debug_train_linear";
+    if (M <= 0 || N <= 0 || K <= 0 || (accum != 0 && accum != 1) || b_offset < (int64_t)N * K) {
+        p2s_set_error("%s: M = %d, N = %d, K = %d must be positive, accum = %d must be 0 or 1, b_offset = %lld at least N * K", who, M,
+                      N, K, accum, (long long)b_offset);
+        return P2S_EINVAL;
+    }
+    if ((long long)M * std::max(N, K) >= (1LL << 31)) {
+        p2s_set_error("%s: M = %d with N = %d, K = %d: more than 2^31 values in one array", who, M, N, K);
+        return P2S_ECAPACITY;
+    }
+    DebugCtx c;
+    TRY(c.open(who, {x_dev, params_dev, dy_dev, y_dev, dx_dev, grads_dev}, stream));
+    TRY(c.scratch(who, M, N, (long long)N * K));
+    c.t.params = const_cast<float *>(params_dev);
+    c.t.grads = grads_dev;
+    LinP l;
+    l.K = K; l.N = N; l.w = 0; l.b = b_offset;
+    TRY(linear_fwd(&c.t, l, x_dev, y_dev, M));
+    TRY(linear_bwd(&c.t, l, x_dev, dy_dev, dx_dev, M, accum));
+    P2S_HIP_CHECK(hipStreamSynchronize(c.t.s));
+    return P2S_OK;
+}
+
+int p2s_debug_train_bn(const float *y_dev, const float *params_dev, int64_t second_offset, float *z_dev, float *mean_dev,
+                       float *invstd_dev, float *pending_dev, float *d_dev, float *grads_dev, int M, int C, int relu, void *stream) {
+    const char *who = "p2s_debug_train_bn";
+    if (M < 2 || C <= 0 || second_offset < C) {
+        p2s_set_error("%s: M = %d must be at least 2 (batch statistics), C = %d positive, second_offset = %lld at least C", who, M, C,
+                      (long long)second_offset);
+        return P2S_EINVAL;
+    }
+    if ((long long)M * C >= (1LL << 31)) {
+        p2s_set_error("%s: M = %d with C = %d: more than 2^31 values in one array", who, M, C);
+        return P2S_ECAPACITY;
+    }
+    DebugCtx c;
+    TRY(c.open(who, {y_dev, params_dev, z_dev, mean_dev, invstd_dev, pending_dev, d_dev, grads_dev}, stream));
+    TRY(c.scratch(who, M, C, 0));
+    if (hipMalloc((void **)&c.t.arena, 2 * (size_t)C * 4) != hipSuccess) {      // the two means of the backward
+        (void)hipGetLastError();
+        p2s_set_error("%s: cannot allocate %zu bytes of scratch", who, 2 * (size_t)C * 4);
+        return P2S_ENOMEM;
+    }
+    c.t.params = const_cast<float *>(params_dev);
+    c.t.grads = grads_dev;
+    c.t.pend = pending_dev;
+    Blk b{};
+    b.bn.C = C; b.bn.g = 0; b.bn.be = second_offset; b.bn.rm = 0; b.bn.rv = second_offset;
+    b.relu = relu ? 1 : 0; b.M = M;
+    b.Y = const_cast<float *>(y_dev); b.Z = z_dev;
+    b.mean = mean_dev; b.invstd = invstd_dev; b.m1 = c.t.arena; b.m2 = c.t.arena + C;
+    TRY(bn_fwd(&c.t, b));
+    TRY(bn_bwd(&c.t, b, d_dev));
+    P2S_HIP_CHECK(hipStreamSynchronize(c.t.s));
+    return P2S_OK;
+}
+
+int p2s_debug_train_relu_masks(p2s_trainer_t t, uint8_t *host, int64_t n) {
+    const char *who = "p2s_debug_train_relu_masks";
+    if (!t || !host) { p2s_set_error("%s: null argument", who); return P2S_EINVAL; }
+    if (!t->arena || t->B < 2) { p2s_set_error("%s: no training step has run on this trainer", who); return P2S_EINVAL; }
+    // the order of the reference's forward: feat_global, fc1_global, feat_local, fc1_local, fc2, fc3
+    std::vector<const Blk *> blks;
+    for (int e = 1; e >= 0; --e) {
+        const FeatA &f = t->fa[e];
+        blks.push_back(&f.b0a); blks.push_back(&f.b0b);
+        if (t->stn)
+            for (const Blk *b : {&f.t1, &f.t2, &f.t3, &f.t4, &f.t5}) blks.push_back(b);
+        blks.push_back(&f.b1); blks.push_back(&f.b2);
+        blks.push_back(&t->h1[e]);
+    }
+    blks.push_back(&t->h2); blks.push_back(&t->h3);
+    long long total = 0;
+    for (const Blk *b : blks) total += (long long)b->M * b->bn.C;
+    if (n != total) {
+        p2s_set_error("%s: %lld values asked, the last step has %lld units behind a ReLU", who, (long long)n, total);
+        return P2S_EINVAL;
+    }
+    P2S_HIP_CHECK(hipSetDevice(t->device));
+    P2S_HIP_CHECK(hipDeviceSynchronize());
+    std::vector<float> tmp;
+    long long o = 0;
+    for (const Blk *b : blks) {
+        const size_t cnt = (size_t)b->M * b->bn.C;
+        tmp.resize(cnt);
+        P2S_HIP_CHECK(hipMemcpy(tmp.data(), b->Z, cnt * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < cnt; ++i) host[o + i] = tmp[i] > 0.f ? 1 : 0;
+        o += (long long)cnt;
+    }
     return P2S_OK;
 }
 

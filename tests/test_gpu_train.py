@@ -2,7 +2,10 @@
 reference's train-mode step (tests/train_model.py), net size 1024, both trainable configurations.
 
 Shapes (B, P, S): (5, 37, 53) nothing is a multiple of a 64-row tile (item 0 padded with duplicate points: exact pool
-ties); (3, 64, 33) exactly one row tile per patch beside partial ones; (2, 8, 8) the smallest legal batch.
+ties); (3, 64, 33) exactly one row tile per patch beside partial ones; (2, 8, 8) the smallest legal batch; (33, 64, 70)
+M = 2112 and 2310 point rows: the weight gradients of the point-wise layers are summed over two 2048-row slabs, one of them
+exactly full and one partial; (2049, 2, 3) M = 4098 and 6147 (3 and 4 slabs), M = B = 2049 in the per-item layers (two slabs,
+the 4096 x 256 partials of the arena) and a loss summed over more than one pass of its 256 threads.
 
 GRADIENTS.  Per parameter tensor ||g_dev - g_cpu||_2 / ||g_cpu||_2 against the float64 restatement with every max-pool
 forced to the DEVICE's recorded indices.  The gate is measured, not fixed: the same restatement runs in float32 on the
@@ -17,6 +20,20 @@ within fp32 rounding of the maximum: the pooled tensor is at most 12 linear laye
 keeps every layer O(1)), so |z_max - z_dev| <= 12 * 128 * 2^-24 * max|z| of that channel = 9.2e-5 of the channel's
 largest magnitude; a wrong pick is off by O(0.1) of it.  At most 0.1 % of all (item, channel) pairs may differ at all; the
 seeds are chosen so that float32-CPU against float64-CPU stays under 0.025 % on the same inputs, which is checked here.
+
+RELU MASKS.  A ReLU is the other place where two precisions can differentiate different pieces of the network: a unit whose
+pre-activation lies within fp32 rounding of zero is let through by one and not by the other, which moves a gradient by
+about 1 / sqrt(active units).  At (2049, 2, 3) the step has 21.8 M such units and a tie is the expected case: measured on the
+MI355X with p2s_max, three units whose float64 pre-activations lie within 3e-8 of their channel's largest magnitude are
+masked the other way by the device; left to the float64 signs, 52 of 76 gradient tensors miss the 7.8e-6 gate (worst
+1.1e-3), and with the device's masks all agree within 1.64e-6.  So the CPU runs of _one_step take the DEVICE's masks
+(p2s_debug_train_relu_masks) as they take its pool indices, in both precisions, and test_relu_masks holds the device to
+them: where its mask differs from the sign of the float64 pre-activation, that pre-activation must lie within fp32 rounding
+of zero.  The bound follows the pool rule: a unit lies behind at most 15 linear layers whose reduced lengths add up to
+3 + 3 x 64 + 128 + 1024 + 512 + 256 + 3 x 64 + 128 + 1024 + 1024 + 256 = 4739 products (batch-norm keeps every layer
+O(1)), so |z| <= 4739 * 2^-24 * max|z| of its channel = 2.8e-4 of the channel's largest magnitude, and at most 0.1 % of all
+units may differ at all.  A mask that is wrong by more than rounding fails this rule; a right one leaves the gates what they
+were: 4x the float32-CPU error, the loss gates and the pool rule unchanged.
 """
 import os
 import subprocess
@@ -34,9 +51,11 @@ import train_model as TM  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 CONFIGS = ['p2s_max', 'p2s_max_no_feat_stn']
-SHAPES = [(5, 37, 53, True), (3, 64, 33, False), (2, 8, 8, False)]
+SHAPES = [(5, 37, 53, True), (3, 64, 33, False), (2, 8, 8, False), (33, 64, 70, False), (2049, 2, 3, False)]
+SLAB_SHAPE = SHAPES[3]
 SEED = 1
 POOL_ROUNDING = 12 * 128 * 2.0 ** -24
+RELU_ROUNDING = 4739 * 2.0 ** -24
 GATE_FACTOR = 4.0
 
 
@@ -82,6 +101,29 @@ def _check_tensors(dev, ref, gate, what, zero=(), ref_grads=None):
     return worst
 
 
+def _relu_masks(tr, cfg, B, P, S):
+    """the device's ReLU masks of the last step, one array per ReLU of train_model's forward, shaped like its input"""
+    import ctypes
+    from points2surf_amd import _lib
+    layers = []                         # (points per item or 0 for a per-item layer, channels), in forward order
+    for pts in (S, P):
+        layers += [(pts, 64), (pts, 64)]
+        if cfg.get('use_feat_stn', True):
+            layers += [(pts, 64), (pts, 128), (pts, 1024), (0, 512), (0, 256)]
+        layers += [(pts, 64), (pts, 128), (0, 512)]
+    layers += [(0, 256), (0, 128)]
+    flat = np.empty(sum(B * max(pts, 1) * C for pts, C in layers), np.uint8)
+    _lib.check(tr.lib.p2s_debug_train_relu_masks(tr.handle, flat.ctypes.data_as(ctypes.c_void_p), flat.size))
+    assert flat.max() <= 1
+    out, o = [], 0
+    for pts, C in layers:
+        n = B * max(pts, 1) * C
+        m = flat[o:o + n]
+        out.append(np.ascontiguousarray(m.reshape(B, pts, C).transpose(0, 2, 1)) if pts else m.reshape(B, C))
+        o += n
+    return out
+
+
 _step_cache = {}
 
 
@@ -97,7 +139,8 @@ def _one_step(torch, name, shape):
     b = TM.make_batch(B, P, S, SEED, pad)
     tr = train.Trainer(cfg, w)
     loss = tr.forward_backward(*_dev_batch(torch, b))
-    r = dict(batch=b, cfg=cfg, w=w, loss=loss, grads=tr.grads(), pools=tr.pool_indices(), state=tr.state_dict(module_prefix=False))
+    r = dict(batch=b, cfg=cfg, w=w, loss=loss, grads=tr.grads(), pools=tr.pool_indices(), state=tr.state_dict(module_prefix=False),
+             relu=_relu_masks(tr, cfg, B, P, S))
     tr.close()
     free64 = TM.TrainModel(w, cfg)
     free64.forward_backward(*_cpu_args(b))
@@ -107,8 +150,9 @@ def _one_step(torch, name, shape):
     r['free32_pools'] = free32.pools
     for tag, dt in (('f64', th.float64), ('f32', th.float32)):
         m = TM.TrainModel(w, cfg, dtype=dt)
-        r[tag + '_loss'] = m.forward_backward(*_cpu_args(b), forced=r['pools'])
+        r[tag + '_loss'] = m.forward_backward(*_cpu_args(b), forced=r['pools'], forced_relu=r['relu'])
         r[tag + '_grads'], r[tag + '_state'], r[tag + '_pred'] = m.grads(), m.state(), m.pred
+        r[tag + '_relu_ties'], r[tag + '_relu_units'] = m.relu_ties, m.relu_units
     _step_cache[key] = r
     return r
 
@@ -160,15 +204,39 @@ def test_pool_indices(name, shape, torch_cuda):
     assert differ <= 0.001 * n
 
 
+@pytest.mark.parametrize('shape', SHAPES, ids=lambda s: '%dx%dx%d' % s[:3])
 @pytest.mark.parametrize('name', CONFIGS)
-def test_running_statistics_after_one_step(name, torch_cuda):
-    r = _one_step(torch_cuda, name, SHAPES[0])
+def test_relu_masks(name, shape, torch_cuda):
+    """the device's ReLU masks against the float64 pre-activations (module docstring, RELU MASKS)"""
+    r = _one_step(torch_cuda, name, shape)
+    ties, n = r['f64_relu_ties'], r['f64_relu_units']
+    assert len(ties) == len(r['relu']) == (22 if r['cfg'].get('use_feat_stn', True) else 12) and n == sum(m.size for m in r['relu'])
+    differ = sum(t.size for t in ties)
+    worst = max([float(t.max()) for t in ties if t.size] or [0.0])
+    print('%s %s: %d of %d ReLU units masked unlike float64 (unlike float32 on the CPU: %d), the furthest from zero at %.3g of its channel'
+          % (name, shape[:3], differ, n, sum(t.size for t in r['f32_relu_ties']), worst))
+    assert worst <= RELU_ROUNDING, (worst, RELU_ROUNDING)
+    assert differ <= 0.001 * n
+
+
+def _check_running_statistics(torch_cuda, name, shape):
+    r = _one_step(torch_cuda, name, shape)
     bufs = [k for k in r['f64_state'] if k.endswith(('running_mean', 'running_var'))]
     gate = _gate({k: r['f32_state'][k] for k in bufs}, {k: r['f64_state'][k] for k in bufs})
     _check_tensors({k: r['state'][k].numpy() for k in bufs}, {k: r['f64_state'][k] for k in bufs}, gate, 'buffer')
     for k, v in r['state'].items():
         if k.endswith('num_batches_tracked'):
             assert v.dtype == torch_cuda.int64 and int(v) == 1001 == int(r['f64_state'][k])
+
+
+@pytest.mark.parametrize('name', CONFIGS)
+def test_running_statistics_after_one_step(name, torch_cuda):
+    _check_running_statistics(torch_cuda, name, SHAPES[0])
+
+
+@pytest.mark.parametrize('name', CONFIGS)
+def test_running_statistics_after_one_step_with_two_slabs(name, torch_cuda):
+    _check_running_statistics(torch_cuda, name, SLAB_SHAPE)
 
 
 @pytest.mark.parametrize('name', CONFIGS)
@@ -224,10 +292,9 @@ def test_three_sgd_steps_in_lockstep_and_round_trip(name, torch_cuda):
     tr.close()
 
 
-@pytest.mark.parametrize('name', CONFIGS)
-def test_equal_state_and_batch_give_equal_bytes(name, torch_cuda):
+def _check_equal_bytes(torch_cuda, name, shape):
     from points2surf_amd import train
-    B, P, S, pad = SHAPES[0]
+    B, P, S, pad = shape
     w, cfg = _weights(name, P, S)
     b = TM.make_batch(B, P, S, SEED, pad)
     out = []
@@ -243,6 +310,17 @@ def test_equal_state_and_batch_give_equal_bytes(name, torch_cuda):
         assert v.tobytes() == out[1][0][k].tobytes(), k
     for k, v in out[0][1].items():
         assert v.tobytes() == out[1][1][k].tobytes(), k
+
+
+@pytest.mark.parametrize('name', CONFIGS)
+def test_equal_state_and_batch_give_equal_bytes(name, torch_cuda):
+    _check_equal_bytes(torch_cuda, name, SHAPES[0])
+
+
+@pytest.mark.parametrize('name', CONFIGS)
+def test_equal_state_and_batch_give_equal_bytes_with_two_slabs(name, torch_cuda):
+    """the slab partials are reduced in slab order: equal bytes through p2s_train_slab_reduce_kernel as well"""
+    _check_equal_bytes(torch_cuda, name, SLAB_SHAPE)
 
 
 def test_refusals(torch_cuda):

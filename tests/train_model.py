@@ -6,6 +6,8 @@ source/points_to_surf_train.py:537-563 (compute_loss) and source/sdf_nn.py:30-40
 update from ``torch.optim.SGD``.  Any dtype (float64 is the yardstick of the device tests, float32 measures what single
 precision alone costs).  A max-pool can be FORCED to given indices -- a gather in place of the max -- so that two
 precisions (or the device and the CPU) differentiate the same piecewise-linear function where near-ties resolve differently.
+A ReLU can be forced in the same way to given masks (``forced_relu``): a pre-activation within rounding of zero is let
+through by one precision and not by the other, which is the same kind of tie.
 """
 from collections import OrderedDict
 
@@ -78,10 +80,26 @@ class TrainModel:
 
     def _conv_bn(self, x, conv, bn, relu=True):
         x = self._bn(F.conv1d(x, self.w[conv + '.weight'], self.w[conv + '.bias']), bn)
-        return F.relu(x) if relu else x
+        return self._relu(x) if relu else x
 
     def _fc_bn(self, x, fc, bn):
-        return F.relu(self._bn(F.linear(x, self.w[fc + '.weight'], self.w[fc + '.bias']), bn))
+        return self._relu(self._bn(F.linear(x, self.w[fc + '.weight'], self.w[fc + '.bias']), bn))
+
+    def _relu(self, x):
+        """forced: the mask of this call (in the order of the forward) replaces x > 0.  Where the two differ, |x| over the
+        largest |x| of its channel in this layer is kept in ``self.relu_ties``, and ``self.relu_units`` counts all units"""
+        j = len(self.relu_ties)
+        if self.forced_relu is None:
+            self.relu_ties.append(np.zeros(0))
+            return F.relu(x)
+        mask = torch.as_tensor(np.asarray(self.forced_relu[j])).to(self.device) != 0
+        assert mask.shape == x.shape, (j, mask.shape, x.shape)
+        xd = x.detach()
+        dims = (0, 2) if xd.dim() == 3 else (0,)
+        ratio = xd.abs() / xd.abs().amax(dim=dims, keepdim=True).clamp_min(1e-300)
+        self.relu_ties.append(ratio[mask != (xd > 0)].cpu().numpy().astype(np.float64))
+        self.relu_units += xd.numel()
+        return x * mask.to(x.dtype)
 
     def _pool(self, x, name, forced):
         if forced is not None:
@@ -116,10 +134,12 @@ class TrainModel:
         x = self._conv_bn(x, pre + '.conv3', pre + '.bn3', relu=False)
         return self._pool(x, pre, forced)
 
-    def forward(self, patch_ps, sub_ms, query, forced=None):
+    def forward(self, patch_ps, sub_ms, query, forced=None, forced_relu=None):
         """-> pred [B, 2]; the batch-norms run on batch statistics and update their running buffers.  The pooled indices of
-        this call are left in ``self.pools`` (and the pooled tensors in ``self.pool_inputs`` when nothing is forced)."""
+        this call are left in ``self.pools`` (and the pooled tensors in ``self.pool_inputs`` when nothing is forced).
+        ``forced_relu``: one 0 / 1 array per ReLU in the order of this forward, shaped like its input"""
         self.pools, self.pool_inputs = {}, {}
+        self.forced_relu, self.relu_ties, self.relu_units = forced_relu, [], 0
         dt, dev = self.dtype, self.device
         as_t = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(dev, dt)
         patch = as_t(patch_ps).transpose(1, 2)
@@ -139,11 +159,11 @@ class TrainModel:
         sgn = F.binary_cross_entropy_with_logits(pred[:, 1], as_t(sign01), reduction='none').mean()
         return mag, sgn
 
-    def forward_backward(self, patch_ps, sub_ms, query, dist_abs, sign01, radius, forced=None):
+    def forward_backward(self, patch_ps, sub_ms, query, dist_abs, sign01, radius, forced=None, forced_relu=None):
         """-> (magnitude loss, sign loss) as floats; gradients are left in the parameters' ``.grad``"""
         for p in self.params().values():
             p.grad = None
-        pred = self.forward(patch_ps, sub_ms, query, forced)
+        pred = self.forward(patch_ps, sub_ms, query, forced, forced_relu)
         self.pred = pred.detach().cpu().numpy().astype(np.float64) if self.record else None
         mag, sgn = self.losses(pred, dist_abs, sign01, radius)
         (mag + sgn).backward()
