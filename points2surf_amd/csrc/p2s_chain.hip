@@ -215,11 +215,13 @@ constexpr int SCR_HB = 128 + 8;      // halfs per row of the fp16 copy of the co
 constexpr int SCR_QCAP = 256;        // candidates a wave's queue holds: < 64 left over + what one column tile may add
 constexpr float P2S_SCR_KAPPA = 0x1.1p-10f;   // k_screen + k_fp32 of the margin (derived in p2s_chain_screen.inl)
 // LDS of the screened kernel (floats): the two fp32 tiles (the fp16 copy of h lies over bufA), the exact pool E [1024], the four
-// waves' candidate queues, the reduction scratch
+// waves' candidate queues, the reduction scratch, the running screen maxima and the margin coefficients (66 KB in all)
 constexpr int SCR_OFF_E = MT * SA + MT * SB;
 constexpr int SCR_OFF_Q = SCR_OFF_E + 1024;
 constexpr int SCR_OFF_RED = SCR_OFF_Q + 4 * SCR_QCAP;
-constexpr int SCR_LDS_FLOATS = SCR_OFF_RED + 8;
+constexpr int SCR_OFF_R = SCR_OFF_RED + 8;            // running screen maxima R [1024] (r11: out of the registers)
+constexpr int SCR_OFF_MU = SCR_OFF_R + 1024;          // margin coefficients [1024], copied once per workgroup
+constexpr int SCR_LDS_FLOATS = SCR_OFF_MU + 1024;
 static_assert(MT * SCR_HB * 2 <= MT * SA * 4, "the fp16 copy fits the 64-channel tile it lies over");
 static_assert(2 * SCR_LDS_FLOATS * 4 <= 160 * 1024, "two workgroups per CU");
 
@@ -287,7 +289,7 @@ __device__ __forceinline__ void scr_confirm(unsigned entry, const float *hB, __a
     else atomicMin(E + cw, (unsigned)bits);
 }
 
-// SCREEN (max pool, full chain only): conv3 through p2s_chain_screen.inl, two workgroups per CU (58 KB of LDS); an item the
+// SCREEN (max pool, full chain only): conv3 through p2s_chain_screen.inl, two workgroups per CU (66 KB of LDS); an item the
 // screen cannot decide runs a second time with the dense conv3 below
 template <bool SUM, bool SCREEN = false>
 __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArgs args) {
@@ -381,15 +383,21 @@ __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArg
     const float *__restrict__ scr_mu = args.w3mu[bsel];
     const __amdgpu_buffer_rsrc_t rs3h = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(args.w3h[bsel]), 0,
                                                                            (int)(P2S_SCR_PIECE * 2), 0x00020000);
-    float sr0 = -INFINITY, sr1 = -INFINITY, sr2 = -INFINITY, sr3 = -INFINITY, sr4 = -INFINITY, sr5 = -INFINITY, sr6 = -INFINITY,
-          sr7 = -INFINITY;                     // running maxima of the screen values of this lane's column of the 8 column tiles
+    // running maxima of the screen values of this wave's 256 columns and their margin coefficients: in LDS, so that the second
+    // accumulator set of the column-tile pipeline has their registers (lanes l and l ^ 32 hold and write the same value)
+    float *scr_R = smem + SCR_OFF_R + 256 * wave;
+    float *scr_mul = smem + SCR_OFF_MU + 256 * wave;
     bool undec = false;                        // the screen cannot decide this item (wave-uniform)
     float scr_Hsq = 0.0f;                      // largest squared row norm of the conv2 tiles of the item so far
     int nconf = 0;                             // fp32 chains this wave ran
     bool dense_pass = !SCREEN;
     if constexpr (SCREEN) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) scr_E[64 * i + lane] = __float_as_uint(-INFINITY);
+        for (int i = 0; i < 4; ++i) {
+            scr_E[64 * i + lane] = __float_as_uint(-INFINITY);
+            scr_R[64 * i + lane] = -INFINITY;
+            scr_mul[64 * i + lane] = scr_mu[256 * wave + 64 * i + lane];     // read by this wave only: no barrier
+        }
     }
     for (;;) {
     load_point(0, nx0, nx1, nx2);
@@ -465,8 +473,9 @@ __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArg
         {
             f32x16 acc[2];
             layer_k64<2>(bufA, SA, 0, wb, lane, acc);
-            // first conv3 weight fragments, in flight across the barrier
-            if (!SCREEN || dense_pass) {
+            // first conv3 weight fragments, in flight across the barrier (the screened kernel requests them in front of its
+            // dense conv3, below: requested here, their eight registers stayed reserved across the screen)
+            if constexpr (!SCREEN) {
                 bA0 = bufld4(w3rsrc, lane16, w3soff);
                 bA1 = bufld4(w3rsrc, lane16, w3soff + 16 * 1024);
             }
@@ -482,8 +491,13 @@ __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArg
       if constexpr (SCREEN) {
         if (!dense_pass) {
 #include "p2s_chain_screen.inl"
+            // the screened pass never pools into rm0 .. rm7: saying so here keeps the eight registers from being carried
+            // through the screen for the dense pass that may follow
+            rm0 = rm1 = rm2 = rm3 = rm4 = rm5 = rm6 = rm7 = pool0;
             continue;
         }
+        bA0 = bufld4(w3rsrc, lane16, w3soff);
+        bA1 = bufld4(w3rsrc, lane16, w3soff + 16 * 1024);
       }
         // ---- conv3 (K = 128, N = 1024) + running max over points -----------------------------------
         // wave w owns channels [256w, 256w+256) = 8 column tiles, processed as 4 pairs with a

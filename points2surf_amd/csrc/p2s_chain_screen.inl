@@ -3,7 +3,8 @@
 //
 // conv3 feeds only a max over the item's points: of the P x 1024 dot products 1024 reach the output.  This path decides on
 // ONE fp16 MFMA per product block which products can be the maximum and computes only those in fp32:
-//   screen   t[p][c] = sum_k fp16(h_pk) fp16(w_ck) on v_mfma_f32_32x32x16_f16, fp32 accumulate, one accumulator set;
+//   screen   t[p][c] = sum_k fp16(h_pk) fp16(w_ck) on v_mfma_f32_32x32x16_f16, fp32 accumulate, two accumulator sets (one
+//            column tile is selected while the next one's MFMAs issue: Schedule, below);
 //   margin   mu_c = 2 (k_screen + k_fp32) (|w_c| + 2^-10) (H + 2^-10),  H >= |h_p| for every row of every tile of the item so
 //            far, this one included (a running maximum: the margin only grows from tile to tile);
 //   select   (p, c) is a candidate iff t[p][c] >= max(R_c - mu_c, E_c - mu_c / 2), R_c = the running maximum of t[.][c] over
@@ -88,6 +89,12 @@
 // CU for as long as the MFMAs take -- and the weight stream is one ring of 8 slots over the tile's 8 x 8 k-blocks, 7
 // requests (7 KB per wave) in flight: k-block j + 7 is requested between the two MFMAs of k-block j, across the select, the
 // queue and the confirm of a column tile too.
+// The column tiles are a pipeline two deep (r11): the 16 MFMAs of column tile ct + 1 go into a second accumulator set and the
+// select of column tile ct (column maximum, record, threshold, 32 compares, mask: about 130 VALU instructions, which read the
+// first set only) is issued between them; then come the queue and the confirm of ct, as before.  The 32 registers of the
+// second set are the 24 that held `1 << j` for the mask (now built in groups of 7 rows from inline constants), the 8 running
+// maxima R (now in LDS beside E, like the margin coefficients, which were a global load with a full drain per column tile)
+// and 16 that the dense pass had reserved across the screen (profiles/r11/kernel_resources.txt).
 {
             unsigned short *hp0 = reinterpret_cast<unsigned short *>(bufA);      // fp16(h) [64][SCR_HB] over the conv2 input tile
             // ---- the weight stream: ONE ring over the tile's 8 column tiles x 8 k-blocks ---------------------------------
@@ -99,7 +106,6 @@
             u32x4 rb[8];
 #pragma unroll
             for (int s = 0; s < 7; ++s) rb[s] = scr_bufld(rs3h, lane16, soff0 + s * 1024);
-            float mu_c = scr_mu[256 * wave + (lane & 31)];                       // margin coefficient of column tile 0
             // ---- h -> fp16 beside the fp32 tile; row norms -------------------------------------------------------------
             if (scr_abl != 5) {
                 const int p = tid >> 2, q = tid & 3;
@@ -125,7 +131,6 @@
                 if (lane == 0) scr_red[wave] = ss;
                 if (__ballot(oor) != 0ull) undec = true;
             }
-            if (tile + 1 < ntiles) load_point(tile + 1, nx0, nx1, nx2);   // lands during the screen
             __syncthreads();
             // largest squared row norm of the item's tiles so far: the record R_c may be held by a row of an earlier tile
             scr_Hsq = fmaxf(scr_Hsq, fmaxf(fmaxf(scr_red[0], scr_red[1]), fmaxf(scr_red[2], scr_red[3])));
@@ -152,58 +157,68 @@
                 fa[kb][1] = scr_lds_a(hp0, 32, kb, lane);
             }
             int qn = 0;                                                          // entries in this wave's queue (wave-uniform)
-#pragma unroll 1
-            for (int ct = 0; ct < 8; ++ct) {
-                const int soff = soff0 + ct * 8 * 1024;
-                f32x16 acc[2];
-                // k-blocks ascending; the two row tiles alternate so that no MFMA follows the one it depends on, the ring's
-                // request sits between them
-#pragma unroll
-                for (int kb = 0; kb < 8; ++kb) {
-                    const u32x4 b = rb[kb];
-                    rb[(kb + 7) & 7] = scr_bufld(rs3h, lane16, soff + (kb + 7) * 1024);
-                    if (kb == 0) {
-                        acc[0] = scr_mfma(fa[0][0], b, zero16());
-                        acc[1] = scr_mfma(fa[0][1], b, zero16());
-                    } else {
-                        acc[0] = scr_mfma(fa[kb][0], b, acc[0]);
-                        acc[1] = scr_mfma(fa[kb][1], b, acc[1]);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            const int l31 = lane & 31;
+            float keep = -INFINITY;                                              // (development variant 3 only)
+            // k-block kb of one column tile into `acc`: the two row tiles alternate so that no MFMA follows the one it depends
+            // on, the ring's request sits between them (the callers' sched_group_barriers say where)
+            auto kblock = [&](f32x16 (&acc)[2], int soff, int kb) __attribute__((always_inline)) {
+                const u32x4 b = rb[kb];
+                rb[(kb + 7) & 7] = scr_bufld(rs3h, lane16, soff + (kb + 7) * 1024);
+                if (kb == 0) {
+                    acc[0] = scr_mfma(fa[0][0], b, zero16());
+                    acc[1] = scr_mfma(fa[0][1], b, zero16());
+                } else {
+                    acc[0] = scr_mfma(fa[kb][0], b, acc[0]);
+                    acc[1] = scr_mfma(fa[kb][1], b, acc[1]);
                 }
-                if (scr_abl == 3) {       // MFMAs and their loads only: one value of each accumulator, pooled, keeps them live
-                    sr0 = fmaxf(sr0, acc[0][0] + acc[1][0]);
-                    if (ct == 7) scr_E[lane] = __float_as_uint(sr0);
-                    continue;
-                }
-                const float mu = mu_c * Heff;
+            };
+            // The select of column tile ct from its finished accumulators, in the pieces the pipeline places: the column
+            // maximum of row tile 0, then that of row tile 1 and the threshold, then the mask in five groups of rows.
+            struct Sel {
+                float mu, Ec, Rold, m, thr;
+                unsigned mask;
+            };
+            auto sel_begin = [&](Sel &s, const f32x16 (&acc)[2], int ct) __attribute__((always_inline)) {
+                s.mu = scr_mul[32 * ct + l31] * Heff;
                 // the exact pool of this lane's channel over the EARLIER tiles: candidates of this column tile are queued
-                // below and confirmed after that, and every batch of an earlier tile has run (ct == 7 empties the queue);
+                // after this and confirmed after that, and every batch of an earlier tile has run (ct == 7 empties the queue);
                 // scr_E of a wave is written by that wave's own confirms only, the wave barriers order them before this read
-                const float Ec = __uint_as_float(scr_E[32 * ct + (lane & 31)]);
-                mu_c = scr_mu[256 * wave + 32 * (ct < 7 ? ct + 1 : 7) + (lane & 31)];   // the next column tile's, behind the ring's requests
+                s.Ec = __uint_as_float(scr_E[32 * ct + l31]);
+                s.Rold = scr_R[32 * ct + l31];
                 float m = fmaxf(acc[0][0], acc[0][1]);
 #pragma unroll
-                for (int j = 2; j < 32; j += 2) m = fmaxf(fmaxf(m, acc[j >> 4][j & 15]), acc[j >> 4][(j & 15) + 1]);
-                m = half_max(m);
-                float R;
-                if (ct == 0) R = sr0 = fmaxf(sr0, m);
-                else if (ct == 1) R = sr1 = fmaxf(sr1, m);
-                else if (ct == 2) R = sr2 = fmaxf(sr2, m);
-                else if (ct == 3) R = sr3 = fmaxf(sr3, m);
-                else if (ct == 4) R = sr4 = fmaxf(sr4, m);
-                else if (ct == 5) R = sr5 = fmaxf(sr5, m);
-                else if (ct == 6) R = sr6 = fmaxf(sr6, m);
-                else R = sr7 = fmaxf(sr7, m);
-                // -inf (nothing confirmed yet) leaves the R rule; fmaxf drops a NaN operand, so a NaN in E dismisses nothing
-                const float thr = fmaxf(R - mu, Ec - 0.5f * mu);
-                unsigned mask = 0;
+                for (int j = 2; j < 16; j += 2) m = fmaxf(fmaxf(m, acc[0][j]), acc[0][j + 1]);
+                s.m = m;
+                s.mask = 0;
+            };
+            auto sel_threshold = [&](Sel &s, const f32x16 (&acc)[2], int ct) __attribute__((always_inline)) {
+                float m = s.m;
 #pragma unroll
-                for (int j = 0; j < 32; ++j) mask |= (acc[j >> 4][j & 15] >= thr ? 1u : 0u) << j;
-                mask &= vmask;
-                // candidates -> this wave's queue, one per lane and round (ballot / mbcnt compaction)
+                for (int j = 0; j < 16; j += 2) m = fmaxf(fmaxf(m, acc[1][j]), acc[1][j + 1]);
+                {   // half_max() without `volatile`: a volatile asm is ordered against the ring's loads and would pin the
+                    // select behind the last of them
+                    const unsigned u = __float_as_uint(m);
+                    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+                    const float x = __uint_as_float(r[0]), y = __uint_as_float(r[1]);
+                    asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(x), "v"(y));
+                }
+                const float R = fmaxf(s.Rold, m);
+                scr_R[32 * ct + l31] = R;
+                // -inf (nothing confirmed yet) leaves the R rule; fmaxf drops a NaN operand, so a NaN in E dismisses nothing
+                s.thr = fmaxf(R - s.mu, s.Ec - 0.5f * s.mu);
+            };
+            // rows 7 gi .. 7 gi + 6 of the mask: 1 << 0 .. 1 << 6 are inline constants of v_cndmask, so no register holds a
+            // 1 << j (24 did); the group is made opaque before its shift, or the shift is folded back into the constants
+            auto sel_group = [&](Sel &s, const f32x16 (&acc)[2], int gi) __attribute__((always_inline)) {
+                unsigned g = 0;
+#pragma unroll
+                for (int j = 7 * gi; j < 7 * gi + 7 && j < 32; ++j) g |= (acc[j >> 4][j & 15] >= s.thr ? 1u : 0u) << (j - 7 * gi);
+                asm("" : "+v"(g));
+                s.mask |= g << (7 * gi);
+            };
+            // candidates of column tile ct -> this wave's queue, then the confirm of what is due
+            auto queue_confirm = [&](unsigned mask, int ct) __attribute__((always_inline)) {
+                // one candidate per lane and round (ballot / mbcnt compaction)
                 while (!undec) {
                     const bool has = mask != 0u;
                     const unsigned long long bal = __ballot(has);
@@ -218,7 +233,7 @@
                         mask &= mask - 1u;
                         const int row = 32 * (j >> 4) + (j & 3) + 8 * ((j & 15) >> 2) + 4 * (lane >> 5);
                         const int idx = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-                        scr_q[idx] = ((unsigned)row << 16) | (unsigned)(32 * ct + (lane & 31));
+                        scr_q[idx] = ((unsigned)row << 16) | (unsigned)(32 * ct + l31);
                     }
                     qn += n;
                 }
@@ -239,6 +254,60 @@
                     nconf += n;
                 }
                 __builtin_amdgcn_wave_barrier();
+            };
+            // one stage of the column-tile pipeline (r11): the MFMAs of column tile ct + 1 into accN, and in their issue
+            // shadow the select of column tile ct from accS, whose MFMAs were the stage before.  The select needs nothing of
+            // ct + 1.  Each k-block of ct + 1 (MFMA, the ring's request, MFMA: 64 matrix-pipe cycles, 16 VALU issue slots)
+            // is a scheduling region of its own together with one piece of the select -- left to one region of 16 MFMAs the
+            // scheduler packed the MFMAs and put the select behind them in some builds
+            auto stage = [&](f32x16 (&accN)[2], const f32x16 (&accS)[2], int ct, bool has_next) __attribute__((always_inline)) -> unsigned {
+                const int soff = soff0 + (ct + 1) * 8 * 1024;
+                Sel s;
+                s.mask = 0;
+#pragma unroll
+                for (int kb = 0; kb < 8; ++kb) {
+                    if (has_next) kblock(accN, soff, kb);
+                    if (scr_abl == 3) {          // MFMAs and their loads only: one value of each accumulator keeps them live
+                        if (kb == 0) keep = fmaxf(keep, accS[0][0] + accS[1][0]);
+                    } else if (kb == 0) sel_begin(s, accS, ct);
+                    else if (kb == 1) sel_threshold(s, accS, ct);
+                    else if (kb < 7) sel_group(s, accS, kb - 2);
+                    if (has_next) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                return s.mask & vmask;
+            };
+            // The order of events per column tile is the one the exactness argument uses: E read and select of ct, queue,
+            // confirm, and only then the select of ct + 1; only the MFMAs of ct + 1 have moved ahead of them, and they touch
+            // nothing the select, the queue or the confirm reads.  Two accumulator sets, the loop unrolled by two so that each
+            // has its registers; the last column tile has no MFMAs beside its select, and empties the queue as before
+            f32x16 accA[2], accB[2];
+#pragma unroll
+            for (int kb = 0; kb < 8; ++kb) {
+                kblock(accA, soff0, kb);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             }
+#pragma unroll 1
+            for (int ct = 0; ct < 8; ct += 2) {
+                unsigned mask = stage(accB, accA, ct, true);
+                if (scr_abl != 3) queue_confirm(mask, ct);
+                if (ct < 6) mask = stage(accA, accB, ct + 1, true);
+                else {
+                    // the next tile's point: requested here, where the second accumulator set is dead and its registers are
+                    // free (requested before the screen, its three registers were what spilled), it lands during the last
+                    // select, queue and confirm
+                    if (tile + 1 < ntiles) load_point(tile + 1, nx0, nx1, nx2);
+                    mask = stage(accA, accB, ct + 1, false);
+                }
+                if (scr_abl != 3) queue_confirm(mask, ct + 1);
+            }
+            if (scr_abl == 3) scr_E[lane] = __float_as_uint(keep);
             __syncthreads();          // fp16(h) lies over the next tile's first-layer output
 }
