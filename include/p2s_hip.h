@@ -87,7 +87,14 @@ typedef struct {
     int32_t sym_sum;             /* train --sym_op sum (reference source/points_to_surf_model.py:170-175,211-214; set by no
                                     experiment script): the pool of PointNetfeat is a SUM over the points instead of the
                                     max.  The STN / QSTN trunks keep their max-pool in the reference too (:47, :106)  */
-    int32_t reserved[3];
+    /* stem reuse (fp32 models with a screened conv3 and a max pool): the main encoder pass starts at conv1
+       from the conv0b output the STN pass saved in the workspace (16 KB per 64-point tile of a query).  Both took the place of
+       reserved slots: the size and the earlier members are unchanged, and zeros are the defaults */
+    int32_t stem_recompute;      /* 1: the main pass recomputes the stem, nothing is saved (the A/B switch) */
+    int32_t stem_reuse_max_mb;   /* cap of the saved stem in the workspace; 0: 3072 MB, which holds the 2688 MB of an 8192-query
+                                    chunk of 300 + 1000 points.  A chunk whose stem would be larger, or does not fit the
+                                    device, is reserved without it and recomputes */
+    int32_t reserved[1];
 } p2s_model_cfg;
 
 /* Offsets (in floats) into the weight blob.  The blob holds BatchNorm-folded fp32 weights,
@@ -770,7 +777,12 @@ typedef struct {
     int64_t conv3_items_dense;   /* items the screen could not decide (activation beyond the half range, ties beyond the
                                     candidate queue): run again through the dense conv3 inside the same kernel */
     int64_t conv3_items;         /* (query, encoder, pass) items that entered the screened kernel */
-    double  reserved[3];
+    /* stem reuse (fp32 models with a screened conv3 and a max pool): (query, encoder) items whose main
+       encoder pass started at conv1 from the conv0b output the STN pass had saved; 0 where the stem is recomputed
+       (p2s_model_cfg.stem_recompute, a chunk beyond stem_reuse_max_mb, P2S_CONV3_DENSE=1, every other mode).  Counted on the host at launch, in the place of
+       a reserved slot: the size and the earlier members are unchanged */
+    int64_t stem_items_reused;
+    double  reserved[2];
 } p2s_counters;
 int p2s_set_profiling(p2s_model_t m, int enabled);
 int p2s_get_counters(p2s_model_t m, p2s_counters *out);

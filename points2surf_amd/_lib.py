@@ -24,7 +24,7 @@ class Counters(ctypes.Structure):
                 ('queries', ctypes.c_int64), ('launches_chain', ctypes.c_int64),
                 ('ms_chain_qstn', ctypes.c_double), ('fallback_queries', ctypes.c_int64),
                 ('conv3_confirmed', ctypes.c_int64), ('conv3_items_dense', ctypes.c_int64), ('conv3_items', ctypes.c_int64),
-                ('reserved', ctypes.c_double * 3)]
+                ('stem_items_reused', ctypes.c_int64), ('reserved', ctypes.c_double * 2)]
 
 
 # name -> (restype, argtypes): every symbol include/p2s_hip.h declares

@@ -85,6 +85,11 @@ static int screen_init(p2s_model_s *m) {
         m->scr_w3h = nullptr;
         m->scr_mu = nullptr;
     }
+    // stem reuse: both passes of the model run the screened kernel (a sym_op='sum' main pass keeps the dense conv3).  The default
+    // cap holds the 2688 MB of an 8192-query chunk of 300 + 1000 points (21 tiles of 16 KB per query).  The switch and the cap
+    // are members of the configuration, not environment variables: the library keeps to its 20
+    m->stem_reuse = rc == P2S_OK && m->scr_w3h && !m->cfg.sym_sum && !m->cfg.stem_recompute;
+    m->stem_max_bytes = (size_t)(m->cfg.stem_reuse_max_mb > 0 ? m->cfg.stem_reuse_max_mb : 3072) << 20;
     return rc;
 }
 

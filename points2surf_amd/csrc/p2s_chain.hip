@@ -39,6 +39,7 @@ __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
 
 __device__ __forceinline__ f32x4 ldg4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
 __device__ __forceinline__ f32x4 lds4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
+typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 bufld4(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
@@ -48,16 +49,21 @@ __device__ __forceinline__ f32x4 bufld4(__amdgpu_buffer_rsrc_t rsrc, int voff, i
 }
 
 // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+// (b: the bias of the lane's column, bias[col0 + (lane & 31)])
 __device__ __forceinline__ void store_tile_bias_relu(const f32x16 &acc, float *dst, int stride, int row0,
-                                                     int col0, const float *__restrict__ bias, int lane) {
+                                                     int col0, float b, int lane) {
     const int col = col0 + (lane & 31);
-    const float b = bias[col];
     const int rbase = row0 + 4 * (lane >> 5);
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
         const int row = rbase + (reg & 3) + 8 * (reg >> 2);
         dst[row * stride + col] = fmaxf(acc[reg] + b, 0.0f);
     }
+}
+
+__device__ __forceinline__ void store_tile_bias_relu(const f32x16 &acc, float *dst, int stride, int row0,
+                                                     int col0, const float *__restrict__ bias, int lane) {
+    store_tile_bias_relu(acc, dst, stride, row0, col0, bias[col0 + (lane & 31)], lane);
 }
 
 __device__ __forceinline__ f32x16 zero16() {
@@ -110,6 +116,46 @@ __device__ __forceinline__ void layer_k64(const float *src, int ss, int row0, co
     }
 }
 
+// conv1 of the STN pass of a model that reuses the stem (ChainBranch.stem_out): layer_k64<1>, and the wave stores the A fragments
+// it has just read -- the conv0b output of its row tile, as conv1 of the main pass will want it -- one coalesced 1 KB store per
+// k-group.  The two waves of a row tile read the same fragments and share the eight stores: column tile NT writes k-groups
+// 4 NT .. 4 NT + 3.  soff: byte offset of (tile, row tile) in the item's stem
+template <int NT>
+__device__ __forceinline__ void layer_k64_store(const float *src, int ss, int row0, const B8 &b, int lane, f32x16 &acc,
+                                                __amdgpu_buffer_rsrc_t out, int lane16, int soff) {
+    const float *ap = src + (row0 + (lane & 31)) * ss + 4 * (lane >> 5);
+    f32x4 a = lds4(ap), na;
+#pragma unroll
+    for (int kg = 0; kg < 8; ++kg) {
+        if (kg < 7) na = lds4(ap + 8 * (kg + 1));
+        if ((kg >> 2) == NT) {
+            const u32x4s v = {__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]), __float_as_uint(a[3])};
+            __builtin_amdgcn_raw_buffer_store_b128(v, out, lane16, soff + kg * 1024, 0);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc = (kg == 0 && t == 0) ? mfma32(a[0], b.v[0][0], zero16()) : mfma32(a[t], b.v[kg][t], acc);
+        if (kg < 7) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            if ((kg >> 2) == NT) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            } else {
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            }
+            a = na;
+        }
+    }
+}
+// conv1 of the main pass of such a model: the A fragments come from registers (the stem the STN pass saved); the k order and the
+// accumulator chain are layer_k64's, so every value is the one conv1 computed from LDS
+__device__ __forceinline__ void layer_k64_regs(const B8 &a, const B8 &b, f32x16 &acc) {
+#pragma unroll
+    for (int kg = 0; kg < 8; ++kg)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc = (kg == 0 && t == 0) ? mfma32(a.v[0][0], b.v[0][0], zero16()) : mfma32(a.v[kg][t], b.v[kg][t], acc);
+}
 
 // max over the 32 accumulator values of one output column (two row tiles): 1 v_max + 15 v_max3.
 // Inline asm because fmaxf() on MFMA results makes hipcc prepend an sNaN-quieting v_max(x, x) to every
@@ -290,275 +336,21 @@ __device__ __forceinline__ void scr_confirm(unsigned entry, const float *hB, __a
 }
 
 // SCREEN (max pool, full chain only): conv3 through p2s_chain_screen.inl, two workgroups per CU (66 KB of LDS); an item the
-// screen cannot decide runs a second time with the dense conv3 below
+// screen cannot decide runs a second time with the dense conv3 below.  The body is p2s_chain_body.inl
 template <bool SUM, bool SCREEN = false>
 __global__ __launch_bounds__(256, SCREEN ? 2 : 3) void p2s_chain_kernel(ChainArgs args) {
-    static_assert(!(SUM && SCREEN), "the screen selects for a max");
-    float *smem;
-    if constexpr (SCREEN) {
-        extern __shared__ __attribute__((aligned(16))) float smem_screen[];
-        smem = smem_screen;
-    } else {
-        __shared__ __attribute__((aligned(16))) float smem_dense[MT * SA + MT * SB];
-        smem = smem_dense;
-    }
-    float *bufA = smem;
-    float *bufB = smem + MT * SA;
-
-    // (not const: the screened instantiation renews them per tile, below)
-    int tid = threadIdx.x;
-    int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    int item = blockIdx.x;
-    int bsel = 0;
-    if (item >= args.br[0].n_items) {
-        item -= args.br[0].n_items;
-        bsel = 1;
-    }
-    const ChainBranch &br = args.br[bsel];
-    const int P = br.P, P1 = br.P1;
-    const float *__restrict__ w0a = br.w0a;
-    const float *__restrict__ b0a = br.b0a;
-    const float *__restrict__ w1 = br.w1 + (long long)item * br.w1_item_stride;
-    const float *__restrict__ w3 = br.w3;
-    const bool short_chain = br.short_chain != 0;
-
-    float cx = 0.f, cy = 0.f, cz = 0.f;
-    if (br.center) {
-        cx = br.center[item * 3 + 0];
-        cy = br.center[item * 3 + 1];
-        cz = br.center[item * 3 + 2];
-    }
-    float R[9];
-    const bool has_rot = br.rot != nullptr;
-    if (has_rot) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) R[i] = br.rot[item * 9 + i];
-    }
-
-    // eight named scalars, not an array: the pair index pr is a run-time value, an indexed array would live in scratch
-    const float pool0 = SUM ? 0.0f : -INFINITY;
-    float rm0 = pool0, rm1 = pool0, rm2 = pool0, rm3 = pool0, rm4 = pool0, rm5 = pool0, rm6 = pool0, rm7 = pool0;
-    // torch's conv/ReLU/MaxPool propagate NaN (a non-finite coordinate poisons every channel of the
-    // item); v_max_f32 does not.  Track non-finite inputs and poison the pooled output instead.
-    bool bad = false;
-
-    // buffer descriptors of the layer weights (wave-uniform): SGPR base + scalar offset + 16 * lane
-    int lane16 = lane * 16;
-    const __amdgpu_buffer_rsrc_t rs0b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(br.w0b), 0, 4096 * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(w1), 0, 4096 * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(br.w2), 0, 8192 * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w3rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(w3), 0, 128 * 1024 * 4, 0x00020000);
-    // this wave's 8 conv3 column tiles start at byte offset wave * 8 * 16 KB of the packed weights
-    const int w3soff = wave * (8 * 16 * 1024);
-
-    // coordinates of this lane's point of a tile (all 4 waves load the same 64 points; L1/L2 hits);
-    // the next tile's point is fetched under conv3 of the current one
-    auto load_point = [&](int tile, float &x0, float &x1, float &x2) {
-        int p = tile * MT + lane;
-        if (p >= P) p = P - 1;
-        if (p < P1) {
-            const float *src = br.ptsA + ((long long)item * P1 + p) * 3;
-            x0 = src[0]; x1 = src[1]; x2 = src[2];
-        } else {
-            const float *src = br.ptsB + ((long long)item * (P - P1) + (p - P1)) * 3;
-            x0 = src[0] - cx; x1 = src[1] - cy; x2 = src[2] - cz;
-        }
-    };
-
-#ifdef P2S_DEV_ABLATE
-    const int ablate = args.ablate;   // timing-only variants (wrong results): tools/ablate.sh builds with -DP2S_DEV_ABLATE=<variant>
-    constexpr int scr_abl = P2S_DEV_ABLATE + 0;   // 3 .. 5, of the screened conv3, at compile time: its schedule stays the shipped one
-#else
-    constexpr int ablate = 0, scr_abl = 0;
-#endif
-    const int ntiles = (P + MT - 1) / MT;
-    float nx0, nx1, nx2;
-    // screened conv3: the state of p2s_chain_screen.inl
-    // the exact pool: float bits, held as the unsigned the confirm's integer atomics work on -- every access has that type
-    unsigned *scr_E = reinterpret_cast<unsigned *>(smem + SCR_OFF_E) + 256 * wave;
-    float *scr_red = smem + SCR_OFF_RED;
-    unsigned *scr_q = reinterpret_cast<unsigned *>(smem + SCR_OFF_Q) + SCR_QCAP * wave;
-    const float *__restrict__ scr_mu = args.w3mu[bsel];
-    const __amdgpu_buffer_rsrc_t rs3h = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(args.w3h[bsel]), 0,
-                                                                           (int)(P2S_SCR_PIECE * 2), 0x00020000);
-    // running maxima of the screen values of this wave's 256 columns and their margin coefficients: in LDS, so that the second
-    // accumulator set of the column-tile pipeline has their registers (lanes l and l ^ 32 hold and write the same value)
-    float *scr_R = smem + SCR_OFF_R + 256 * wave;
-    float *scr_mul = smem + SCR_OFF_MU + 256 * wave;
-    bool undec = false;                        // the screen cannot decide this item (wave-uniform)
-    float scr_Hsq = 0.0f;                      // largest squared row norm of the conv2 tiles of the item so far
-    int nconf = 0;                             // fp32 chains this wave ran
-    bool dense_pass = !SCREEN;
-    if constexpr (SCREEN) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            scr_E[64 * i + lane] = __float_as_uint(-INFINITY);
-            scr_R[64 * i + lane] = -INFINITY;
-            scr_mul[64 * i + lane] = scr_mu[256 * wave + 64 * i + lane];     // read by this wave only: no barrier
-        }
-    }
-    for (;;) {
-    load_point(0, nx0, nx1, nx2);
-    for (int tile = 0; tile < ntiles; ++tile) {
-      // screened kernel: the thread's index is made opaque at the top of every tile, so that the per-lane addresses of the tile's
-      // layers are built in the tile and are not kept in registers across the screen and its confirm (hoisted out of the
-      // item's loops they were what spilled: profiles/r10/kernel_resources.txt; tests/test_chain_kernel_resources.py holds the
-      // budget).  The values are the same; the other instantiations have no code here
-      if constexpr (SCREEN) {
-          asm volatile("" : "+v"(tid));
-          lane = tid & 63;
-          lane16 = lane * 16;
-      }
-      f32x4 bA0, bA1, aA0, aA1, bB0, bB1, aB0, aB1;   // conv3 operand register sets
-      if (ablate != 1) {
-        float x0 = nx0, x1 = nx1, x2 = nx2;
-        B8 wb;
-        if (!short_chain) load_b8(wb, rs0b, lane16, (wave & 1) * 8192);      // conv0b weights, in flight across the barrier
-        else load_b8(wb, rs2, lane16, wave * 8192);
-        if (has_rot) {
-            // spelled out, contraction off: left to the compiler, the choice of which products fuse differed between the
-            // instantiations of this kernel, and the screened and the dense conv3 must see the same points bit for bit.
-            // The pattern is the one the compiler had chosen for the dense kernel before (read off its disassembly: y0's
-            // third product is rounded on its own and added, y1 / y2 are two nested fma), so its results are unchanged
-#pragma clang fp contract(off)
-            const float y0 = __builtin_fmaf(R[0], x0, R[1] * x1) + R[2] * x2;
-            const float y1 = __builtin_fmaf(R[5], x2, __builtin_fmaf(R[3], x0, R[4] * x1));
-            const float y2 = __builtin_fmaf(R[8], x2, __builtin_fmaf(R[6], x0, R[7] * x1));
-            x0 = y0; x1 = y1; x2 = y2;
-        }
-        bad = bad || !(fabsf(x0) <= 3.0e38f) || !(fabsf(x1) <= 3.0e38f) || !(fabsf(x2) <= 3.0e38f);
-        // ---- first layer (K = 3) on the VALU: wave w produces channels [16w, 16w+16) -------------
-        {
-            float *dst = bufA + lane * SA + 16 * wave;
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) {
-                f32x4 v;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int o = 16 * wave + 4 * c4 + c;   // wave-uniform -> scalar loads
-                    float s = b0a[o];
-                    s = fmaf(w0a[o], x0, s);
-                    s = fmaf(w0a[64 + o], x1, s);
-                    s = fmaf(w0a[128 + o], x2, s);
-                    v[c] = fmaxf(s, 0.0f);
-                }
-                *reinterpret_cast<f32x4 *>(dst + 4 * c4) = v;
-            }
-        }
-        __syncthreads();   // bufA ready; every wave is past its conv3 reads of bufB (previous tile)
-
-        if (!short_chain) {
-            // ---- conv0b: bufA[64x64] -> bufB[:, 0:64] ; wave = (row tile, col tile) ---------------
-            {
-                const int rt = wave >> 1, nt = wave & 1;
-                f32x16 acc[1];
-                layer_k64<1>(bufA, SA, 32 * rt, wb, lane, acc);
-                load_b8(wb, rs1, lane16, nt * 8192);                           // conv1 weights
-                store_tile_bias_relu(acc[0], bufB, SB, 32 * rt, 32 * nt, br.b0b, lane);
-            }
-            __syncthreads();
-            // ---- conv1 (STN: shared weights; main: per-item W1' = W1 . trans2): bufB -> bufA ---------
-            {
-                const int rt = wave >> 1, nt = wave & 1;
-                f32x16 acc[1];
-                layer_k64<1>(bufB, SB, 32 * rt, wb, lane, acc);
-                load_b8(wb, rs2, lane16, wave * 8192);                         // conv2 weights
-                store_tile_bias_relu(acc[0], bufA, SA, 32 * rt, 32 * nt, br.b1, lane);
-            }
-            __syncthreads();
-        }
-        // ---- conv2: bufA[64x64] -> bufB[64x128]; wave w = column tile w, both row tiles --------------
-        {
-            f32x16 acc[2];
-            layer_k64<2>(bufA, SA, 0, wb, lane, acc);
-            // first conv3 weight fragments, in flight across the barrier (the screened kernel requests them in front of its
-            // dense conv3, below: requested here, their eight registers stayed reserved across the screen)
-            if constexpr (!SCREEN) {
-                bA0 = bufld4(w3rsrc, lane16, w3soff);
-                bA1 = bufld4(w3rsrc, lane16, w3soff + 16 * 1024);
-            }
-            store_tile_bias_relu(acc[0], bufB, SB, 0, 32 * wave, br.b2, lane);
-            store_tile_bias_relu(acc[1], bufB, SB, 32, 32 * wave, br.b2, lane);
-        }
-        __syncthreads();
-      } else {
-        bA0 = bufld4(w3rsrc, lane16, w3soff);
-        bA1 = bufld4(w3rsrc, lane16, w3soff + 16 * 1024);
-      }
-      if (ablate == 2) continue;
-      if constexpr (SCREEN) {
-        if (!dense_pass) {
-#include "p2s_chain_screen.inl"
-            // the screened pass never pools into rm0 .. rm7: saying so here keeps the eight registers from being carried
-            // through the screen for the dense pass that may follow
-            rm0 = rm1 = rm2 = rm3 = rm4 = rm5 = rm6 = rm7 = pool0;
-            continue;
-        }
-        bA0 = bufld4(w3rsrc, lane16, w3soff);
-        bA1 = bufld4(w3rsrc, lane16, w3soff + 16 * 1024);
-      }
-        // ---- conv3 (K = 128, N = 1024) + running max over points -----------------------------------
-        // wave w owns channels [256w, 256w+256) = 8 column tiles, processed as 4 pairs with a
-        // 2 (row tiles) x 2 (column tiles) register block: 64 accumulator registers.
-        // One continuous software pipeline over the 4 x 16 k-groups: two operand register sets (A/B)
-        // ping-pong, the operands of k-group g+1 are fetched while the 16 MFMAs of k-group g issue --
-        // across pair boundaries too -- and every memory instruction sits in its own MFMA shadow.
-        // P2S_TAIL (see mfma16b): the item's last tile with <= 48 points -- row tile 1 runs as 16 rows on the 4-block MFMA.
-        // sum pool: padded rows are masked per row of the 32x32 layout (tile_colsum) -- keeps the full tile
-        if (!SUM && tile == ntiles - 1 && P - tile * MT <= 48) {
-#define P2S_TAIL 1
-#include "p2s_chain_conv3.inl"
-#undef P2S_TAIL
-        } else {
-#define P2S_TAIL 0
-#include "p2s_chain_conv3.inl"
-#undef P2S_TAIL
-        }
-        // next tile's first layer writes bufA, whose last readers (conv2) are behind the barrier above
-    }
-    if constexpr (SCREEN) {
-        if (!dense_pass) {
-            // the item's verdict: one wave that could not decide sends the whole workgroup through the dense conv3
-            if (lane == 0) scr_red[4 + wave] = undec ? 1.0f : 0.0f;
-            __syncthreads();
-            const bool redo = (scr_red[4] + scr_red[5] + scr_red[6] + scr_red[7]) != 0.0f;
-            if (args.scr_counters) {
-                if (lane == 0 && !redo) atomicAdd(args.scr_counters + 0, (unsigned long long)nconf);
-                if (tid == 0) {
-                    atomicAdd(args.scr_counters + 2, 1ull);
-                    if (redo) atomicAdd(args.scr_counters + 1, 1ull);
-                }
-            }
-            if (redo) {
-                dense_pass = true;
-                continue;
-            }
-            __builtin_amdgcn_wave_barrier();
-            rm0 = __uint_as_float(scr_E[(lane & 31)]);       rm1 = __uint_as_float(scr_E[32 + (lane & 31)]);
-            rm2 = __uint_as_float(scr_E[64 + (lane & 31)]);  rm3 = __uint_as_float(scr_E[96 + (lane & 31)]);
-            rm4 = __uint_as_float(scr_E[128 + (lane & 31)]); rm5 = __uint_as_float(scr_E[160 + (lane & 31)]);
-            rm6 = __uint_as_float(scr_E[192 + (lane & 31)]); rm7 = __uint_as_float(scr_E[224 + (lane & 31)]);
-        }
-    }
-    break;
-    }
-
-    // ---- pooled affine epilogue: out = [relu](max + bias) ------------------------------------------
-    const bool any_bad = __ballot(bad) != 0ull;
-    if (lane < 32) {
-        float *out = br.out + (long long)item * 1024 + 256 * wave + lane;
-        const float *b3 = br.b3 + 256 * wave + lane;
-        const float rmax[8] = {rm0, rm1, rm2, rm3, rm4, rm5, rm6, rm7};
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            float v = rmax[t] + (SUM ? (float)P * b3[32 * t] : b3[32 * t]);     // sum: the bias once per point
-            if (br.relu_out) v = fmaxf(v, 0.0f);
-            if (any_bad) v = __builtin_nanf("");
-            out[32 * t] = v;
-        }
-    }
+    constexpr bool STEM_SAVE = false, STEM_LOAD = false;
+#include "p2s_chain_body.inl"
+}
+// the two passes of a model that reuses the stem, both screened with a max pool: the STN pass, whose conv1 stores its A
+// fragments to ChainBranch.stem_out, and the main pass, which starts at conv1 from ChainBranch.stem_in
+__global__ __launch_bounds__(256, 2) void p2s_chain_save_kernel(ChainArgs args) {
+    constexpr bool SUM = false, SCREEN = true, STEM_SAVE = true, STEM_LOAD = false;
+#include "p2s_chain_body.inl"
+}
+__global__ __launch_bounds__(256, 2) void p2s_chain_reuse_kernel(ChainArgs args) {
+    constexpr bool SUM = false, SCREEN = true, STEM_SAVE = false, STEM_LOAD = true;
+#include "p2s_chain_body.inl"
 }
 
 // W1'[o][j] = sum_i W1f[o][i] * T[i][j], emitted directly in packed B-fragment order.
@@ -646,20 +438,39 @@ int p2s_launch_chain(const ChainArgs &args_in, hipStream_t stream) {
             p2s_set_error("p2s_launch_chain: the screened conv3 takes full-chain max-pool passes with their screen operands");
             return P2S_EINVAL;
         }
-        // the kernel's LDS exceeds the default limit: raised once per device
-        static std::atomic<bool> lds_set[P2S_MAX_DEVICES];
+        // the saved stem: written by both branches of a launch, read by both, or neither (which: 0 neither, 1 written, 2 read)
+        const int which = args.br[0].stem_in ? 2 : args.br[0].stem_out ? 1 : 0;
+        for (int b = 0; b < 2; ++b) {
+            const ChainBranch &br = args.br[b];
+            if (br.n_items > 0 && ((br.stem_in ? 2 : br.stem_out ? 1 : 0) != which || (br.stem_in && br.stem_out) || (which && !br.stem_bad))) {
+                p2s_set_error("p2s_launch_chain: the saved stem is written, or read, by both branches of a launch, with their flags");
+                return P2S_EINVAL;
+            }
+        }
+        if (which && args.br[1].n_items <= 0) {
+            p2s_set_error("p2s_launch_chain: the saved stem belongs to launches of both branches");
+            return P2S_EINVAL;
+        }
+        // the kernels' LDS exceeds the default limit: raised once per device and kernel
+        static std::atomic<bool> lds_set[3][P2S_MAX_DEVICES];
+        const void *kernel = which == 2 ? (const void *)p2s_chain_reuse_kernel : which == 1 ? (const void *)p2s_chain_save_kernel
+                                                                                            : (const void *)p2s_chain_kernel<false, true>;
         int dev = 0;
         P2S_HIP_CHECK(hipGetDevice(&dev));
-        if (dev < 0 || dev >= P2S_MAX_DEVICES || !lds_set[dev].load()) {
-            const hipError_t attr = hipFuncSetAttribute((const void *)p2s_chain_kernel<false, true>,
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, SCR_LDS_FLOATS * 4);
+        if (dev < 0 || dev >= P2S_MAX_DEVICES || !lds_set[which][dev].load()) {
+            const hipError_t attr = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SCR_LDS_FLOATS * 4);
             if (attr != hipSuccess) {
                 p2s_set_error("p2s_launch_chain: %d bytes of LDS for the screened conv3 refused: %s", SCR_LDS_FLOATS * 4, hipGetErrorString(attr));
                 return P2S_EHIP;
             }
-            if (dev >= 0 && dev < P2S_MAX_DEVICES) lds_set[dev].store(true);
+            if (dev >= 0 && dev < P2S_MAX_DEVICES) lds_set[which][dev].store(true);
         }
-        hipLaunchKernelGGL((p2s_chain_kernel<false, true>), dim3(n), dim3(256), SCR_LDS_FLOATS * 4, stream, args);
+        if (which == 2) hipLaunchKernelGGL(p2s_chain_reuse_kernel, dim3(n), dim3(256), SCR_LDS_FLOATS * 4, stream, args);
+        else if (which == 1) hipLaunchKernelGGL(p2s_chain_save_kernel, dim3(n), dim3(256), SCR_LDS_FLOATS * 4, stream, args);
+        else hipLaunchKernelGGL((p2s_chain_kernel<false, true>), dim3(n), dim3(256), SCR_LDS_FLOATS * 4, stream, args);
+    } else if (args.br[0].stem_in || args.br[0].stem_out || args.br[1].stem_in || args.br[1].stem_out) {
+        p2s_set_error("p2s_launch_chain: only the screened conv3 saves or reuses the stem");
+        return P2S_EINVAL;
     } else if (sum)
         hipLaunchKernelGGL(p2s_chain_kernel<true>, dim3(n), dim3(256), padlds, stream, args);
     else

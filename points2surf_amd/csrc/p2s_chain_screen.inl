@@ -294,8 +294,9 @@
                 __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             }
+            // (STEM_LOAD: the last two column tiles stand behind the loop, below)
 #pragma unroll 1
-            for (int ct = 0; ct < 8; ct += 2) {
+            for (int ct = 0; ct < (STEM_LOAD ? 6 : 8); ct += 2) {
                 unsigned mask = stage(accB, accA, ct, true);
                 if (scr_abl != 3) queue_confirm(mask, ct);
                 if (ct < 6) mask = stage(accA, accB, ct + 1, true);
@@ -307,6 +308,17 @@
                     mask = stage(accA, accB, ct + 1, false);
                 }
                 if (scr_abl != 3) queue_confirm(mask, ct + 1);
+            }
+            if constexpr (STEM_LOAD) {
+                // What is requested for the next tile here is not three coordinates but the 32 registers of conv1's A
+                // fragments.  Requested inside the loop they would be allocated across all of it (a value defined in one
+                // iteration of a loop and used behind it lives through the loop); behind the loop they live from here, where the
+                // second accumulator set, the A fragments of the screen and the weight ring are dead, to the next tile's conv1
+                unsigned mask = stage(accB, accA, 6, true);
+                if (scr_abl != 3) queue_confirm(mask, 6);
+                if (tile + 1 < ntiles) load_point(tile + 1, nx0, nx1, nx2);
+                mask = stage(accA, accB, 7, false);
+                if (scr_abl != 3) queue_confirm(mask, 7);
             }
             if (scr_abl == 3) scr_E[lane] = __float_as_uint(keep);
             __syncthreads();          // fp16(h) lies over the next tile's first-layer output

@@ -73,6 +73,13 @@ struct ChainBranch {
     int relu_out;            // ReLU after the pooled affine (STN trunks) or not (PointNetfeat.conv3)
     int short_chain;         // 1: 3->64->128->1024 (QSTN trunk), 0: 3->64->64->64->128->1024
     int pool_sum;            // 1: the pool over the points is a SUM (sym_op='sum', main trunk only), out = sum + P * b3; 0: max
+    // stem reuse (fp32, screened, max pool): the conv0b output of every 64-point tile in the order conv1 reads
+    // it as its A operand, [n_items][tiles(P)][row tile 2][k-group 8][64 lanes][4].  stem_out: the STN pass writes it (NULL
+    // everywhere else); stem_in: the main pass starts at conv1 from it (both branches of a launch, or neither); stem_bad
+    // [n_items]: the item has a non-finite coordinate -- written with stem_out, read with stem_in (fmaxf hides a NaN in the stem)
+    float *stem_out;
+    const float *stem_in;
+    int *stem_bad;
 };
 struct ChainArgs {
     ChainBranch br[2];       // br[0] items come first in the grid

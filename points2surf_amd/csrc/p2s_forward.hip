@@ -11,10 +11,19 @@ namespace {
 struct Ws {
     float *g_stn, *h1, *h2, *T, *w1p, *feat, *d1, *d2, *d3, *qg, *qg2, *qh1, *qh2, *rot;
     unsigned short *w1h;     // W1' of both encoders as 16-bit fragments, per piece
+    // stem reuse: conv0b's output of every tile of both branches as conv1's A fragments, [branch][item][tile][rt 2][kg 8][lane 64][4]
+    // (branch 0 = the sub-sample, as in the launches), and the items' non-finite flags [2][C]
+    float *stem;
+    int *stem_bad;
     size_t floats;           // all of it
 };
 
-Ws carve(float *base, const p2s_model_cfg &cfg, Precision prec, int C) {       // base == NULL: the size alone
+constexpr size_t STEM_TILE = 4096;       // floats per 64-point tile
+size_t stem_tiles(int points) { return ((size_t)points + 63) / 64; }
+size_t stem_floats(const p2s_model_cfg &cfg, size_t C) { return C * (stem_tiles(cfg.points_per_patch) + stem_tiles(cfg.sub_sample_size)) * STEM_TILE; }
+
+// stem: the workspace holds the stem region (p2s_model_s.ws_stem; never with 16-bit pieces)
+Ws carve(float *base, const p2s_model_cfg &cfg, Precision prec, int C, bool stem) {       // base == NULL: the size alone
     Ws w;
     size_t at = 0;
     auto take = [&](size_t n, bool present = true) {        // an absent region: NULL, no room
@@ -35,6 +44,8 @@ Ws carve(float *base, const p2s_model_cfg &cfg, Precision prec, int C) {       /
     w.qh2 = take((size_t)C * 256, cfg.use_point_stn);
     w.rot = take((size_t)C * 16, cfg.use_point_stn);
     w.w1h = reinterpret_cast<unsigned short *>(take((size_t)C * 4096 * prec.pieces, prec.pieces != 0));
+    w.stem = take(stem_floats(cfg, C), stem);
+    w.stem_bad = reinterpret_cast<int *>(take((size_t)2 * C, stem));
     w.floats = at;
     return w;
 }
@@ -67,6 +78,13 @@ void fill_branch(ChainBranch &b, const Chunk &c, Pass pass, int e) {
     b.relu_out = pass != PASS_MAIN;
     b.short_chain = pass == PASS_QSTN;
     b.pool_sum = pass == PASS_MAIN && m->cfg.sym_sum;        // sym_op='sum': PointNetfeat's pool only (the STN / QSTN trunks keep the max)
+    // stem reuse: the STN pass saves what the main pass starts from (branch 0 of the region = the sub-sample, e = 1)
+    b.stem_out = nullptr; b.stem_in = nullptr; b.stem_bad = nullptr;
+    if (c.w.stem && pass != PASS_QSTN) {
+        float *stem = c.w.stem + (e == 1 ? 0 : C * stem_tiles(m->cfg.sub_sample_size) * STEM_TILE);
+        if (pass == PASS_STN) b.stem_out = stem; else b.stem_in = stem;
+        b.stem_bad = c.w.stem_bad + (e == 1 ? 0 : C);
+    }
     const P2sLayer l2 = pass == PASS_QSTN ? L_QC2 : pass == PASS_STN ? L_S2 : L_M2;       // the 64 -> 128 -> 1024 end of the pass
     const P2sLayer l3 = pass == PASS_QSTN ? L_QC3 : pass == PASS_STN ? L_S3 : L_M3;
     const int z = pass == PASS_QSTN ? 0 : e;
@@ -83,7 +101,7 @@ void fill_branch(ChainBranch &b, const Chunk &c, Pass pass, int e) {
     if (pass == PASS_STN) {         // stem + STN trunk
         b.w1 = chain_operand(c, L_S1, e); b.b1 = m->bias(L_S1, e); b.w1_item_stride = 0;
         b.out = c.w.g_stn + e * C * 1024;
-    } else {                        // stem (recomputed) + the item's own W1' + conv2 + conv3
+    } else {                        // stem (recomputed, or read from stem_in) + the item's own W1' + conv2 + conv3
         b.w1 = c.prec.pieces ? chain_operand(c.w.w1h + e * C * 4096) : c.w.w1p + e * C * 4096;
         b.b1 = W + eo.mb1; b.w1_item_stride = 4096;
         b.out = c.w.feat + e * C * 1024;
@@ -144,8 +162,17 @@ int p2s_model_reserve(p2s_model_s *m, int chunk) {
         m->ws = nullptr;
         m->ws_chunk = 0;
     }
-    const size_t n = carve(nullptr, m->cfg, p2s_precision(m->cfg), 1).floats * (size_t)chunk;
-    hipError_t e = hipMalloc(&m->ws, n * sizeof(float));
+    const Precision prec = p2s_precision(m->cfg);
+    const size_t n = carve(nullptr, m->cfg, prec, 1, false).floats * (size_t)chunk;
+    hipError_t e = hipErrorOutOfMemory;
+    m->ws_stem = false;
+    if (m->stem_reuse && !prec.pieces && stem_floats(m->cfg, chunk) * sizeof(float) <= m->stem_max_bytes) {
+        // with the stem region where it is allowed and fits the device; a chunk that does not get it recomputes the stem
+        e = hipMalloc(&m->ws, carve(nullptr, m->cfg, prec, 1, true).floats * (size_t)chunk * sizeof(float));
+        m->ws_stem = e == hipSuccess;
+        if (e != hipSuccess) (void)hipGetLastError();
+    }
+    if (e != hipSuccess) e = hipMalloc(&m->ws, n * sizeof(float));
     if (e != hipSuccess) {
         p2s_set_error("hipMalloc(workspace %zu MB) failed: %s", n * 4 >> 20, hipGetErrorString(e));
         return P2S_ENOMEM;
@@ -200,7 +227,7 @@ int p2s_run_chunk(p2s_model_s *m, Precision prec, const float *patch, const floa
                   hipStream_t s, long long index0) {
     const p2s_weight_offsets &o = m->offs;
     const float *W = m->blob;
-    Chunk c = {m, prec, patch, sub, query, nullptr, C, carve(m->ws, m->cfg, prec, C)};
+    Chunk c = {m, prec, patch, sub, query, nullptr, C, carve(m->ws, m->cfg, prec, C, m->ws_stem && !prec.pieces)};
     const Ws &w = c.w;
     int rc;
     const int ev0 = p2s_prof_mark(m, s);
@@ -268,11 +295,12 @@ int p2s_run_chunk(p2s_model_s *m, Precision prec, const float *patch, const floa
     if ((rc = p2s_launch_fold(f, s))) return rc;
     const int ev2 = p2s_prof_mark(m, s);
 
-    // ---- pass 2: stem (recomputed) + transformed conv1 + conv2 + conv3 + max-pool -------------------
+    // ---- pass 2: stem (recomputed, or the one pass 1 saved) + transformed conv1 + conv2 + conv3 + max-pool ---
     for (int slot = 0; slot < 2; ++slot) fill_branch(a.br[slot], c, PASS_MAIN, 1 - slot);
     if ((rc = launch_chain(a, c, s, PASS_MAIN))) return rc;
     const int ev3 = p2s_prof_mark(m, s);
     m->counters.launches_chain += 2;
+    if (w.stem) m->counters.stem_items_reused += 2 * (int64_t)C;
 
     if (feat_local_out) P2S_HIP_CHECK(hipMemcpyAsync(feat_local_out, w.feat, (size_t)C * 1024 * 4, hipMemcpyDeviceToDevice, s));
     if (feat_global_out)
@@ -320,7 +348,7 @@ extern "C" int p2s_debug_stn_pool(p2s_model_t m, int n_queries, float *out_dev, 
         return P2S_EINVAL;
     }
     P2S_HIP_CHECK(hipSetDevice(m->device));
-    const Ws w = carve(m->ws, m->cfg, p2s_precision(m->cfg), n_queries);
+    const Ws w = carve(m->ws, m->cfg, p2s_precision(m->cfg), n_queries, false);       // (g_stn comes first)
     P2S_HIP_CHECK(hipMemcpyAsync(out_dev, w.g_stn, (size_t)2 * n_queries * 1024 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return P2S_OK;
 }

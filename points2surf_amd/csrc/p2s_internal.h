@@ -104,6 +104,14 @@ struct p2s_model_s {
     int64_t logits_capacity = 0;
     float *ws = nullptr;      // per-chunk workspace, grown on demand
     int ws_chunk = 0;
+    // stem reuse: the main encoder pass starts at conv1 from the conv0b output the STN pass saved in the
+    // workspace.  Decided once, at creation: the model's own precision is fp32, its conv3 is screened and its main pass pools by
+    // max (cfg.stem_recompute switches it off) -- not per run: the fp32 fall-back of an fp16 pair model runs inside that model's
+    // 16-bit workspace.  stem_max_bytes (cfg.stem_reuse_max_mb): a chunk whose region would be larger, or does not fit the
+    // device, is reserved without it (ws_stem) and recomputes the stem
+    bool stem_reuse = false;
+    size_t stem_max_bytes = 0;
+    bool ws_stem = false;
     int max_chunk = 8192;     // queries per internal batch (r03: 4096 -> 8192: 180.4 -> 182.0 k queries/s, the launch boundaries
                               // of a chunk -- four drains of the chip -- weigh half as much; 12288: 182.1 k)
     // profiling: HIP events recorded on the launch stream, no host synchronisation until collect

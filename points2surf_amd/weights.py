@@ -47,7 +47,8 @@ class ModelCfg(ctypes.Structure):
                 ('use_point_stn', ctypes.c_int32), ('shared_transformer', ctypes.c_int32),
                 ('weighted_subsample', ctypes.c_int32), ('encoder_bf16', ctypes.c_int32),
                 ('fixed_subsample', ctypes.c_int32), ('single_transformer', ctypes.c_int32),
-                ('patch_radius', ctypes.c_double), ('sym_sum', ctypes.c_int32), ('reserved', ctypes.c_int32 * 3)]
+                ('patch_radius', ctypes.c_double), ('sym_sum', ctypes.c_int32),
+                ('stem_recompute', ctypes.c_int32), ('stem_reuse_max_mb', ctypes.c_int32), ('reserved', ctypes.c_int32 * 1)]
 
 
 def _np(v):
@@ -273,6 +274,8 @@ def build_blob(state_dict, cfg):
     mc.single_transformer = int(single)
     mc.sym_sum = int(sym_op == 'sum')
     mc.patch_radius = max(float(cfg.get('patch_radius', 0.0) or 0.0), 0.0)     # the float64 of the reference's Python float
+    mc.stem_recompute = int(not bool(cfg.get('stem_reuse', True)))      # stem reuse of the fp32 encoders: on
+    mc.stem_reuse_max_mb = int(cfg.get('stem_reuse_max_mb', 0) or 0)    # 0: the default cap
     mc.encoder_bf16 = int(cfg.get('encoder_bf16', 0) or 0)      # 0 fp32, 1 bf16, 2 / 3 split bf16 (pieces per operand), 4 fp16 pair
     if mc.output_dim not in (1, 2):
         raise ValueError('engine supports outputs imp_surf (pred_dim 1) or imp_surf_magnitude + imp_surf_sign (pred_dim 2)')
