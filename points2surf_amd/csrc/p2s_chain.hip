@@ -428,7 +428,7 @@ int p2s_launch_chain(const ChainArgs &args_in, hipStream_t stream) {
     ChainArgs args = args_in;
     constexpr int padlds = 0;
 #ifdef P2S_DEV_ABLATE
-    args.ablate = P2S_DEV_ABLATE + 0;      // the variant is the value of the define (1 = conv3 only, 2 = all but conv3, 3 .. 5 = parts of the screen)
+    args.ablate = P2S_DEV_ABLATE + 0;      // the variant is the value of the define (1 = conv3 only, 2 = all but conv3, 3 .. 5, 7, 8 = parts of the screen)
 #endif
     // both branches of a launch pool alike (pass 2 of a sym_op='sum' model: sum; every other launch: max)
     const bool sum = args.br[0].pool_sum || (args.br[1].n_items > 0 && args.br[1].pool_sum);

@@ -106,7 +106,7 @@
 
 #ifdef P2S_DEV_ABLATE
     const int ablate = args.ablate;   // timing-only variants (wrong results): tools/ablate.sh builds with -DP2S_DEV_ABLATE=<variant>
-    constexpr int scr_abl = P2S_DEV_ABLATE + 0;   // 3 .. 5, of the screened conv3, at compile time: its schedule stays the shipped one
+    constexpr int scr_abl = P2S_DEV_ABLATE + 0;   // 3 .. 5, 7, 8, of the screened conv3, at compile time: its schedule stays the shipped one
 #else
     constexpr int ablate = 0, scr_abl = 0;
 #endif

@@ -90,9 +90,9 @@
 // requests (7 KB per wave) in flight: k-block j + 7 is requested between the two MFMAs of k-block j, across the select, the
 // queue and the confirm of a column tile too.
 // The column tiles are a pipeline two deep (r11): the 16 MFMAs of column tile ct + 1 go into a second accumulator set and the
-// select of column tile ct (column maximum, record, threshold, 32 compares, mask: about 130 VALU instructions, which read the
+// select of column tile ct (column maximum, record, threshold, 32 compares, mask: about 100 VALU instructions, which read the
 // first set only) is issued between them; then come the queue and the confirm of ct, as before.  The 32 registers of the
-// second set are the 24 that held `1 << j` for the mask (now built in groups of 7 rows from inline constants), the 8 running
+// second set are the 24 that held `1 << j` for the mask (now shifted in row by row through the carry: sel_rows3), the 8 running
 // maxima R (now in LDS beside E, like the margin coefficients, which were a global load with a full drain per column tile)
 // and 16 that the dense pass had reserved across the screen (profiles/r11/kernel_resources.txt).
 {
@@ -158,7 +158,8 @@
             }
             int qn = 0;                                                          // entries in this wave's queue (wave-uniform)
             const int l31 = lane & 31;
-            float keep = -INFINITY;                                              // (development variant 3 only)
+            float keep = -INFINITY;                                              // (development variants 3 and 8 only)
+            unsigned keepm = 0;                                                  // (development variants 7 and 8 only)
             // k-block kb of one column tile into `acc`: the two row tiles alternate so that no MFMA follows the one it depends
             // on, the ring's request sits between them (the callers' sched_group_barriers say where)
             auto kblock = [&](f32x16 (&acc)[2], int soff, int kb) __attribute__((always_inline)) {
@@ -173,13 +174,18 @@
                 }
             };
             // The select of column tile ct from its finished accumulators, in the pieces the pipeline places: the column
-            // maximum of row tile 0, then that of row tile 1 and the threshold, then the mask in five groups of rows.
+            // maximum of row tile 0, then that of row tile 1 and the threshold, then the mask in six pieces of rows.
             struct Sel {
-                float mu, Ec, Rold, m, thr;
+                float mul, Ec, Rold, m, thr;
                 unsigned mask;
             };
+            // The three LDS reads (mu's coefficient, E, R) are requested in the stage's first k-block and nothing of that k-block
+            // uses them: their first use is the threshold, one k-block -- two MFMAs -- later (until r13 the product mul * Heff
+            // was taken here, and the wait for the reads stood behind the eight v_max of this piece).  Requested a whole column
+            // tile ahead, in the stage of ct - 1, the values live across the queue and the confirm, and the save kernel and
+            // p2s_chain_kernel<false, true> spill 4 and 2 VGPRs (with two of the three carried as with all three): not built
             auto sel_begin = [&](Sel &s, const f32x16 (&acc)[2], int ct) __attribute__((always_inline)) {
-                s.mu = scr_mul[32 * ct + l31] * Heff;
+                s.mul = scr_mul[32 * ct + l31];
                 // the exact pool of this lane's channel over the EARLIER tiles: candidates of this column tile are queued
                 // after this and confirmed after that, and every batch of an earlier tile has run (ct == 7 empties the queue);
                 // scr_E of a wave is written by that wave's own confirms only, the wave barriers order them before this read
@@ -205,21 +211,62 @@
                 const float R = fmaxf(s.Rold, m);
                 scr_R[32 * ct + l31] = R;
                 // -inf (nothing confirmed yet) leaves the R rule; fmaxf drops a NaN operand, so a NaN in E dismisses nothing
-                s.thr = fmaxf(R - s.mu, s.Ec - 0.5f * s.mu);
+                const float mu = s.mul * Heff;
+                s.thr = fmaxf(R - mu, s.Ec - 0.5f * mu);
             };
-            // rows 7 gi .. 7 gi + 6 of the mask: 1 << 0 .. 1 << 6 are inline constants of v_cndmask, so no register holds a
-            // 1 << j (24 did); the group is made opaque before its shift, or the shift is folded back into the constants
+            // The mask, two VALU instructions per row (r13): the rows are taken from 31 down to 0, each compares into a carry
+            // register and `mask = mask + mask + carry` shifts it in, so row j ends at bit j, as the queue decodes it.
+            // v_cmp_ge_f32 is the compare the C++ `>=` compiled to: false on a NaN.  A VALU read of a carry a VALU instruction
+            // wrote needs two wait states on gfx950, and the compiler pads nothing inside an asm: three carry registers (VCC
+            // and two SGPR pairs) rotate so that two other instructions of the group always stand between a compare and the
+            // add that reads it, and no s_nop is needed.  The adds' own carry-outs (always 0: 32 shifts of a mask that starts
+            // at 0) go to the register just read, which is dead.  Plain asm in groups of three and five rows, not volatile
+            // and not one block: the pipeline places one piece per k-block between the MFMAs (a volatile asm is pinned)
+            auto sel_rows3 = [&](Sel &s, float a2, float a1, float a0) __attribute__((always_inline)) {
+                unsigned long long c0, c1;
+                asm("v_cmp_ge_f32_e32 vcc, %3, %6\n\t"
+                    "v_cmp_ge_f32_e64 %1, %4, %6\n\t"
+                    "v_cmp_ge_f32_e64 %2, %5, %6\n\t"
+                    "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
+                    "v_addc_co_u32_e64 %0, %1, %0, %0, %1\n\t"
+                    "v_addc_co_u32_e64 %0, %2, %0, %0, %2"
+                    : "+v"(s.mask), "=&s"(c0), "=&s"(c1)
+                    : "v"(a2), "v"(a1), "v"(a0), "v"(s.thr)
+                    : "vcc");
+            };
+            auto sel_rows5 = [&](Sel &s, float a4, float a3, float a2, float a1, float a0) __attribute__((always_inline)) {
+                unsigned long long c0, c1;
+                asm("v_cmp_ge_f32_e32 vcc, %3, %8\n\t"
+                    "v_cmp_ge_f32_e64 %1, %4, %8\n\t"
+                    "v_cmp_ge_f32_e64 %2, %5, %8\n\t"
+                    "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
+                    "v_cmp_ge_f32_e32 vcc, %6, %8\n\t"
+                    "v_addc_co_u32_e64 %0, %1, %0, %0, %1\n\t"
+                    "v_cmp_ge_f32_e64 %1, %7, %8\n\t"
+                    "v_addc_co_u32_e64 %0, %2, %0, %0, %2\n\t"
+                    "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
+                    "v_addc_co_u32_e64 %0, %1, %0, %0, %1"
+                    : "+v"(s.mask), "=&s"(c0), "=&s"(c1)
+                    : "v"(a4), "v"(a3), "v"(a2), "v"(a1), "v"(a0), "v"(s.thr)
+                    : "vcc");
+            };
+            // piece gi of the mask, one per k-block 2 .. 7 of a stage: rows 31 .. 26, 25 .. 20, then four times five rows
             auto sel_group = [&](Sel &s, const f32x16 (&acc)[2], int gi) __attribute__((always_inline)) {
-                unsigned g = 0;
-#pragma unroll
-                for (int j = 7 * gi; j < 7 * gi + 7 && j < 32; ++j) g |= (acc[j >> 4][j & 15] >= s.thr ? 1u : 0u) << (j - 7 * gi);
-                asm("" : "+v"(g));
-                s.mask |= g << (7 * gi);
+                auto a = [&](int j) __attribute__((always_inline)) { return acc[j >> 4][j & 15]; };
+                if (gi < 2) {
+                    const int hi = 31 - 6 * gi;
+                    sel_rows3(s, a(hi), a(hi - 1), a(hi - 2));
+                    sel_rows3(s, a(hi - 3), a(hi - 4), a(hi - 5));
+                } else {
+                    const int hi = 19 - 5 * (gi - 2);
+                    sel_rows5(s, a(hi), a(hi - 1), a(hi - 2), a(hi - 3), a(hi - 4));
+                }
             };
             // candidates of column tile ct -> this wave's queue, then the confirm of what is due
             auto queue_confirm = [&](unsigned mask, int ct) __attribute__((always_inline)) {
                 // one candidate per lane and round (ballot / mbcnt compaction)
-                while (!undec) {
+                if (scr_abl == 7 || scr_abl == 8) keepm |= mask; // the select alone: no queue (one use keeps the mask), no confirm
+                else while (!undec) {
                     const bool has = mask != 0u;
                     const unsigned long long bal = __ballot(has);
                     if (bal == 0ull) break;
@@ -270,8 +317,10 @@
                     if (scr_abl == 3) {          // MFMAs and their loads only: one value of each accumulator keeps them live
                         if (kb == 0) keep = fmaxf(keep, accS[0][0] + accS[1][0]);
                     } else if (kb == 0) sel_begin(s, accS, ct);
-                    else if (kb == 1) sel_threshold(s, accS, ct);
-                    else if (kb < 7) sel_group(s, accS, kb - 2);
+                    else if (kb == 1) {
+                        sel_threshold(s, accS, ct);
+                        if (scr_abl == 8) keep = fmaxf(keep, s.thr); // the select without its mask: one use keeps the threshold
+                    } else if (scr_abl != 8) sel_group(s, accS, kb - 2);
                     if (has_next) {
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
@@ -321,5 +370,6 @@
                 if (scr_abl != 3) queue_confirm(mask, 7);
             }
             if (scr_abl == 3) scr_E[lane] = __float_as_uint(keep);
+            if (scr_abl == 7 || scr_abl == 8) scr_q[lane] = keepm ^ __float_as_uint(keep);
             __syncthreads();          // fp16(h) lies over the next tile's first-layer output
 }

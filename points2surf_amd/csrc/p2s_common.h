@@ -83,7 +83,7 @@ struct ChainBranch {
 };
 struct ChainArgs {
     ChainBranch br[2];       // br[0] items come first in the grid
-    int ablate;              // only read when built with -DP2S_DEV_ABLATE (timing variants: 1 = conv3 only, 2 = all but conv3; 3 .. 5: p2s_chain_screen.inl)
+    int ablate;              // only read when built with -DP2S_DEV_ABLATE (timing variants: 1 = conv3 only, 2 = all but conv3; 3 .. 5, 7, 8: p2s_chain_screen.inl)
     // bf16 kernels: number of bf16 pieces per operand (1 = plain bf16, 2 / 3 = split precision) and the distance in
     // halfs between the pieces of a weight array (shared weights / per-item W1')
     int ns;
