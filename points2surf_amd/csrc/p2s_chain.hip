@@ -85,9 +85,14 @@ __device__ __forceinline__ void load_b8(B8 &b, __amdgpu_buffer_rsrc_t rsrc, int 
 
 // one K=64 layer: RT row tiles (rows row0 + 32 r) x one 32-column tile; A from LDS one k-group ahead, each
 // ds_read in its own MFMA shadow; the first k-group accumulates into the literal 0 (no v_mov init)
-template <int RT>
-__device__ __forceinline__ void layer_k64(const float *src, int ss, int row0, const B8 &b, int lane,
-                                          f32x16 (&acc)[RT]) {
+// NEXT: the registers of a k-group's weights take the same k-group of the NEXT layer's weights (nrs, byte offset nsoff) as soon
+// as the k-group's MFMAs have issued: the request has the rest of this layer, its epilogue and a barrier to come back.
+// The fences keep the order written here.  Left to itself the scheduler moved every ds_read directly in front of the four
+// MFMAs that use it (one full lgkmcnt(0) per k-group, the row tiles one after the other); with the fences alone the next
+// layer's weights, which it had hoisted into this layer's MFMAs, were requested behind the layer's last MFMA
+template <int RT, bool NEXT>
+__device__ __forceinline__ void layer_k64(const float *src, int ss, int row0, B8 &b, int lane, f32x16 (&acc)[RT],
+                                          __amdgpu_buffer_rsrc_t nrs, int lane16, int nsoff) {
     const float *ap = src + (row0 + (lane & 31)) * ss + 4 * (lane >> 5);
     f32x4 a[RT], na[RT];
 #pragma unroll
@@ -98,11 +103,14 @@ __device__ __forceinline__ void layer_k64(const float *src, int ss, int row0, co
 #pragma unroll
             for (int r = 0; r < RT; ++r) na[r] = lds4(ap + 32 * r * ss + 8 * (kg + 1));
         }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int r = 0; r < RT; ++r)
                 acc[r] = (kg == 0 && t == 0) ? mfma32(a[r][0], b.v[0][0], zero16()) : mfma32(a[r][t], b.v[kg][t], acc[r]);
+        if constexpr (NEXT) b.v[kg] = bufld4(nrs, lane16, nsoff + kg * 1024);
+        __builtin_amdgcn_sched_barrier(0);
         if (kg < 7) {
 #pragma unroll
             for (int r = 0; r < RT; ++r) {
@@ -114,6 +122,11 @@ __device__ __forceinline__ void layer_k64(const float *src, int ss, int row0, co
             for (int r = 0; r < RT; ++r) a[r] = na[r];
         }
     }
+}
+
+template <int RT>
+__device__ __forceinline__ void layer_k64(const float *src, int ss, int row0, B8 &b, int lane, f32x16 (&acc)[RT]) {
+    layer_k64<RT, false>(src, ss, row0, b, lane, acc, __builtin_amdgcn_make_buffer_rsrc((float *)nullptr, 0, 0, 0x00020000), 0, 0);
 }
 
 // conv1 of the STN pass of a model that reuses the stem (ChainBranch.stem_out): layer_k64<1>, and the wave stores the A fragments
@@ -149,12 +162,16 @@ __device__ __forceinline__ void layer_k64_store(const float *src, int ss, int ro
     }
 }
 // conv1 of the main pass of such a model: the A fragments come from registers (the stem the STN pass saved); the k order and the
-// accumulator chain are layer_k64's, so every value is the one conv1 computed from LDS
-__device__ __forceinline__ void layer_k64_regs(const B8 &a, const B8 &b, f32x16 &acc) {
+// accumulator chain are layer_k64's, so every value is the one conv1 computed from LDS.  The next layer's weights follow every
+// k-group as in layer_k64<RT, true>
+__device__ __forceinline__ void layer_k64_regs(const B8 &a, B8 &b, f32x16 &acc, __amdgpu_buffer_rsrc_t nrs, int lane16, int nsoff) {
 #pragma unroll
-    for (int kg = 0; kg < 8; ++kg)
+    for (int kg = 0; kg < 8; ++kg) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc = (kg == 0 && t == 0) ? mfma32(a.v[0][0], b.v[0][0], zero16()) : mfma32(a.v[kg][t], b.v[kg][t], acc);
+        b.v[kg] = bufld4(nrs, lane16, nsoff + kg * 1024);
+        __builtin_amdgcn_sched_barrier(0);
+    }
 }
 
 // max over the 32 accumulator values of one output column (two row tiles): 1 v_max + 15 v_max3.
@@ -261,13 +278,14 @@ constexpr int SCR_HB = 128 + 8;      // halfs per row of the fp16 copy of the co
 constexpr int SCR_QCAP = 256;        // candidates a wave's queue holds: < 64 left over + what one column tile may add
 constexpr float P2S_SCR_KAPPA = 0x1.1p-10f;   // k_screen + k_fp32 of the margin (derived in p2s_chain_screen.inl)
 // LDS of the screened kernel (floats): the two fp32 tiles (the fp16 copy of h lies over bufA), the exact pool E [1024], the four
-// waves' candidate queues, the reduction scratch, the running screen maxima and the margin coefficients (66 KB in all)
+// waves' candidate queues, the reduction scratch, the running screen maxima, the margin coefficients and conv0a's operands (67 KB in all)
 constexpr int SCR_OFF_E = MT * SA + MT * SB;
 constexpr int SCR_OFF_Q = SCR_OFF_E + 1024;
 constexpr int SCR_OFF_RED = SCR_OFF_Q + 4 * SCR_QCAP;
 constexpr int SCR_OFF_R = SCR_OFF_RED + 8;            // running screen maxima R [1024] (r11: out of the registers)
 constexpr int SCR_OFF_MU = SCR_OFF_R + 1024;          // margin coefficients [1024], copied once per workgroup
-constexpr int SCR_LDS_FLOATS = SCR_OFF_MU + 1024;
+constexpr int SCR_OFF_W0 = SCR_OFF_MU + 1024;         // conv0a's weights [3][64] and biases [64], copied once per workgroup
+constexpr int SCR_LDS_FLOATS = SCR_OFF_W0 + 256;
 static_assert(MT * SCR_HB * 2 <= MT * SA * 4, "the fp16 copy fits the 64-channel tile it lies over");
 static_assert(2 * SCR_LDS_FLOATS * 4 <= 160 * 1024, "two workgroups per CU");
 

@@ -134,7 +134,16 @@
             scr_R[64 * i + lane] = -INFINITY;
             scr_mul[64 * i + lane] = scr_mu[256 * wave + 64 * i + lane];     // read by this wave only: no barrier
         }
+        if constexpr (!STEM_LOAD) {
+            // conv0a's 256 operands are the launch's: from LDS a tile reads them in a few cycles, where its 16 vector loads were
+            // a trip to L2 in front of the tile's first fma (the screen's weight ring leaves nothing of them in L1)
+            smem[SCR_OFF_W0 + tid] = tid < 192 ? w0a[tid] : b0a[tid - 192];
+            __syncthreads();
+        }
     }
+    const float *w0lds = smem + (SCREEN ? SCR_OFF_W0 : 0);
+    auto conv0a_w = [&](int i) { return SCREEN ? w0lds[i] : w0a[i]; };
+    auto conv0a_b = [&](int o) { return SCREEN ? w0lds[192 + o] : b0a[o]; };
     for (;;) {
     load_point(0, nx0, nx1, nx2);
     for (int tile = 0; tile < ntiles; ++tile) {
@@ -151,30 +160,44 @@
       if (STEM_LOAD && ablate != 1) {
         // ---- conv1 from the saved stem: registers -> bufA (free: the screen ends with a barrier behind its last read of
         // fp16(h), the dense conv3 reads bufB); the barrier behind it also puts every wave past its conv3 reads of bufB
+        // A layer's bias is requested with its weights, in front of its MFMAs: requested by the epilogue it was a trip to
+        // the argument block and one to L1/L2, both waited for in full behind the layer's last MFMA.  The fences keep all
+        // eight requests of W1' in front of conv1's first MFMA (per item: the screen's weight ring has pushed it out of L1);
+        // left alone, the scheduler requested one fragment per k-group and waited for it in front of the k-group's MFMAs
         B8 wb;
         load_b8(wb, rs1, lane16, (wave & 1) * 8192);
+        __builtin_amdgcn_sched_barrier(0);         // (the bias behind W1': its pointer is a trip to the argument block)
+        const float bias1 = br.b1[32 * (wave & 1) + (lane & 31)];
+        __builtin_amdgcn_sched_barrier(0);
+        float bias2;
         {
             const int rt = wave >> 1, nt = wave & 1;
             f32x16 acc;
-            layer_k64_regs(sf, wb, acc);
-            load_b8(wb, rs2, lane16, wave * 8192);                         // conv2 weights
-            store_tile_bias_relu(acc, bufA, SA, 32 * rt, 32 * nt, br.b1, lane);
+            layer_k64_regs(sf, wb, acc, rs2, lane16, wave * 8192);         // (and the conv2 weights)
+            bias2 = br.b2[32 * wave + (lane & 31)];
+            store_tile_bias_relu(acc, bufA, SA, 32 * rt, 32 * nt, bias1, lane);
         }
         __syncthreads();
         {
             f32x16 acc[2];
             layer_k64<2>(bufA, SA, 0, wb, lane, acc);
-            store_tile_bias_relu(acc[0], bufB, SB, 0, 32 * wave, br.b2, lane);
-            store_tile_bias_relu(acc[1], bufB, SB, 32, 32 * wave, br.b2, lane);
+            store_tile_bias_relu(acc[0], bufB, SB, 0, 32 * wave, bias2, lane);
+            store_tile_bias_relu(acc[1], bufB, SB, 32, 32 * wave, bias2, lane);
         }
         __syncthreads();
       } else if (ablate != 1) {
         float x0 = nx0, x1 = nx1, x2 = nx2;
         B8 wb;
-        B8 wb2;                                // (stem_store: the conv2 weights and the biases of conv1 and conv2)
-        float bias1 = 0.0f, bias2 = 0.0f;
-        if (!short_chain) load_b8(wb, rs0b, lane16, (wave & 1) * 8192);      // conv0b weights, in flight across the barrier
-        else load_b8(wb, rs2, lane16, wave * 8192);
+        B8 wb2;                                // (stem_store: the conv2 weights)
+        // the bias of a layer's epilogue, requested with the layer's weights (stem_store: conv1's and conv2's with conv1's weights)
+        float bias0b = 0.0f, bias1 = 0.0f, bias2 = 0.0f;
+        if (!short_chain) {
+            load_b8(wb, rs0b, lane16, (wave & 1) * 8192);                    // conv0b weights, in flight across the barrier
+            bias0b = br.b0b[32 * (wave & 1) + (lane & 31)];
+        } else {
+            load_b8(wb, rs2, lane16, wave * 8192);
+            bias2 = br.b2[32 * wave + (lane & 31)];
+        }
         if (has_rot) {
             // spelled out, contraction off: left to the compiler, the choice of which products fuse differed between the
             // instantiations of this kernel, and the screened and the dense conv3 must see the same points bit for bit.
@@ -195,11 +218,11 @@
                 f32x4 v;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    const int o = 16 * wave + 4 * c4 + c;   // wave-uniform -> scalar loads
-                    float s = b0a[o];
-                    s = fmaf(w0a[o], x0, s);
-                    s = fmaf(w0a[64 + o], x1, s);
-                    s = fmaf(w0a[128 + o], x2, s);
+                    const int o = 16 * wave + 4 * c4 + c;   // wave-uniform (screened kernels: from LDS)
+                    float s = conv0a_b(o);
+                    s = fmaf(conv0a_w(o), x0, s);
+                    s = fmaf(conv0a_w(64 + o), x1, s);
+                    s = fmaf(conv0a_w(128 + o), x2, s);
                     v[c] = fmaxf(s, 0.0f);
                 }
                 *reinterpret_cast<f32x4 *>(dst + 4 * c4) = v;
@@ -212,20 +235,20 @@
             {
                 const int rt = wave >> 1, nt = wave & 1;
                 f32x16 acc[1];
-                layer_k64<1>(bufA, SA, 32 * rt, wb, lane, acc);
-                load_b8(wb, rs1, lane16, nt * 8192);                           // conv1 weights
                 if constexpr (stem_store) {
                     // Loads and stores return through one counter (vmcnt), and with stores in flight the compiler's waits for
                     // a load are waits for the stores' round trip to HBM as well (conv1's bias and the conv2 weights requested
                     // behind the stores cost the STN launch 0.45 ms, requested in front of them and waited for behind them
                     // 0.3 ms: profiles/r12/variants.json).  So everything the tile loads before the screen is requested here,
-                    // a barrier and an epilogue ahead of conv1, and has arrived before the first store: nothing waits for a
-                    // load while the stores are in flight
+                    // a layer, an epilogue and a barrier ahead of conv1 (the conv1 weights: by conv0b's k-groups), and has
+                    // arrived before the first store: nothing waits for a load while the stores are in flight
                     load_b8(wb2, rs2, lane16, wave * 8192);                    // conv2 weights
                     bias1 = br.b1[32 * nt + (lane & 31)];
                     bias2 = br.b2[32 * wave + (lane & 31)];
                 }
-                store_tile_bias_relu(acc[0], bufB, SB, 32 * rt, 32 * nt, br.b0b, lane);
+                layer_k64<1, true>(bufA, SA, 32 * rt, wb, lane, acc, rs1, lane16, nt * 8192);     // (and the conv1 weights)
+                if constexpr (!stem_store) bias1 = br.b1[32 * nt + (lane & 31)];
+                store_tile_bias_relu(acc[0], bufB, SB, 32 * rt, 32 * nt, bias0b, lane);
             }
             __syncthreads();
             // ---- conv1 (STN: shared weights; main: per-item W1' = W1 . trans2): bufB -> bufA ---------
@@ -243,9 +266,9 @@
                     wb = wb2;
                     store_tile_bias_relu(acc[0], bufA, SA, 32 * rt, 32 * nt, bias1, lane);
                 } else {
-                    layer_k64<1>(bufB, SB, 32 * rt, wb, lane, acc);
-                    load_b8(wb, rs2, lane16, wave * 8192);                     // conv2 weights
-                    store_tile_bias_relu(acc[0], bufA, SA, 32 * rt, 32 * nt, br.b1, lane);
+                    layer_k64<1, true>(bufB, SB, 32 * rt, wb, lane, acc, rs2, lane16, wave * 8192);     // (and the conv2 weights)
+                    bias2 = br.b2[32 * wave + (lane & 31)];
+                    store_tile_bias_relu(acc[0], bufA, SA, 32 * rt, 32 * nt, bias1, lane);
                 }
             }
             __syncthreads();
@@ -260,13 +283,8 @@
                 bA0 = bufld4(w3rsrc, lane16, w3soff);
                 bA1 = bufld4(w3rsrc, lane16, w3soff + 16 * 1024);
             }
-            if constexpr (stem_store) {    // (the bias was requested in front of the stem's stores)
-                store_tile_bias_relu(acc[0], bufB, SB, 0, 32 * wave, bias2, lane);
-                store_tile_bias_relu(acc[1], bufB, SB, 32, 32 * wave, bias2, lane);
-            } else {
-                store_tile_bias_relu(acc[0], bufB, SB, 0, 32 * wave, br.b2, lane);
-                store_tile_bias_relu(acc[1], bufB, SB, 32, 32 * wave, br.b2, lane);
-            }
+            store_tile_bias_relu(acc[0], bufB, SB, 0, 32 * wave, bias2, lane);
+            store_tile_bias_relu(acc[1], bufB, SB, 32, 32 * wave, bias2, lane);
         }
         __syncthreads();
       } else {
