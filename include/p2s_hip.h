@@ -416,7 +416,9 @@ int p2s_mesh_sample_surface(const float *verts_dev, const int32_t *faces_dev, in
                             int64_t n_samples, float *pts_out_dev, int32_t *face_out_dev, double *area_host,
                             int device, void *stream);
 /* trimesh.points.remove_close + the [:count] cut of sample_surface_even: of every pair of points within `radius` the
- * one with more close neighbours is dropped (ties: the first); the survivors, in order, at most `limit` */
+ * one with more close neighbours is dropped (ties: the first); the survivors, in order, at most `limit`.  A pair is
+ * close when its squared float64 distance is <= radius * radius.  P2S_EINVAL, with nothing written and *n_out left
+ * alone: a NULL pointer, m > 2,000,000, limit < 0, or a radius that is negative, infinite or NaN */
 int p2s_points_remove_close(const float *pts_dev, int64_t m, double radius, int64_t limit, float *pts_out_dev,
                             int64_t *n_out, int device, void *stream);
 /* nearest-neighbour distance (float64, exact) of every query point to the cloud `target`; *max_host = directed

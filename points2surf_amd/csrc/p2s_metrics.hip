@@ -14,6 +14,7 @@
 #include "p2s_common.h"
 #include "p2s_internal.h"
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -297,6 +298,10 @@ extern "C" int p2s_points_remove_close(const float *pts_dev, int64_t m, double r
                                        int64_t *n_out, int device, void *stream) {
     if (!pts_dev || m < 0 || m > 2000000 || !pts_out_dev || !n_out || limit < 0) {
         p2s_set_error("p2s_points_remove_close: bad argument");
+        return P2S_EINVAL;
+    }
+    if (!(radius >= 0.0) || std::isinf(radius)) {      // r * r would take a negative radius for |r|, a NaN would remove nothing
+        p2s_set_error("p2s_points_remove_close: the radius must be finite and >= 0");
         return P2S_EINVAL;
     }
     if (p2s_device_count() <= device || device < 0) return P2S_ENODEVICE;

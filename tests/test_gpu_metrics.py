@@ -30,10 +30,11 @@ def test_random_sample_and_surface_sampling_match_the_oracle():
     torch.cuda.synchronize()
     rs = np.random.RandomState(123)
     ref, area_ref, idx_ref = MO.sample_surface(v, f, 5000, rs)
-    assert abs(area - area_ref) < 1e-12 * area_ref
+    # the device's scan and np.cumsum each stay within nf * 2^-53 relative of the exact sum of the nf areas
+    assert abs(area - area_ref) <= 2 * f.shape[0] * 2.0 ** -53 * area_ref
     same = fid.cpu().numpy() == idx_ref
     assert same.mean() > 0.999                               # cumulative areas: parallel scan vs np.cumsum, last-bit ties only
-    assert np.abs(pts.cpu().numpy()[same] - ref[same]).max() < 1e-6
+    assert np.array_equal(pts.cpu().numpy()[same], ref[same])   # the same float64 expression, rounded once to float32
     mt, pos = rng.get_state()                                # 3 * 5000 doubles consumed, like numpy
     st = rs.get_state()
     assert np.array_equal(mt, st[1]) and pos == st[2]
@@ -71,8 +72,9 @@ def test_mesh_distances_match_the_oracle_on_the_same_samples():
     h_ab, s_ab = metrics.directed_stats(sa, sb)
     h_ba, s_ba = metrics.directed_stats(sb, sa)
     ref = MO.mesh_distances(sa.cpu().numpy(), sb.cpu().numpy())
-    assert abs(h_ab - ref[0]) < 1e-9 and abs(h_ba - ref[1]) < 1e-9
-    assert abs((s_ab + s_ba) - ref[3]) < 1e-7 * ref[3]
+    assert h_ab == ref[0] and h_ba == ref[1]                 # the max of distances that are scipy's bit for bit
+    # two sums of the same na + nb non-negative terms, each within (na + nb - 1) * 2^-53 relative of the exact one
+    assert abs((s_ab + s_ba) - ref[3]) <= 2 * (sa.shape[0] + sb.shape[0]) * 2.0 ** -53 * ref[3]
     # even sampling: no two samples closer than the rejection radius
     import scipy.spatial as spatial
     a = sa.cpu().numpy().astype(np.float64)
