@@ -5,27 +5,43 @@
 //   decoder    fc1_{local,global},bn1_*,relu / fc2,bn2,relu / fc3,bn3,relu / fc4   :335-350
 // BatchNorm (eval) is folded into W/bias on the host; W is packed in B-fragment order so that
 // each wave streams its own 32-column panel from L2 with coalesced 16-byte loads (no LDS for W);
-// the activation tile [64 rows x 128 k] is staged in LDS once per k-chunk and shared by 4 waves.
+// the activation tile [32 or 64 rows x 64 or 128 k] is staged in LDS once per k-chunk and shared by 4 waves.
 #include "p2s_common.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
-constexpr int GK = 128;    // k chunk staged in LDS
-constexpr int GS = 132;    // LDS row stride
+constexpr int GK = 128;    // k chunk staged in LDS (fp16 pair kernel); K is a multiple of it
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
-// grid: (ceil(M / (32 RT)), N/128, Z); block 256: wave w -> column tile (blockIdx.y*4 + w), RT row tiles of 32.
+// grid: (ceil(M / (32 RT)), N/128, Z); block 256: wave w -> column tile (y*4 + w), RT row tiles of 32.
 // RT = 2 halves the weight stream per output; RT = 1 doubles the number of workgroups for the layers whose grid would
 // not fill the chip (a 4096-query chunk gives the 512- and 256-column layers 512 / 256 workgroups of 64 rows for 1024
 // workgroup slots: M = 4096 is all the parallelism there is).
-template <int RT>
+//
+// r17: one accumulation chain per output element as before (k ascending, the pairs (8g + t, 8g + 4 + t) of one MFMA), but
+// nothing of a chunk waits behind its barrier any more:
+//   - the weight fragments are a ring of DEPTH steps that runs on across the chunk boundary (the panel is contiguous in k);
+//   - the next activation chunk is requested BEHIND the ring's loads of the step (waits count in issue order: requested
+//     ahead of them, as it was, the first MFMA of every chunk waited for it) and written to the OTHER LDS buffer late in the
+//     chunk, so a chunk ends in one barrier with nothing to do behind it;
+//   - the A2 test sits outside the unrolled loads (inside, every load got a branch and a full wait of its own).
+//   - a full tile stores its results without row tests (behind a test every store waited for the one before it).
+// Chunks are 64 RT wide in k: the two LDS buffers of a workgroup take what the one 128-wide buffer took.
+template <int RT, bool HAS_A2>
 __global__ __launch_bounds__(256) void p2s_gemm_kernel(GemmArgs g) {
     constexpr int GM = 32 * RT;
-    __shared__ __attribute__((aligned(16))) float As[GM * GS];
+    constexpr int CK = 64 * RT;           // k chunk staged in LDS
+    constexpr int DEPTH = 4;              // steps of 8 k the weight ring runs ahead
+    constexpr int CS = CK + 4;            // LDS row stride
+    constexpr int CL = CK / 4;            // lanes per staged row
+    constexpr int RP = 256 / CL;          // rows per staging pass
+    constexpr int NS = GM / RP;
+    __shared__ __attribute__((aligned(16))) float As[2 * GM * CS];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -39,69 +55,103 @@ __global__ __launch_bounds__(256) void p2s_gemm_kernel(GemmArgs g) {
     const float *__restrict__ bias = g.bias[z];
     float *__restrict__ C = g.C + (long long)z * g.c_z;
 
-    f32x16 acc0, acc1;
+    f32x16 acc[RT];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
+    for (int r = 0; r < RT; ++r)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[r][i] = 0.f;
 
-    const float *a0p = As + (lane & 31) * GS + 4 * (lane >> 5);
-    const float *a1p = a0p + 32 * GS;
+    const int aoff = (lane & 31) * CS + 4 * (lane >> 5);
 
-    // the activation chunk [GM rows][128 k] goes global -> registers -> LDS; r04: the NEXT chunk's loads are issued before
-    // the MFMAs of the current one and land in registers while they run (the kernel used to wait out the load latency
-    // behind every barrier: 55 % of the fp32 MFMA peak).  8 rows per pass, 32 lanes x 16 B per row (coalesced).
-    f32x4 stage[GM / 8];
+    // the activation chunk [GM rows][CK k] goes global -> registers -> LDS: RP rows per pass, CL lanes x 16 B per row
+    f32x4 stage[NS];
+    int mrow[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) mrow[i] = min(m0 + tid / CL + RP * i, g.M - 1);
     auto fetch = [&](int kc) {
 #pragma unroll
-        for (int i = 0; i < GM / 8; ++i) {
-            const int r = (tid >> 5) + 8 * i;
-            int m = m0 + r;
-            if (m >= g.M) m = g.M - 1;
-            f32x4 v = *reinterpret_cast<const f32x4 *>(A + (long long)m * g.lda + kc + 4 * (tid & 31));
-            if (A2) {                 // max-pool over two point sets = max of their pools; NaN wins like torch's max
-                const f32x4 u = *reinterpret_cast<const f32x4 *>(A2 + (long long)m * g.lda + kc + 4 * (tid & 31));
+        for (int i = 0; i < NS; ++i) stage[i] = *reinterpret_cast<const f32x4 *>(A + (long long)mrow[i] * g.lda + kc + 4 * (tid % CL));
+        if (HAS_A2) {                 // max-pool over two point sets = max of their pools; NaN wins like torch's max
+            f32x4 u[NS];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) v[t] = g.a2_add ? v[t] + u[t] : ((u[t] > v[t] || u[t] != u[t]) ? u[t] : v[t]);
+            for (int i = 0; i < NS; ++i) u[i] = *reinterpret_cast<const f32x4 *>(A2 + (long long)mrow[i] * g.lda + kc + 4 * (tid % CL));
+            if (g.a2_add) {
+#pragma unroll
+                for (int i = 0; i < NS; ++i) stage[i] += u[i];
+            } else {
+#pragma unroll
+                for (int i = 0; i < NS; ++i)
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) stage[i][t] = (u[i][t] > stage[i][t] || u[i][t] != u[i][t]) ? u[i][t] : stage[i][t];
             }
-            stage[i] = v;
         }
     };
-    auto commit = [&]() {
+    auto commit = [&](float *as) {
 #pragma unroll
-        for (int i = 0; i < GM / 8; ++i) *reinterpret_cast<f32x4 *>(As + ((tid >> 5) + 8 * i) * GS + 4 * (tid & 31)) = stage[i];
+        for (int i = 0; i < NS; ++i) *reinterpret_cast<f32x4 *>(as + (tid / CL + RP * i) * CS + 4 * (tid % CL)) = stage[i];
     };
+
+    f32x4 b[DEPTH];
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) b[d] = *reinterpret_cast<const f32x4 *>(Wp + d * 256);
     fetch(0);
-    for (int kc = 0; kc < g.K; kc += GK) {
-        __syncthreads();              // every wave is done reading the previous chunk
-        commit();
-        __syncthreads();
-        if (kc + GK < g.K) fetch(kc + GK);
+    commit(As);
+    __syncthreads();
+
+    // one chunk of CK / 8 steps of 8 k; LAST: the ring runs dry and no chunk follows.  The requests of a step stand where
+    // they are written (the fence at its end): left alone, the compiler moves them down to their first use
+    auto chunk = [&](int kc, auto last) {
+        constexpr bool LAST = decltype(last)::value;
+        const float *as = As + ((kc / CK) & 1) * (GM * CS) + aoff;
         const float *wk = Wp + (long long)(kc / 8) * 256;
-        f32x4 b = *reinterpret_cast<const f32x4 *>(wk);
+        f32x4 a[2][RT];
 #pragma unroll
-        for (int kg = 0; kg < GK / 8; ++kg) {
-            f32x4 nb = b;
-            if (kg < GK / 8 - 1) nb = *reinterpret_cast<const f32x4 *>(wk + (kg + 1) * 256);
-            const f32x4 a0 = *reinterpret_cast<const f32x4 *>(a0p + 8 * kg);
-            f32x4 a1 = a0;
-            if (RT == 2) a1 = *reinterpret_cast<const f32x4 *>(a1p + 8 * kg);
+        for (int r = 0; r < RT; ++r) a[0][r] = *reinterpret_cast<const f32x4 *>(as + 32 * r * CS);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                acc0 = mfma32(a0[t], b[t], acc0);
-                if (RT == 2) acc1 = mfma32(a1[t], b[t], acc1);
+        for (int kg = 0; kg < CK / 8; ++kg) {
+            const f32x4 bk = b[kg % DEPTH];
+            if (!LAST || kg + DEPTH < CK / 8) b[kg % DEPTH] = *reinterpret_cast<const f32x4 *>(wk + (kg + DEPTH) * 256);
+            if (!LAST && kg == 1) fetch(kc + CK);
+            if (kg + 1 < CK / 8) {
+#pragma unroll
+                for (int r = 0; r < RT; ++r) a[(kg + 1) & 1][r] = *reinterpret_cast<const f32x4 *>(as + 32 * r * CS + 8 * (kg + 1));
             }
-            b = nb;
+            if (!LAST && kg == CK / 8 - 3) commit(As + (((kc / CK) & 1) ^ 1) * (GM * CS));
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int r = 0; r < RT; ++r) acc[r] = mfma32(a[kg & 1][r][t], bk[t], acc[r]);
+            __builtin_amdgcn_sched_barrier(0);
         }
-    }
+        if (!LAST) __syncthreads();   // the other buffer is written, this one is read out
+    };
+    int kc = 0;
+    for (; kc + CK < g.K; kc += CK) chunk(kc, std::false_type());
+    chunk(kc, std::true_type());
+
     const int col = nt * 32 + (lane & 31);
     const float bv = bias[col];
+    // NaN-propagating ReLU (torch.relu(NaN) = NaN; fmaxf would swallow it)
+    float *cp = C + (long long)(m0 + 4 * (lane >> 5)) * g.ldc + col;
+    if (m0 + GM <= g.M) {             // a full tile stores without tests: behind a test, every store waited for the one before
 #pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int r = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-        float v0 = acc0[reg] + bv, v1 = acc1[reg] + bv;
-        // NaN-propagating ReLU (torch.relu(NaN) = NaN; fmaxf would swallow it)
-        if (g.relu) { v0 = (v0 < 0.f) ? 0.f : v0; v1 = (v1 < 0.f) ? 0.f : v1; }
-        if (m0 + r < g.M) C[(long long)(m0 + r) * g.ldc + col] = v0;
-        if (RT == 2 && m0 + 32 + r < g.M) C[(long long)(m0 + 32 + r) * g.ldc + col] = v1;
+        for (int r2 = 0; r2 < RT; ++r2)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                float v = acc[r2][reg] + bv;
+                if (g.relu) v = (v < 0.f) ? 0.f : v;
+                cp[(long long)(32 * r2 + (reg & 3) + 8 * (reg >> 2)) * g.ldc] = v;
+            }
+    } else {
+#pragma unroll
+        for (int r2 = 0; r2 < RT; ++r2)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int r = 32 * r2 + (reg & 3) + 8 * (reg >> 2);
+                float v = acc[r2][reg] + bv;
+                if (g.relu) v = (v < 0.f) ? 0.f : v;
+                if (m0 + 4 * (lane >> 5) + r < g.M) cp[(long long)r * g.ldc] = v;
+            }
     }
 }
 
@@ -331,12 +381,13 @@ int p2s_launch_gemm(const GemmArgs &g, hipStream_t stream) {
         P2S_LAUNCH_CHECK("p2s_gemm_f16_kernel");
         return P2S_OK;
     }
-    if (rt2) {
+    if (rt2 && !g.A2) {              // (the layers with a second operand are 512 columns wide: 32-row tiles up to 16,384 rows anyway)
         dim3 grid((g.M + 63) / 64, g.N / 128, g.Z);
-        hipLaunchKernelGGL(p2s_gemm_kernel<2>, grid, dim3(256), 0, stream, g);
+        hipLaunchKernelGGL((p2s_gemm_kernel<2, false>), grid, dim3(256), 0, stream, g);
     } else {
         dim3 grid((g.M + 31) / 32, g.N / 128, g.Z);
-        hipLaunchKernelGGL(p2s_gemm_kernel<1>, grid, dim3(256), 0, stream, g);
+        if (g.A2) hipLaunchKernelGGL((p2s_gemm_kernel<1, true>), grid, dim3(256), 0, stream, g);
+        else hipLaunchKernelGGL((p2s_gemm_kernel<1, false>), grid, dim3(256), 0, stream, g);
     }
     P2S_LAUNCH_CHECK("p2s_gemm_kernel");
     return P2S_OK;
