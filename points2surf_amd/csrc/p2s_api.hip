@@ -16,9 +16,8 @@ void p2s_set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
-// Process-wide grow-only scratch buffer per device (volume / iso-surface stages).  The caller holds the device's
-// scratch lock for its whole call (P2sScratchLock), so concurrent host threads serialise on it instead of each keeping
-// ~2 GB of HBM alive until the process exits; p2s_release_scratch() gives the memory back.
+// Process-wide grow-only scratch buffer per device (P2sScratchLock, p2s_common.h; when to use it and when a handle's own
+// DevBuf: DESIGN.md, "who owns device memory").
 namespace {
 struct DevScratch {
     std::mutex mu;
@@ -59,31 +58,27 @@ static int screen_init(p2s_model_s *m) {
     if (m->cfg.encoder_bf16 != 0) return P2S_OK;
     const char *dense = getenv("P2S_CONV3_DENSE");
     if (dense && atoi(dense) != 0) return P2S_OK;
-    int *flag = nullptr;
-    bool ok = hipMalloc(&m->scr_w3h, (size_t)4 * P2S_SCR_PIECE * 2) == hipSuccess && hipMalloc(&m->scr_mu, (size_t)4 * 1024 * 4) == hipSuccess &&
-              hipMalloc(&m->scr_counters, 3 * 8) == hipSuccess && hipMalloc(&flag, 4) == hipSuccess &&
-              hipMemset(m->scr_counters, 0, 3 * 8) == hipSuccess && hipMemset(flag, 0, 4) == hipSuccess;
+    DevBuf<int> flag;
+    const bool ok = p2s_alloc_all(m->scr_w3h, (size_t)4 * P2S_SCR_PIECE, m->scr_mu, (size_t)4 * 1024, m->scr_counters, 3, flag, 1) &&
+                    hipMemset(m->scr_counters.get(), 0, 3 * 8) == hipSuccess && hipMemset(flag.get(), 0, 4) == hipSuccess;
     int rc = P2S_OK, h = 0;
     if (!ok) {
         (void)hipGetLastError();
-        p2s_set_error("hipMalloc(screen operands of conv3) failed");
+        p2s_set_error("allocation of the screen operands of conv3 failed");
         rc = P2S_ENOMEM;
     }
     for (int i = 0; i < 4 && rc == P2S_OK; ++i) {
         const P2sLayer layer = i < 2 ? L_S3 : L_M3;
         rc = p2s_launch_screen_prepare(m->w32(layer, i & 1), const_cast<unsigned short *>(m->screen_w(layer, i & 1)),
-                                       const_cast<float *>(m->screen_mu(layer, i & 1)), nullptr, flag);
+                                       const_cast<float *>(m->screen_mu(layer, i & 1)), nullptr, flag.get());
     }
-    if (rc == P2S_OK && hipMemcpy(&h, flag, 4, hipMemcpyDeviceToHost) != hipSuccess) {
+    if (rc == P2S_OK && hipMemcpy(&h, flag.get(), 4, hipMemcpyDeviceToHost) != hipSuccess) {
         p2s_set_error("hipMemcpy(conv3 range flag) failed");
         rc = P2S_EHIP;
     }
-    if (flag) (void)hipFree(flag);
     if (rc == P2S_OK && h) {          // a conv3 weight beyond the half range: this model keeps the dense conv3
-        (void)hipFree(m->scr_w3h);
-        (void)hipFree(m->scr_mu);
-        m->scr_w3h = nullptr;
-        m->scr_mu = nullptr;
+        m->scr_w3h.reset();
+        m->scr_mu.reset();
     }
     // stem reuse: both passes of the model run the screened kernel (a sym_op='sum' main pass keeps the dense conv3).  The default
     // cap holds the 2688 MB of an 8192-query chunk of 300 + 1000 points (21 tiles of 16 KB per query).  The switch and the cap
@@ -93,15 +88,14 @@ static int screen_init(p2s_model_s *m) {
     return rc;
 }
 
-// p2s_model_create: the device side of a new handle; on failure the caller destroys the half-built handle and frees *wflag
-static int model_init(p2s_model_s *m, const float *blob_host, size_t n_floats, int **wflag) {
+// p2s_model_create: the device side of a new handle; on failure the caller destroys the half-built handle
+static int model_init(p2s_model_s *m, const float *blob_host, size_t n_floats) {
     const p2s_model_cfg &cfg = m->cfg;
-    hipError_t e = hipMalloc(&m->blob, n_floats * sizeof(float));
-    if (e != hipSuccess) {
-        p2s_set_error("hipMalloc(weights) failed: %s", hipGetErrorString(e));
+    if (!m->blob.alloc(n_floats)) {
+        p2s_set_error("allocation of the weights failed");
         return P2S_ENOMEM;
     }
-    e = hipMemcpy(m->blob, blob_host, n_floats * sizeof(float), hipMemcpyHostToDevice);
+    const hipError_t e = hipMemcpy(m->blob.get(), blob_host, n_floats * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         p2s_set_error("hipMemcpy(weights) failed: %s", hipGetErrorString(e));
         return P2S_EHIP;
@@ -127,26 +121,26 @@ static int model_init(p2s_model_s *m, const float *blob_host, size_t n_floats, i
                 m->h_total += (size_t)p2s_layers[l].K * p2s_layers[l].N;
             }
     }
-    if (hipMalloc(&m->blob_h, m->h_total * 2 * prec.pieces) != hipSuccess) {
-        (void)hipGetLastError();
-        p2s_set_error("hipMalloc(bf16 weights) failed");
+    if (!m->blob_h.alloc(m->h_total * prec.pieces)) {
+        p2s_set_error("allocation of the 16-bit weights failed");
         return P2S_ENOMEM;
     }
-    if (prec.f16 && (hipMalloc(wflag, 4) != hipSuccess || hipMemset(*wflag, 0, 4) != hipSuccess)) {
+    DevBuf<int> wflag;          // fp16 pair: raised by the packing kernel when a BN-folded weight does not fit the half range
+    if (prec.f16 && (!wflag.alloc(1) || hipMemset(wflag.get(), 0, 4) != hipSuccess)) {
         (void)hipGetLastError();
-        p2s_set_error("hipMalloc(weight range flag) failed");
+        p2s_set_error("allocation of the weight range flag failed");
         return P2S_ENOMEM;
     }
     for (int piece = 0; piece < prec.pieces; ++piece)
         for (const Item &it : items) {
             const P2sLayerDesc &d = p2s_layers[it.layer];
-            const int rc = p2s_launch_pack_bf16(m->w32(it.layer, it.z), m->blob_h + (size_t)piece * m->h_total + m->h_off[it.layer][it.z],
-                                                d.K, d.N, 0, 0, 1, piece, prec.f16, nullptr, *wflag);
+            const int rc = p2s_launch_pack_bf16(m->w32(it.layer, it.z), m->blob_h.get() + (size_t)piece * m->h_total + m->h_off[it.layer][it.z],
+                                                d.K, d.N, 0, 0, 1, piece, prec.f16, nullptr, wflag.get());
             if (rc) return rc;
         }
     if (prec.f16) {
         int h = 0;
-        const hipError_t e2 = hipMemcpy(&h, *wflag, 4, hipMemcpyDeviceToHost);
+        const hipError_t e2 = hipMemcpy(&h, wflag.get(), 4, hipMemcpyDeviceToHost);
         if (e2 != hipSuccess) {
             p2s_set_error("hipMemcpy(weight range flag) failed: %s", hipGetErrorString(e2));
             return P2S_EHIP;
@@ -161,16 +155,13 @@ static int model_init(p2s_model_s *m, const float *blob_host, size_t n_floats, i
         p2s_model_s::Fallback &fb = m->fb;
         fb.cap = 16384;
         const size_t k3 = (size_t)cfg.points_per_patch * 3, n3 = (size_t)cfg.sub_sample_size * 3, cap = fb.cap;
-        bool ok = hipMalloc(&fb.flags, (size_t)m->max_chunk * 4) == hipSuccess && hipMalloc(&fb.count, 4) == hipSuccess &&
-                  hipMalloc(&fb.patch, cap * k3 * 4) == hipSuccess && hipMalloc(&fb.sub, cap * n3 * 4) == hipSuccess &&
-                  hipMalloc(&fb.query, cap * 12) == hipSuccess && hipMalloc(&fb.radius, cap * 4) == hipSuccess &&
-                  hipMalloc(&fb.index, cap * 8) == hipSuccess && hipMalloc(&fb.sdf, cap * 4) == hipSuccess &&
-                  hipMalloc(&fb.logits, cap * 8) == hipSuccess;
-        ok = ok && hipMemset(fb.flags, 0, (size_t)m->max_chunk * 4) == hipSuccess && hipMemset(fb.count, 0, 4) == hipSuccess &&
-             hipMemset(fb.radius, 0, cap * 4) == hipSuccess;
+        const bool ok = p2s_alloc_all(fb.flags, (size_t)m->max_chunk, fb.count, 1, fb.patch, cap * k3, fb.sub, cap * n3, fb.query, cap * 3,
+                                      fb.radius, cap, fb.index, cap, fb.sdf, cap, fb.logits, cap * 2) &&
+                        hipMemset(fb.flags.get(), 0, (size_t)m->max_chunk * 4) == hipSuccess && hipMemset(fb.count.get(), 0, 4) == hipSuccess &&
+                        hipMemset(fb.radius.get(), 0, cap * 4) == hipSuccess;
         if (!ok) {
             (void)hipGetLastError();
-            p2s_set_error("hipMalloc(fp32 fallback buffers of the fp16 pair mode) failed");
+            p2s_set_error("allocation of the fp32 fallback buffers of the fp16 pair mode failed");
             return P2S_ENOMEM;
         }
     }
@@ -228,9 +219,7 @@ int p2s_model_create(const p2s_model_cfg *cfg, const float *blob_host, size_t n_
     }
     P2S_HIP_CHECK(hipSetDevice(device));
     p2s_model_s *m = new p2s_model_s(*cfg, *offs, device);
-    int *wflag = nullptr;       // fp16 pair: raised by the packing kernel when a BN-folded weight does not fit the half range
-    const int rc = model_init(m, blob_host, n_floats, &wflag);
-    if (wflag) (void)hipFree(wflag);
+    const int rc = model_init(m, blob_host, n_floats);
     if (rc) p2s_model_destroy(m);
     else *out = m;
     return rc;
@@ -239,22 +228,7 @@ int p2s_model_create(const p2s_model_cfg *cfg, const float *blob_host, size_t n_
 int p2s_model_destroy(p2s_model_t m) {
     if (!m) return P2S_OK;
     (void)hipSetDevice(m->device);
-    p2s_pipe_free(m);
-    p2s_workers_free(m);
-    if (m->ws) (void)hipFree(m->ws);
-    if (m->blob) (void)hipFree(m->blob);
-    if (m->blob_h) (void)hipFree(m->blob_h);
-    if (m->scr_w3h) (void)hipFree(m->scr_w3h);
-    if (m->scr_mu) (void)hipFree(m->scr_mu);
-    if (m->scr_counters) (void)hipFree(m->scr_counters);
-    for (void *p : {(void *)m->fb.flags, (void *)m->fb.count, (void *)m->fb.patch, (void *)m->fb.sub, (void *)m->fb.query,
-                    (void *)m->fb.radius, (void *)m->fb.index, (void *)m->fb.sdf, (void *)m->fb.logits})
-        if (p) (void)hipFree(p);
-    for (auto &ev : m->evpool)
-        if (ev) (void)hipEventDestroy(ev);
-    if (m->aux) (void)hipStreamDestroy(m->aux);
-    if (m->ball) (void)hipStreamDestroy(m->ball);
-    delete m;
+    delete m;          // the members release what they own; the streams (declared first) go last
     return P2S_OK;
 }
 
@@ -270,7 +244,7 @@ int p2s_get_counters(p2s_model_t m, p2s_counters *out) {
     if (m->scr_counters) {            // the screened conv3 counts on the device; valid once the call's stream is synchronised
         unsigned long long h[3] = {};
         P2S_HIP_CHECK(hipSetDevice(m->device));
-        P2S_HIP_CHECK(hipMemcpy(h, m->scr_counters, sizeof(h), hipMemcpyDeviceToHost));
+        P2S_HIP_CHECK(hipMemcpy(h, m->scr_counters.get(), sizeof(h), hipMemcpyDeviceToHost));
         out->conv3_confirmed = (int64_t)h[0];
         out->conv3_items_dense = (int64_t)h[1];
         out->conv3_items = (int64_t)h[2];
@@ -283,12 +257,12 @@ int p2s_get_counters(p2s_model_t m, p2s_counters *out) {
 int p2s_prof_mark(p2s_model_s *m, hipStream_t s) {
     if (!m->profiling) return -1;
     if (m->ev_used >= (int)m->evpool.size()) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return -1;
-        m->evpool.push_back(e);
+        DevEvent e;
+        if (!e.create()) return -1;
+        m->evpool.push_back(std::move(e));
     }
     const int i = m->ev_used++;
-    if (hipEventRecord(m->evpool[i], s) != hipSuccess) return -1;
+    if (hipEventRecord(m->evpool[i].get(), s) != hipSuccess) return -1;
     return i;
 }
 
@@ -304,10 +278,10 @@ static void prof_reset(p2s_model_s *m) {
 
 static void prof_collect(p2s_model_s *m) {           // synchronises the last event
     if (!m->profiling || m->ev_used == 0) return;
-    (void)hipEventSynchronize(m->evpool[m->ev_used - 1]);
+    (void)hipEventSynchronize(m->evpool[m->ev_used - 1].get());
     for (const auto &sp : m->spans) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, m->evpool[sp.a], m->evpool[sp.b]) != hipSuccess) {
+        if (hipEventElapsedTime(&ms, m->evpool[sp.a].get(), m->evpool[sp.b].get()) != hipSuccess) {
             (void)hipGetLastError();          // an event that was never reached: only this complaint is dropped
             continue;
         }
@@ -339,10 +313,10 @@ ModelCall::ModelCall(p2s_model_s *m_, hipStream_t s_, bool pipeline_) : m(m_), s
     rc = [&]() -> int {
         P2S_HIP_CHECK(hipSetDevice(m->device));
         prof_reset(m);
-        if (m->scr_counters) P2S_HIP_CHECK(hipMemsetAsync(m->scr_counters, 0, 3 * 8, s));
+        if (m->scr_counters) P2S_HIP_CHECK(hipMemsetAsync(m->scr_counters.get(), 0, 3 * 8, s));
         if (m->fb.count) {
-            P2S_HIP_CHECK(hipMemsetAsync(m->fb.count, 0, 4, s));
-            P2S_HIP_CHECK(hipMemsetAsync(m->fb.flags, 0, (size_t)m->max_chunk * 4, s));
+            P2S_HIP_CHECK(hipMemsetAsync(m->fb.count.get(), 0, 4, s));
+            P2S_HIP_CHECK(hipMemsetAsync(m->fb.flags.get(), 0, (size_t)m->max_chunk * 4, s));
         }
         return P2S_OK;
     }();
@@ -351,8 +325,8 @@ ModelCall::ModelCall(p2s_model_s *m_, hipStream_t s_, bool pipeline_) : m(m_), s
 int ModelCall::fail(int code) {
     if (!m) return code;
     (void)hipStreamSynchronize(s);          // (an error here is a real fault and stays pending)
-    if (pipeline && m->aux) (void)hipStreamSynchronize(m->aux);
-    if (pipeline && m->ball) (void)hipStreamSynchronize(m->ball);
+    if (pipeline && m->aux) (void)hipStreamSynchronize(m->aux.get());
+    if (pipeline && m->ball) (void)hipStreamSynchronize(m->ball.get());
     return code;
 }
 

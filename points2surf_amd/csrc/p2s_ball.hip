@@ -380,13 +380,11 @@ int ball_ws_reserve(p2s_rng_s *r, size_t bytes) {
     if (bytes <= r->ball_ws_bytes) return P2S_OK;
     if (r->ball_ws) {
         P2S_HIP_CHECK(hipDeviceSynchronize());
-        (void)hipFree(r->ball_ws);
-        r->ball_ws = nullptr;
+        r->ball_ws.reset();
         r->ball_ws_bytes = 0;
     }
     bytes += bytes / 4;
-    if (hipMalloc(&r->ball_ws, bytes) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!r->ball_ws.alloc(bytes)) {
         p2s_set_error("fixed-radius patches: hipMalloc of %zu bytes of work space failed", bytes);
         return P2S_ENOMEM;
     }
@@ -395,12 +393,6 @@ int ball_ws_reserve(p2s_rng_s *r, size_t bytes) {
 }
 
 }  // namespace
-
-void p2s_ball_free_rng(p2s_rng_s *r) {
-    if (r->ball_ws) (void)hipFree(r->ball_ws);
-    if (r->ball_counts_host) (void)hipHostFree(r->ball_counts_host);
-    if (r->ball_counts_dev) (void)hipFree(r->ball_counts_dev);
-}
 
 extern "C" int p2s_kd_order_host(const float *pts_host, int64_t n, int leafsize, int32_t *order_out, int32_t *leaf_start_out,
                                  int64_t leaf_cap, int32_t *n_leaves_out) {
@@ -528,7 +520,7 @@ int p2s_ball_patch_counted(p2s_rng_s *r, p2s_cloud_s *c, const float *q_dev, con
                      o_list = o_six + (size_t)cur * 24, total = o_list + (size_t)std::max<long long>(hits, 1) * 4;
         int rc = ball_ws_reserve(r, total);
         if (rc) return rc;
-        char *ws = (char *)r->ball_ws;
+        char *ws = (char *)r->ball_ws.get();
         long long *off = (long long *)(ws + o_off), *spos = (long long *)(ws + o_spos), *tpos = (long long *)(ws + o_tpos);
         uint32_t *six = (uint32_t *)(ws + o_six);
         int *lists = (int *)(ws + o_list);
@@ -544,15 +536,15 @@ int p2s_ball_patch_counted(p2s_rng_s *r, p2s_cloud_s *c, const float *q_dev, con
         }
         // one latency-bound wave next to MFMA-saturated encoders: claim most of a CU's LDS so that it gets a CU of its own
         const size_t lds = cur >= 64 ? (size_t)120 * 1024 : (size_t)BC_RING * 4;
-        hipLaunchKernelGGL(ball_chain_kernel, dim3(1), dim3(64), lds, s, r->tmp, cap, cap + 624, cb, cur, k, tail_words, spos,
+        hipLaunchKernelGGL(ball_chain_kernel, dim3(1), dim3(64), lds, s, r->tmp.get(), cap, cap + 624, cb, cur, k, tail_words, spos,
                            tail_words ? tpos : (long long *)nullptr, meta);
         if (patch_out_dev)
-        hipLaunchKernelGGL(ball_patch_kernel, dim3(cur), dim3(64), 0, s, r->tmp, cap, c->pts, qb, cb, off, lists, spos, k, (float)radius,
+        hipLaunchKernelGGL(ball_patch_kernel, dim3(cur), dim3(64), 0, s, r->tmp.get(), cap, c->pts, qb, cb, off, lists, spos, k, (float)radius,
                            ids_out_dev ? ids_out_dev + (size_t)done * k : (int32_t *)nullptr, patch_out_dev + (size_t)done * k * 3,
                            radius_out_dev ? radius_out_dev + done : (float *)nullptr, meta);
         P2S_LAUNCH_CHECK("fixed-radius patch kernels");
         if (rot_out_dev && tail_words == 6) {
-            hipLaunchKernelGGL(ball_rot_words_kernel, dim3((unsigned)((cur + 255) / 256)), dim3(256), 0, s, r->tmp, tpos, (long long)cur, six,
+            hipLaunchKernelGGL(ball_rot_words_kernel, dim3((unsigned)((cur + 255) / 256)), dim3(256), 0, s, r->tmp.get(), tpos, (long long)cur, six,
                                cap + 624, meta);
             P2S_LAUNCH_CHECK("ball_rot_words_kernel");
             rc = p2s_rotations_from_words(six, cur, rot_out_dev + (size_t)done * 9, s);
@@ -568,26 +560,22 @@ int p2s_ball_counts_to_host(p2s_rng_s *r, p2s_cloud_s *c, const float *q_dev, in
                             const int32_t **count_host, hipStream_t s) {
     if ((size_t)nq > r->ball_counts_cap) {
         P2S_HIP_CHECK(hipDeviceSynchronize());
-        if (r->ball_counts_host) (void)hipHostFree(r->ball_counts_host);
-        if (r->ball_counts_dev) (void)hipFree(r->ball_counts_dev);
-        r->ball_counts_host = nullptr;
-        r->ball_counts_dev = nullptr;
+        r->ball_counts_host.reset();
+        r->ball_counts_dev.reset();
         r->ball_counts_cap = 0;
         const size_t cap = (size_t)nq + (size_t)nq / 4 + 1024;
-        if (hipHostMalloc((void **)&r->ball_counts_host, cap * 4, hipHostMallocDefault) != hipSuccess ||
-            hipMalloc((void **)&r->ball_counts_dev, cap * 4) != hipSuccess) {
-            (void)hipGetLastError();
+        if (!p2s_alloc_all(r->ball_counts_host, cap, r->ball_counts_dev, cap)) {
             p2s_set_error("fixed-radius patches: allocation of %zu hit counts failed", cap);
             return P2S_ENOMEM;
         }
         r->ball_counts_cap = cap;
     }
-    int rc = p2s_ball_count(c, q_dev, nq, radius, r->ball_counts_dev, (void *)s);
+    int rc = p2s_ball_count(c, q_dev, nq, radius, r->ball_counts_dev.get(), (void *)s);
     if (rc) return rc;
-    P2S_HIP_CHECK(hipMemcpyAsync(r->ball_counts_host, r->ball_counts_dev, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    P2S_HIP_CHECK(hipMemcpyAsync(r->ball_counts_host.get(), r->ball_counts_dev.get(), (size_t)nq * 4, hipMemcpyDeviceToHost, s));
     P2S_HIP_CHECK(hipStreamSynchronize(s));
-    *count_dev = r->ball_counts_dev;
-    *count_host = r->ball_counts_host;
+    *count_dev = r->ball_counts_dev.get();
+    *count_host = r->ball_counts_host.get();
     return P2S_OK;
 }
 

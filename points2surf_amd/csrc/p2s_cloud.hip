@@ -510,7 +510,7 @@ int p2s_rng_reseed(p2s_rng_s *r, uint32_t seed, hipStream_t s) {
     if (rc) return rc;
     uint32_t st[625];
     p2s_mt_seed_host(seed, st);
-    P2S_HIP_CHECK(hipMemcpyAsync(r->state, st, sizeof(st), hipMemcpyHostToDevice, s));
+    P2S_HIP_CHECK(hipMemcpyAsync(r->state.get(), st, sizeof(st), hipMemcpyHostToDevice, s));
     P2S_HIP_CHECK(hipStreamSynchronize(s));        // st lives on this stack frame
     return P2S_OK;
 }
@@ -532,7 +532,7 @@ int p2s_rng_serial_randint(p2s_rng_s *r, uint32_t rng, uint32_t mask, long long 
     }
     // tiny requests (tests, tails) do not need a CU of their own
     const int lds = target >= 100000 ? hog : 0;
-    hipLaunchKernelGGL(p2s_mt_randint_kernel, dim3(1), dim3(128), lds, s, r->state, rng, mask, target, out);
+    hipLaunchKernelGGL(p2s_mt_randint_kernel, dim3(1), dim3(128), lds, s, r->state.get(), rng, mask, target, out);
     P2S_LAUNCH_CHECK("p2s_mt_randint_kernel");
     return P2S_OK;
 }
@@ -550,13 +550,12 @@ int p2s_rng_create(uint32_t seed, int device, p2s_rng_t *out) {
     p2s_mt_seed_host(seed, st);
     p2s_rng_s *r = new p2s_rng_s();
     r->device = device;
-    if (hipMalloc(&r->state, sizeof(st)) != hipSuccess) {
+    if (!r->state.alloc(625)) {
         delete r;
         p2s_set_error("p2s_rng_create: hipMalloc failed");
         return P2S_ENOMEM;
     }
-    if (hipMemcpy(r->state, st, sizeof(st), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(r->state);
+    if (hipMemcpy(r->state.get(), st, sizeof(st), hipMemcpyHostToDevice) != hipSuccess) {
         delete r;
         p2s_set_error("p2s_rng_create: hipMemcpy failed");
         return P2S_EHIP;
@@ -568,14 +567,6 @@ int p2s_rng_create(uint32_t seed, int device, p2s_rng_t *out) {
 int p2s_rng_destroy(p2s_rng_t r) {
     if (!r) return P2S_OK;
     (void)hipSetDevice(r->device);
-    if (r->state) (void)hipFree(r->state);
-    if (r->jump_sup) (void)hipFree(r->jump_sup);
-    if (r->streams) (void)hipFree(r->streams);
-    if (r->tmp) (void)hipFree(r->tmp);
-    if (r->blk_cum) (void)hipFree(r->blk_cum);
-    if (r->meta) (void)hipFree(r->meta);
-    p2s_wc_free_rng(r);
-    p2s_ball_free_rng(r);
     delete r;
     return P2S_OK;
 }
@@ -588,7 +579,7 @@ int p2s_rng_get_state(p2s_rng_t r, uint32_t *mt624_host, int32_t *pos_host, void
         if (rc) return rc;
     }
     uint32_t st[625];
-    P2S_HIP_CHECK(hipMemcpyAsync(st, r->state, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    P2S_HIP_CHECK(hipMemcpyAsync(st, r->state.get(), sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream));
     P2S_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     memcpy(mt624_host, st, 624 * 4);
     *pos_host = (int32_t)st[624];
@@ -605,7 +596,7 @@ int p2s_rng_set_state(p2s_rng_t r, const uint32_t *mt624_host, int32_t pos, void
     uint32_t st[625];
     memcpy(st, mt624_host, 624 * 4);
     st[624] = (uint32_t)pos;
-    P2S_HIP_CHECK(hipMemcpyAsync(r->state, st, sizeof(st), hipMemcpyHostToDevice, (hipStream_t)stream));
+    P2S_HIP_CHECK(hipMemcpyAsync(r->state.get(), st, sizeof(st), hipMemcpyHostToDevice, (hipStream_t)stream));
     P2S_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return P2S_OK;
 }
@@ -637,7 +628,7 @@ int p2s_subsample_shuffle_pad(p2s_rng_t r, p2s_cloud_t c, int64_t nq, int n, int
         }
         P2S_HIP_CHECK(hipMemcpy(c->shuffle_perm, id.data(), id.size() * 4, hipMemcpyHostToDevice));
     }
-    hipLaunchKernelGGL(p2s_shuffle_pad_kernel, dim3(1), dim3(64), 0, s, r->state, c->shuffle_perm, c->d.n, (long long)nq, n,
+    hipLaunchKernelGGL(p2s_shuffle_pad_kernel, dim3(1), dim3(64), 0, s, r->state.get(), c->shuffle_perm, c->d.n, (long long)nq, n,
                        perm_before_dev, ids_out_dev);
     P2S_LAUNCH_CHECK("p2s_shuffle_pad_kernel");
     return P2S_OK;

@@ -10,18 +10,8 @@ void cloudset_note_stream(p2s_cloudset_s *s, hipStream_t st) {
     else s->many_streams = true;
 }
 
-void cloudset_free_buffers(p2s_cloudset_s *s) {
-    if (s->cloud_of_pin) (void)hipHostFree(s->cloud_of_pin);
-    if (s->seg_pin) (void)hipHostFree(s->seg_pin);
-    if (s->cloud_of_dev) (void)hipFree(s->cloud_of_dev);
-    if (s->seg_dev) (void)hipFree(s->seg_dev);
-    s->cloud_of_pin = s->cloud_of_dev = nullptr;
-    s->seg_pin = s->seg_dev = nullptr;
-    s->cap_items = 0;
-}
-
 // Host checks of one call (`who`: its name; `limit`: its k or n, named `what`, which no item's cloud may fall short of),
-// then the per-item cloud ids on the device in s->cloud_of_dev, ordered on `st`.  When this returns P2S_OK the pinned
+// then the per-item cloud ids on the device in s->items.cloud_of_dev, ordered on `st`.  When this returns P2S_OK the pinned
 // buffers are free for writing and the device buffers hold at least nq entries.
 int cloudset_begin(p2s_cloudset_s *s, const char *who, const char *what, const int32_t *cloud_of, int64_t nq, int limit,
                    hipStream_t st) {
@@ -40,28 +30,24 @@ int cloudset_begin(p2s_cloudset_s *s, const char *who, const char *what, const i
     P2S_HIP_CHECK(hipSetDevice(s->device));
     // the per-call buffers are shared by all calls: work of another stream, and the last copy out of the pinned side, first
     if (s->used && s->last != st) P2S_HIP_CHECK(hipStreamSynchronize(s->last));
-    if (s->used) P2S_HIP_CHECK(hipEventSynchronize(s->copied));
-    if (nq > s->cap_items) {
+    if (s->used) P2S_HIP_CHECK(hipEventSynchronize(s->copied.get()));
+    p2s_cloudset_s::Items &b = s->items;
+    if (nq > b.cap) {
         drain_streams(s->streams, s->n_streams, s->many_streams, who);
-        cloudset_free_buffers(s);
+        b = p2s_cloudset_s::Items();
         const int64_t cap = std::max<int64_t>(nq, 1024);
-        if (hipHostMalloc((void **)&s->cloud_of_pin, (size_t)cap * 4) != hipSuccess ||
-            hipHostMalloc((void **)&s->seg_pin, (size_t)cap * sizeof(P2sRandSeg)) != hipSuccess ||
-            hipMalloc((void **)&s->cloud_of_dev, (size_t)cap * 4) != hipSuccess ||
-            hipMalloc((void **)&s->seg_dev, (size_t)cap * sizeof(P2sRandSeg)) != hipSuccess) {
-            (void)hipGetLastError();
-            cloudset_free_buffers(s);
+        if (!p2s_alloc_all(b.cloud_of_pin, cap, b.seg_pin, cap, b.cloud_of_dev, cap, b.seg_dev, cap)) {
             p2s_set_error("%s: allocation of the buffers of %lld items failed", who, (long long)cap);
             return P2S_ENOMEM;
         }
-        s->cap_items = cap;
+        b.cap = cap;
     }
     cloudset_note_stream(s, st);
     s->last = st;
     s->used = true;
-    memcpy(s->cloud_of_pin, cloud_of, (size_t)nq * 4);
-    P2S_HIP_CHECK(hipMemcpyAsync(s->cloud_of_dev, s->cloud_of_pin, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    P2S_HIP_CHECK(hipEventRecord(s->copied, st));
+    memcpy(b.cloud_of_pin.get(), cloud_of, (size_t)nq * 4);
+    P2S_HIP_CHECK(hipMemcpyAsync(b.cloud_of_dev.get(), b.cloud_of_pin.get(), (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    P2S_HIP_CHECK(hipEventRecord(s->copied.get(), st));
     return P2S_OK;
 }
 
@@ -101,9 +87,15 @@ int p2s_cloudset_create(const p2s_cloud_t *clouds, int n_clouds, int device, p2s
         s->min_points = std::min(s->min_points, clouds[i]->d.n);
     }
     const int rc = [&]() -> int {
-        P2S_HIP_CHECK(hipMalloc((void **)&s->table, table.size() * sizeof(CloudDev)));
-        P2S_HIP_CHECK(hipMemcpy(s->table, table.data(), table.size() * sizeof(CloudDev), hipMemcpyHostToDevice));
-        P2S_HIP_CHECK(hipEventCreateWithFlags(&s->copied, hipEventDisableTiming));
+        if (!s->table.alloc(table.size())) {
+            p2s_set_error("p2s_cloudset_create: allocation of the table of %d clouds failed", n_clouds);
+            return P2S_ENOMEM;
+        }
+        P2S_HIP_CHECK(hipMemcpy(s->table.get(), table.data(), table.size() * sizeof(CloudDev), hipMemcpyHostToDevice));
+        if (!s->copied.create(hipEventDisableTiming)) {
+            p2s_set_error("p2s_cloudset_create: hipEventCreateWithFlags failed");
+            return P2S_EHIP;
+        }
         return P2S_OK;
     }();
     if (rc != P2S_OK) {
@@ -118,9 +110,6 @@ int p2s_cloudset_destroy(p2s_cloudset_t s) {
     if (!s) return P2S_OK;
     (void)hipSetDevice(s->device);
     drain_streams(s->streams, s->n_streams, s->many_streams, "p2s_cloudset_destroy");
-    cloudset_free_buffers(s);
-    if (s->table) (void)hipFree(s->table);
-    if (s->copied) (void)hipEventDestroy(s->copied);
     delete s;
     return P2S_OK;
 }
@@ -150,7 +139,7 @@ int p2s_cloudset_knn_patch(p2s_cloudset_t s, const int32_t *cloud_of_host, const
     const int rc = cloudset_begin(s, "p2s_cloudset_knn_patch", "k", cloud_of_host, nq, k, st);
     if (rc) return rc;
     const unsigned grid = (unsigned)std::min<int64_t>(nq, 256 * 64);
-    hipLaunchKernelGGL(p2s_knn_set_kernel, dim3(grid), dim3(64), 0, st, s->table, s->cloud_of_dev, query_dev, (long long)nq, k,
+    hipLaunchKernelGGL(p2s_knn_set_kernel, dim3(grid), dim3(64), 0, st, s->table.get(), s->items.cloud_of_dev.get(), query_dev, (long long)nq, k,
                        ids_out_dev, patch_ps_out_dev, radius_out_dev);
     P2S_LAUNCH_CHECK("p2s_knn_set_kernel");
     return P2S_OK;
@@ -171,6 +160,7 @@ int p2s_cloudset_subsample_uniform(p2s_rng_t r, p2s_cloudset_t s, const int32_t 
     int rc = cloudset_begin(s, "p2s_cloudset_subsample_uniform", "n", cloud_of_host, nq, n, st);
     if (rc) return rc;
     // runs of items whose clouds have the same size are one segment of the stream; a cloud of one point draws nothing
+    P2sRandSeg *const segs = s->items.seg_pin.get();
     int64_t n_segs = 0;
     bool zeros = false;
     for (int64_t i = 0; i < nq; ++i) {
@@ -179,31 +169,31 @@ int p2s_cloudset_subsample_uniform(p2s_rng_t r, p2s_cloudset_t s, const int32_t 
             zeros = true;
             continue;
         }
-        P2sRandSeg *last = n_segs ? &s->seg_pin[n_segs - 1] : nullptr;
+        P2sRandSeg *last = n_segs ? &segs[n_segs - 1] : nullptr;
         if (last && last->rng == rng && last->out_begin + last->count == (long long)i * n) {
             last->count += n;
             continue;
         }
         uint32_t mask = rng;
         mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-        s->seg_pin[n_segs++] = P2sRandSeg{rng, mask, (long long)i * n, (long long)n};
+        segs[n_segs++] = P2sRandSeg{rng, mask, (long long)i * n, (long long)n};
     }
     const long long target = (long long)nq * n;
     if ((rc = p2s_rng_session_close(r, st))) return rc;         // the state lags behind an open session
     if (zeros && ids_out_dev) P2S_HIP_CHECK(hipMemsetAsync(ids_out_dev, 0, (size_t)target * 4, st));
     if (n_segs) {
-        P2S_HIP_CHECK(hipMemcpyAsync(s->seg_dev, s->seg_pin, (size_t)n_segs * sizeof(P2sRandSeg), hipMemcpyHostToDevice, st));
-        P2S_HIP_CHECK(hipEventRecord(s->copied, st));
+        P2S_HIP_CHECK(hipMemcpyAsync(s->items.seg_dev.get(), s->items.seg_pin.get(), (size_t)n_segs * sizeof(P2sRandSeg), hipMemcpyHostToDevice, st));
+        P2S_HIP_CHECK(hipEventRecord(s->copied.get(), st));
         // one workgroup, pure latency: large requests keep a CU to themselves (see p2s_rng_serial_randint)
         constexpr int hog = 120 * 1024;
         (void)hipFuncSetAttribute((const void *)p2s_mt_randint_seg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         const int lds = target >= 100000 ? hog : 0;
-        hipLaunchKernelGGL(p2s_mt_randint_seg_kernel, dim3(1), dim3(128), lds, st, r->state, s->seg_dev, (int)n_segs, ids_out_dev);
+        hipLaunchKernelGGL(p2s_mt_randint_seg_kernel, dim3(1), dim3(128), lds, st, r->state.get(), s->items.seg_dev.get(), (int)n_segs, ids_out_dev);
         P2S_LAUNCH_CHECK("p2s_mt_randint_seg_kernel");
     }
     if (pts_out_dev) {
-        hipLaunchKernelGGL(p2s_gather_set_kernel, dim3((unsigned)((target + 255) / 256)), dim3(256), 0, st, s->table,
-                           s->cloud_of_dev, ids_out_dev, target, n, pts_out_dev);
+        hipLaunchKernelGGL(p2s_gather_set_kernel, dim3((unsigned)((target + 255) / 256)), dim3(256), 0, st, s->table.get(),
+                           s->items.cloud_of_dev.get(), ids_out_dev, target, n, pts_out_dev);
         P2S_LAUNCH_CHECK("p2s_gather_set_kernel");
     }
     return P2S_OK;

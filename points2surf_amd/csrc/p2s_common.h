@@ -21,6 +21,7 @@ void p2s_set_error(const char *fmt, ...);
 // Process-wide grow-only scratch buffer per device (volume / iso-surface stages: ~0.5 ms of hipMalloc + hipFree per
 // call otherwise).  A caller holds the lock for its whole call -- host threads serialise per device -- and synchronises
 // its stream before it returns, so the buffer is idle whenever the lock is free.  p2s_release_scratch() frees it.
+// (The other allocators and which to use when: DESIGN.md, "who owns device memory".)
 constexpr int P2S_MAX_DEVICES = 16;
 class P2sScratchLock {
 public:

@@ -68,7 +68,7 @@ enum Pass { PASS_QSTN, PASS_STN, PASS_MAIN };
 // the branch of `pass` over the points of encoder e: 1 = the sub-sample minus the query point, 0 = the patch
 void fill_branch(ChainBranch &b, const Chunk &c, Pass pass, int e) {
     const p2s_model_s *m = c.m;
-    const float *W = m->blob;
+    const float *W = m->blob.get();
     const p2s_encoder_offsets &eo = m->offs.enc[e];
     const size_t C = c.C;
     if (e == 1) { b.ptsA = nullptr; b.ptsB = c.sub; b.center = c.query; b.P = m->cfg.sub_sample_size; b.P1 = 0; }
@@ -114,7 +114,7 @@ ChainArgs chain_args(const Chunk &c) {
     memset(&a, 0, sizeof(a));
     a.ns = c.prec.pieces;
     a.f16 = c.prec.f16;
-    a.bad_items = c.m->fb.flags;
+    a.bad_items = c.m->fb.flags.get();
     a.piece_stride = (long long)c.m->h_total;
     a.w1_piece_stride = (long long)2 * c.C * 4096;
     return a;
@@ -130,7 +130,7 @@ int launch_chain(ChainArgs &a, const Chunk &c, hipStream_t s, Pass pass = PASS_Q
             a.w3h[slot] = c.m->screen_w(l3, 1 - slot);
             a.w3mu[slot] = c.m->screen_mu(l3, 1 - slot);
         }
-        a.scr_counters = c.m->scr_counters;
+        a.scr_counters = c.m->scr_counters.get();
     }
     return p2s_launch_chain(a, s);
 }
@@ -146,7 +146,7 @@ int fc(GemmArgs &g, const Chunk &c, P2sLayer layer, const float *A, float *out, 
         g.Wh[z] = h16 ? c.m->w16(layer, z) : nullptr;
     }
     g.wh_piece = h16 ? (long long)c.m->h_total : 0;
-    g.bad_rows = h16 ? c.m->fb.flags : nullptr;
+    g.bad_rows = h16 ? c.m->fb.flags.get() : nullptr;
     g.A = A; g.lda = d.K; g.a_z = g.Z == 2 ? (long long)c.C * d.K : 0;
     g.C = out; g.ldc = ldc; g.c_z = c_z; g.N = d.N; g.K = d.K;
     return p2s_launch_gemm(g, s);
@@ -158,23 +158,16 @@ int p2s_model_reserve(p2s_model_s *m, int chunk) {
     if (chunk <= m->ws_chunk) return P2S_OK;
     if (m->ws) {
         P2S_HIP_CHECK(hipDeviceSynchronize());
-        (void)hipFree(m->ws);
-        m->ws = nullptr;
+        m->ws.reset();
         m->ws_chunk = 0;
     }
     const Precision prec = p2s_precision(m->cfg);
     const size_t n = carve(nullptr, m->cfg, prec, 1, false).floats * (size_t)chunk;
-    hipError_t e = hipErrorOutOfMemory;
-    m->ws_stem = false;
-    if (m->stem_reuse && !prec.pieces && stem_floats(m->cfg, chunk) * sizeof(float) <= m->stem_max_bytes) {
-        // with the stem region where it is allowed and fits the device; a chunk that does not get it recomputes the stem
-        e = hipMalloc(&m->ws, carve(nullptr, m->cfg, prec, 1, true).floats * (size_t)chunk * sizeof(float));
-        m->ws_stem = e == hipSuccess;
-        if (e != hipSuccess) (void)hipGetLastError();
-    }
-    if (e != hipSuccess) e = hipMalloc(&m->ws, n * sizeof(float));
-    if (e != hipSuccess) {
-        p2s_set_error("hipMalloc(workspace %zu MB) failed: %s", n * 4 >> 20, hipGetErrorString(e));
+    // with the stem region where it is allowed and fits the device; a chunk that does not get it recomputes the stem
+    m->ws_stem = m->stem_reuse && !prec.pieces && stem_floats(m->cfg, chunk) * sizeof(float) <= m->stem_max_bytes &&
+                 m->ws.alloc(carve(nullptr, m->cfg, prec, 1, true).floats * (size_t)chunk);
+    if (!m->ws_stem && !m->ws.alloc(n)) {
+        p2s_set_error("allocation of the workspace (%zu MB) failed", n * 4 >> 20);
         return P2S_ENOMEM;
     }
     m->ws_chunk = chunk;
@@ -226,8 +219,8 @@ int p2s_run_chunk(p2s_model_s *m, Precision prec, const float *patch, const floa
                   int C, float *logits_out, float *sdf_out, float *feat_local_out, float *feat_global_out,
                   hipStream_t s, long long index0) {
     const p2s_weight_offsets &o = m->offs;
-    const float *W = m->blob;
-    Chunk c = {m, prec, patch, sub, query, nullptr, C, carve(m->ws, m->cfg, prec, C, m->ws_stem && !prec.pieces)};
+    const float *W = m->blob.get();
+    Chunk c = {m, prec, patch, sub, query, nullptr, C, carve(m->ws.get(), m->cfg, prec, C, m->ws_stem && !prec.pieces)};
     const Ws &w = c.w;
     int rc;
     const int ev0 = p2s_prof_mark(m, s);
@@ -290,7 +283,7 @@ int p2s_run_chunk(p2s_model_s *m, Precision prec, const float *patch, const floa
     f.h_piece_stride = (long long)2 * C * 4096;
     f.ns = prec.pieces;
     f.f16 = prec.f16;
-    f.bad_items = prec.f16 ? m->fb.flags : nullptr;
+    f.bad_items = prec.f16 ? m->fb.flags.get() : nullptr;
     f.n_items = C;
     if ((rc = p2s_launch_fold(f, s))) return rc;
     const int ev2 = p2s_prof_mark(m, s);
@@ -335,8 +328,8 @@ int p2s_run_chunk(p2s_model_s *m, Precision prec, const float *patch, const floa
     if (prec.f16 && m->fb.flags) {
         // fp16 pair mode: the inputs of the queries the 16-bit kernels flagged are put aside (the chunk buffers are reused
         // two chunks on); one workgroup per query, all but the flagged ones return at once
-        hipLaunchKernelGGL(p2s_fb_collect_kernel, dim3(C), dim3(256), 0, s, m->fb.flags, m->fb.count, m->fb.cap, patch, sub, query,
-                           radius, m->cfg.points_per_patch * 3, m->cfg.sub_sample_size * 3, index0, m->fb.patch, m->fb.sub, m->fb.query, m->fb.radius, m->fb.index);
+        hipLaunchKernelGGL(p2s_fb_collect_kernel, dim3(C), dim3(256), 0, s, m->fb.flags.get(), m->fb.count.get(), m->fb.cap, patch, sub, query,
+                           radius, m->cfg.points_per_patch * 3, m->cfg.sub_sample_size * 3, index0, m->fb.patch.get(), m->fb.sub.get(), m->fb.query.get(), m->fb.radius.get(), m->fb.index.get());
         P2S_LAUNCH_CHECK("p2s_fb_collect_kernel");
     }
     return P2S_OK;
@@ -348,7 +341,7 @@ extern "C" int p2s_debug_stn_pool(p2s_model_t m, int n_queries, float *out_dev, 
         return P2S_EINVAL;
     }
     P2S_HIP_CHECK(hipSetDevice(m->device));
-    const Ws w = carve(m->ws, m->cfg, p2s_precision(m->cfg), n_queries, false);       // (g_stn comes first)
+    const Ws w = carve(m->ws.get(), m->cfg, p2s_precision(m->cfg), n_queries, false);       // (g_stn comes first)
     P2S_HIP_CHECK(hipMemcpyAsync(out_dev, w.g_stn, (size_t)2 * n_queries * 1024 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return P2S_OK;
 }
@@ -357,7 +350,7 @@ int p2s_fallback_finish(p2s_model_s *m, float *logits_out, float *sdf_out, hipSt
     p2s_model_s::Fallback &fb = m->fb;
     if (!fb.count) return P2S_OK;
     int h = 0;
-    P2S_HIP_CHECK(hipMemcpyAsync(&h, fb.count, 4, hipMemcpyDeviceToHost, s));
+    P2S_HIP_CHECK(hipMemcpyAsync(&h, fb.count.get(), 4, hipMemcpyDeviceToHost, s));
     P2S_HIP_CHECK(hipStreamSynchronize(s));
     if (!h) return P2S_OK;
     if (h > fb.cap || (!logits_out && !sdf_out)) {
@@ -373,11 +366,11 @@ int p2s_fallback_finish(p2s_model_s *m, float *logits_out, float *sdf_out, hipSt
     int rc = P2S_OK;
     for (int i0 = 0; i0 < h && rc == P2S_OK; i0 += m->ws_chunk) {
         const int C = std::min(m->ws_chunk, h - i0);
-        rc = p2s_run_chunk(m, P2S_FP32, fb.patch + i0 * k3, fb.sub + i0 * n3, fb.query + (size_t)i0 * 3, sdf_out ? fb.radius + i0 : nullptr, C,
-                           fb.logits + (size_t)i0 * od, sdf_out ? fb.sdf + i0 : nullptr, nullptr, nullptr, s, 0);
+        rc = p2s_run_chunk(m, P2S_FP32, fb.patch.get() + i0 * k3, fb.sub.get() + i0 * n3, fb.query.get() + (size_t)i0 * 3, sdf_out ? fb.radius.get() + i0 : nullptr, C,
+                           fb.logits.get() + (size_t)i0 * od, sdf_out ? fb.sdf.get() + i0 : nullptr, nullptr, nullptr, s, 0);
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(p2s_fb_scatter_kernel, dim3((h + 255) / 256), dim3(256), 0, s, fb.index, fb.sdf, fb.logits, h, od, sdf_out, logits_out);
+    hipLaunchKernelGGL(p2s_fb_scatter_kernel, dim3((h + 255) / 256), dim3(256), 0, s, fb.index.get(), fb.sdf.get(), fb.logits.get(), h, od, sdf_out, logits_out);
     P2S_LAUNCH_CHECK("p2s_fb_scatter_kernel");
     P2S_HIP_CHECK(hipStreamSynchronize(s));
     return P2S_OK;

@@ -1,25 +1,26 @@
 // Handle definitions shared by the API translation units.
 #pragma once
 #include "p2s_common.h"
+#include "p2s_devmem.h"
 #include <vector>
 #include <cstddef>
 
 // per-shape pipeline buffers (p2s_pipeline.hip): owned by the model handle, grown on demand, reused across
 // shapes, released by p2s_model_destroy -- no allocation and no leak on the per-shape path
 struct PipeBuffers {
-    float *patch[2] = {};           // [C][k][3]
-    float *radius[2] = {};          // [C]
-    int32_t *sub_ids[2] = {};       // [C][n]
-    float *sub[2] = {};             // [C][n][3]
-    float *qrot[2] = {};            // [C][3]   rotated query points (GT-query pass)
-    double *rot[2] = {};            // [C][9]   per-query rotation (GT-query pass)
-    hipEvent_t ready[2] = {};       // data path of the buffer finished (aux stream)
-    hipEvent_t freed[2] = {};       // the gather has read the sub-sample ids of the buffer (compute stream)
-    hipEvent_t done[2] = {};        // encoders finished reading the buffer (main stream)
-    hipEvent_t ball_ready[2] = {};  // fixed-radius patch of the buffer finished (ball stream)
-    hipEvent_t grid = nullptr;
-    int32_t *knn_ids[2] = {};       // [C][k]   } only for clouds with fewer points than the sub-sample
-    int32_t *perm[2] = {};          // [C][N]   } (shape.pts is shuffled in place by every query)
+    DevBuf<float> patch[2];         // [C][k][3]
+    DevBuf<float> radius[2];        // [C]
+    DevBuf<int32_t> sub_ids[2];     // [C][n]
+    DevBuf<float> sub[2];           // [C][n][3]
+    DevBuf<float> qrot[2];          // [C][3]   rotated query points (GT-query pass)
+    DevBuf<double> rot[2];          // [C][9]   per-query rotation (GT-query pass)
+    DevEvent ready[2];              // data path of the buffer finished (aux stream)
+    DevEvent freed[2];              // the gather has read the sub-sample ids of the buffer (compute stream)
+    DevEvent done[2];               // encoders finished reading the buffer (main stream)
+    DevEvent ball_ready[2];         // fixed-radius patch of the buffer finished (ball stream)
+    DevEvent grid;
+    DevBuf<int32_t> knn_ids[2];     // [C][k]   } only for clouds with fewer points than the sub-sample
+    DevBuf<int32_t> perm[2];        // [C][N]   } (shape.pts is shuffled in place by every query)
     int cap_chunk = 0, cap_k = 0, cap_n = 0, cap_small = 0;
 };
 
@@ -69,40 +70,45 @@ struct p2s_model_s {
     const p2s_model_cfg cfg;
     const p2s_weight_offsets offs;
     const int device;
-    float *blob = nullptr;
+    // auxiliary stream: the data path (kNN, sub-sample) of chunk i+1, i+2 overlaps the encoders of chunk i.  The streams are
+    // declared in front of every buffer: members go in reverse order, so the streams are destroyed after the buffers are released
+    DevStream aux;                 // high-priority stream of the sub-sample generator
+    DevStream ball;                // fixed-radius models: the serial walk along the first generator's stream (one wave) -- its own
+                                   // stream so that it runs beside the sub-sample kernels of the auxiliary stream, not behind them
+    DevBuf<float> blob;
     // 16-bit encoder modes: 16-bit B fragments of the layers p2s_kind_packed() names, converted once at creation
-    unsigned short *blob_h = nullptr;      // [pieces][h_total]
+    DevBuf<unsigned short> blob_h;         // [pieces][h_total]
     size_t h_total = 0;
     size_t h_off[P2S_LAYERS][2] = {};      // of slice 0 / 1 of a layer within a piece (a layer without slices: the same twice)
     p2s_model_s(const p2s_model_cfg &c, const p2s_weight_offsets &o, int dev) : cfg(c), offs(o), device(dev) {}
     // the operands of `layer`, slice z: fp32 fragments / bias in blob, piece 0 of the 16-bit fragments in blob_h
-    const float *w32(P2sLayer layer, int z) const { return blob + offset(p2s_layers[layer].w + z * p2s_layers[layer].slice); }
-    const float *bias(P2sLayer layer, int z) const { return blob + offset(p2s_layers[layer].b + z * p2s_layers[layer].slice); }
-    const unsigned short *w16(P2sLayer layer, int z) const { return blob_h + h_off[layer][z]; }
+    const float *w32(P2sLayer layer, int z) const { return blob.get() + offset(p2s_layers[layer].w + z * p2s_layers[layer].slice); }
+    const float *bias(P2sLayer layer, int z) const { return blob.get() + offset(p2s_layers[layer].b + z * p2s_layers[layer].slice); }
+    const unsigned short *w16(P2sLayer layer, int z) const { return blob_h.get() + h_off[layer][z]; }
     uint64_t offset(size_t member) const { return *reinterpret_cast<const uint64_t *>(reinterpret_cast<const char *>(&offs) + member); }
     // screened conv3 of the fp32 kernel (p2s_chain_screen.inl; mode 0 only): the conv3
     // layers of the STN and main trunks (layer = L_S3 / L_M3, encoder z) rounded to fp16, as fragments [2][2][P2S_SCR_PIECE], and
     // their margin coefficients [2][2][1024], built at creation; NULL: the dense conv3 (P2S_CONV3_DENSE=1, a sym_op='sum' main
     // trunk keeps it for that pass, a conv3 weight beyond the half range for the model)
-    unsigned short *scr_w3h = nullptr;
-    float *scr_mu = nullptr;
-    unsigned long long *scr_counters = nullptr;     // device [3]: fp32 chains run, items re-run densely, items -- per call
-    const unsigned short *screen_w(P2sLayer layer, int z) const { return scr_w3h + ((layer == L_M3 ? 2 : 0) + z) * P2S_SCR_PIECE; }
-    const float *screen_mu(P2sLayer layer, int z) const { return scr_mu + ((layer == L_M3 ? 2 : 0) + z) * 1024; }
+    DevBuf<unsigned short> scr_w3h;
+    DevBuf<float> scr_mu;
+    DevBuf<unsigned long long> scr_counters;        // device [3]: fp32 chains run, items re-run densely, items -- per call
+    const unsigned short *screen_w(P2sLayer layer, int z) const { return scr_w3h.get() + ((layer == L_M3 ? 2 : 0) + z) * P2S_SCR_PIECE; }
+    const float *screen_mu(P2sLayer layer, int z) const { return scr_mu.get() + ((layer == L_M3 ? 2 : 0) + z) * 1024; }
     // fp16 pair mode: queries with an activation beyond the half range are flagged by the 16-bit kernels, collected per
     // chunk (inputs copied aside) and re-run through the fp32 kernels at the end of the same call (ModelCall::finish)
     struct Fallback {
-        int *flags = nullptr;              // [max_chunk] per query of the chunk in flight
-        int *count = nullptr;              // queries collected by the call (may run past cap: overflow)
-        float *patch = nullptr, *sub = nullptr, *query = nullptr, *radius = nullptr;   // [cap] inputs of the collected queries
-        long long *index = nullptr;        // [cap] position in the call's output arrays
-        float *sdf = nullptr, *logits = nullptr;                                       // [cap] results of the fp32 run
+        DevBuf<int> flags;                 // [max_chunk] per query of the chunk in flight
+        DevBuf<int> count;                 // queries collected by the call (may run past cap: overflow)
+        DevBuf<float> patch, sub, query, radius;   // [cap] inputs of the collected queries
+        DevBuf<long long> index;           // [cap] position in the call's output arrays
+        DevBuf<float> sdf, logits;         // [cap] results of the fp32 run
         int cap = 0;
     } fb;
     // one-shot capture of the decoder logits of the next pipeline call (p2s_model_capture_logits; the drop-in's tie report)
     float *logits_capture = nullptr;
     int64_t logits_capacity = 0;
-    float *ws = nullptr;      // per-chunk workspace, grown on demand
+    DevBuf<float> ws;         // per-chunk workspace, grown on demand
     int ws_chunk = 0;
     // stem reuse: the main encoder pass starts at conv1 from the conv0b output the STN pass saved in the
     // workspace.  Decided once, at creation: the model's own precision is fp32, its conv3 is screened and its main pass pools by
@@ -116,27 +122,22 @@ struct p2s_model_s {
                               // of a chunk -- four drains of the chip -- weigh half as much; 12288: 182.1 k)
     // profiling: HIP events recorded on the launch stream, no host synchronisation until collect
     bool profiling = false;
-    std::vector<hipEvent_t> evpool;
+    std::vector<DevEvent> evpool;
     int ev_used = 0;
     struct Span { int stage, a, b; };
     std::vector<Span> spans;
     p2s_counters counters = {};
-    // auxiliary stream: the data path (kNN, sub-sample) of chunk i+1, i+2 overlaps the encoders of chunk i
-    hipStream_t aux = nullptr;     // high-priority stream of the sub-sample generator
-    hipStream_t ball = nullptr;    // fixed-radius models: the serial walk along the first generator's stream (one wave) -- its own
-                                   // stream so that it runs beside the sub-sample kernels of the auxiliary stream, not behind them
     bool overlap = true;
     PipeBuffers pipe;
     int fault_chunk = -1;          // test hook (p2s_debug_fault_chunk): fail with P2S_EHIP before this chunk
     // workers mode (p2s_streams.hip): the stream-ordered queries, their source indices and the SDF / logits produced in that
     // order, before the scatter to the caller's buffers; grown on demand
     struct Workers {
-        float *q = nullptr, *sdf = nullptr, *logits = nullptr;
-        int64_t *src = nullptr;
+        DevBuf<float> q, sdf, logits;
+        DevBuf<int64_t> src;
         int64_t cap = 0;
     } wk;
 };
-void p2s_pipe_free(p2s_model_s *m);
 
 // consecutive pipeline queries and their generators (first: patch choice / rotation, NULL if unused): dataset mode is one
 // segment, workers mode (p2s_streams.hip) one per non-empty stream
@@ -145,7 +146,6 @@ struct P2sSegment {
     p2s_rng_s *first;
     int64_t rows;
 };
-void p2s_workers_free(p2s_model_s *m);
 int p2s_workers_reserve(p2s_model_s *m, int64_t n);
 // validation of a p2s_worker_streams (need_first: the call draws from the first generators); counts: the per-stream query
 // counts of n queries at ws->first_position; segs: the non-empty streams as pipeline segments
@@ -255,13 +255,17 @@ struct p2s_cloudset_s {
     int device = 0;
     std::vector<int> n_points;     // per cloud (host)
     int min_points = 0;
-    CloudDev *table = nullptr;     // device [n_clouds]
+    DevBuf<CloudDev> table;        // device [n_clouds]
     // per-call inputs: filled in pinned host memory, copied on the call's stream; `copied` is recorded behind the copies
     // and waited for before the pinned side is written again
-    int32_t *cloud_of_pin = nullptr, *cloud_of_dev = nullptr;
-    P2sRandSeg *seg_pin = nullptr, *seg_dev = nullptr;
-    int64_t cap_items = 0;
-    hipEvent_t copied = nullptr;
+    struct Items {
+        PinnedBuf<int32_t> cloud_of_pin;
+        PinnedBuf<P2sRandSeg> seg_pin;
+        DevBuf<int32_t> cloud_of_dev;
+        DevBuf<P2sRandSeg> seg_dev;
+        int64_t cap = 0;
+    } items;
+    DevEvent copied;
     hipStream_t last = nullptr;    // stream of the last call: a call on another one waits for it (the buffers are shared)
     bool used = false;
     hipStream_t streams[4] = {};   // as p2s_cloud_s: drained by destroy
@@ -271,7 +275,7 @@ struct p2s_cloudset_s {
 
 struct p2s_rng_s {
     int device = 0;
-    uint32_t *state = nullptr;     // [624] mt + [1] pos
+    DevBuf<uint32_t> state;        // [624] mt + [1] pos
     // parallel generation (GF(2) jump-ahead), optional: tables uploaded by p2s_rng_set_jump_tables
     int levels_max = 0;            // jump tables uploaded (sessions use 2^levels_max streams)
     int levels_alloc = 0;          // tmp / blk_cum sized for 2^levels_alloc streams
@@ -281,24 +285,28 @@ struct p2s_rng_s {
     uint32_t sess_rng = 0, sess_mask = 0;
     long long sess_cursor = 0;     // mode 1: values handed out; mode 2: conservative word estimate
     long long sess_limit = 0;
-    uint16_t *jump_sup = nullptr;  // concatenated supports of the jump polynomials
+    DevBuf<uint16_t> jump_sup;     // concatenated supports of the jump polynomials
     int jump_off[16] = {};         // offset / count per level
     int jump_cnt[16] = {};
-    uint32_t *streams = nullptr;   // [S][624] block states
-    uint32_t *tmp = nullptr;       // [S][B*624] accepted values per stream
-    int *blk_cum = nullptr;        // [S][B] cumulative accepted count per block
-    long long *meta = nullptr;     // [S] offsets + locate record + sticky error flag + raw-request record
+    DevBuf<uint32_t> streams;      // [S][624] block states
+    DevBuf<uint32_t> tmp;          // [S][B*624] accepted values per stream
+    DevBuf<int> blk_cum;           // [S][B] cumulative accepted count per block
+    DevBuf<long long> meta;        // [S] offsets + locate record + sticky error flag + raw-request record
     // weighted sub-sample workspace (p2s_wchoice.hip), grown on demand
-    double *wc_S = nullptr;        // [C][n]   exact prefix sums of the probabilities
-    void *wc_T = nullptr;          // [C][K]   guide records of the cdf (16 B each)
-    double *wc_sc = nullptr;       // [C]      per-query scalars (stot, word offset, pmax, dmax + sum, mu)
-    void *wc_spec = nullptr;       // offsets pass: ctl, window origins, verdicts [SP_B][SP_W], tentative path, saved windows, scratch
-    unsigned short *wc_J = nullptr; // [2 SP_B][SP_W] ruler of jump tables of the offsets chain (p2s_wchoice.hip)
-    size_t wc_cap_q = 0, wc_cap_n = 0, wc_cap_k = 0;
+    struct WChoice {
+        DevBuf<double> S;          // [C][n]   exact prefix sums of the probabilities
+        DevBuf<void> T;            // [C][K]   guide records of the cdf (16 B each)
+        DevBuf<double> sc;         // [C][5]   per-query scalars (stot, word offset, pmax, dmax + sum, mu)
+        DevBuf<void> spec;         // offsets pass: ctl, window origins, verdicts [SP_B][SP_W], tentative path, saved windows, scratch
+        DevBuf<unsigned short> J;  // [2 SP_B][SP_W] ruler of jump tables of the offsets chain (p2s_wchoice.hip)
+        size_t cap_q = 0, cap_n = 0, cap_k = 0;
+        DevBuf<long long> stats;   // [16] development counters (P2S_WC_STATS)
+    } wc;
     // fixed-radius patches (p2s_ball.hip): hit counts of a shape's queries (device + pinned host), batch work space
-    int32_t *ball_counts_dev = nullptr, *ball_counts_host = nullptr;
+    DevBuf<int32_t> ball_counts_dev;
+    PinnedBuf<int32_t> ball_counts_host;
     size_t ball_counts_cap = 0;
-    void *ball_ws = nullptr;
+    DevBuf<void> ball_ws;
     size_t ball_ws_bytes = 0;
 };
 
@@ -321,9 +329,7 @@ long long *p2s_rng_raw_meta(p2s_rng_s *r);                     // device: [0] wo
 int p2s_rng_session_close(p2s_rng_s *r, hipStream_t s);        // advance the generator to the cursor; no-op if closed
 int p2s_rng_session_randint(p2s_rng_s *r, uint32_t rng, uint32_t mask, long long target, int32_t *out, hipStream_t s);
 int p2s_rng_session_raw(p2s_rng_s *r, long long need_words, hipStream_t s);
-void p2s_wc_free_rng(p2s_rng_s *r);               // p2s_wchoice.hip workspace
 // fixed-radius patches (p2s_ball.hip)
-void p2s_ball_free_rng(p2s_rng_s *r);
 int p2s_cloud_kd_prepare(p2s_cloud_s *c);
 int p2s_ball_counts_to_host(p2s_rng_s *r, p2s_cloud_s *c, const float *q_dev, int64_t nq, double radius, int32_t **count_dev,
                             const int32_t **count_host, hipStream_t s);

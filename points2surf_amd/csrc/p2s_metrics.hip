@@ -252,7 +252,7 @@ extern "C" int p2s_rng_random_sample(p2s_rng_t r, int64_t n, double *out_dev, vo
         const int rc = p2s_rng_session_raw(r, 2 * cur, s);
         if (rc) return rc;
         long long *meta = p2s_rng_raw_meta(r);
-        hipLaunchKernelGGL(rs_sample_kernel, dim3((unsigned)((cur + 255) / 256)), dim3(256), 0, s, r->tmp, meta, cap, cur, out_dev + done,
+        hipLaunchKernelGGL(rs_sample_kernel, dim3((unsigned)((cur + 255) / 256)), dim3(256), 0, s, r->tmp.get(), meta, cap, cur, out_dev + done,
                            meta + 1);
         hipLaunchKernelGGL(rs_advance_kernel, dim3(1), dim3(1), 0, s, meta, 2 * cur);
         P2S_LAUNCH_CHECK("rs_sample_kernel");
@@ -271,12 +271,12 @@ extern "C" int p2s_mesh_sample_surface(const float *verts_dev, const int32_t *fa
     if (p2s_device_count() <= device || device < 0) return P2S_ENODEVICE;
     P2S_HIP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
-    double *cum = nullptr;
-    if (hipMalloc(&cum, (size_t)n_faces * 8) != hipSuccess) {
-        (void)hipGetLastError();
+    DevBuf<double> cum_buf;
+    if (!cum_buf.alloc(n_faces)) {
         p2s_set_error("p2s_mesh_sample_surface: hipMalloc failed");
         return P2S_ENOMEM;
     }
+    double *cum = cum_buf.get();
     hipLaunchKernelGGL(mesh_area_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, s, verts_dev, faces_dev, (long long)n_faces, cum);
     hipLaunchKernelGGL(scan_f64_kernel, dim3(1), dim3(1024), 0, s, cum, (long long)n_faces);
     if (n_samples > 0)
@@ -284,8 +284,8 @@ extern "C" int p2s_mesh_sample_surface(const float *verts_dev, const int32_t *fa
                            (long long)n_faces, cum, u_dev, (long long)n_samples, pts_out_dev, face_out_dev);
     double total = 0.0;
     hipError_t e = hipMemcpyAsync(&total, cum + n_faces - 1, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(cum);
+    const hipError_t drained = hipStreamSynchronize(s);      // whatever e says: cum_buf is freed when this call returns
+    if (e == hipSuccess) e = drained;
     if (e != hipSuccess) {
         p2s_set_error("p2s_mesh_sample_surface: %s", hipGetErrorString(e));
         return P2S_EHIP;
@@ -309,19 +309,14 @@ extern "C" int p2s_points_remove_close(const float *pts_dev, int64_t m, double r
     if (m == 0) return P2S_OK;
     P2S_HIP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
-    char *scratch = nullptr;
-    if (hipMalloc(&scratch, (size_t)m * 5 + 64) != hipSuccess) {
-        (void)hipGetLastError();
+    DevBuf<char> scratch;
+    DevBuf<int> n_buf;
+    if (!p2s_alloc_all(scratch, (size_t)m * 5 + 64, n_buf, 4)) {
         p2s_set_error("p2s_points_remove_close: hipMalloc failed");
         return P2S_ENOMEM;
     }
-    int *degree = (int *)scratch;
+    int *degree = (int *)scratch.get(), *n_dev = n_buf.get();
     unsigned char *keep = (unsigned char *)(degree + m);
-    int *n_dev = nullptr;
-    if (hipMalloc(&n_dev, 16) != hipSuccess) {
-        (void)hipFree(scratch);
-        return P2S_ENOMEM;
-    }
     (void)hipMemsetAsync(keep, 1, (size_t)m, s);
     const unsigned g = (unsigned)((m + 255) / 256);
     hipLaunchKernelGGL(close_degree_kernel, dim3(g), dim3(256), 0, s, pts_dev, (int)m, radius * radius, degree);
@@ -330,9 +325,8 @@ extern "C" int p2s_points_remove_close(const float *pts_dev, int64_t m, double r
                        pts_out_dev, n_dev);
     int h = 0;
     hipError_t e = hipMemcpyAsync(&h, n_dev, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(scratch);
-    (void)hipFree(n_dev);
+    const hipError_t drained = hipStreamSynchronize(s);      // whatever e says: the buffers are freed when this call returns
+    if (e == hipSuccess) e = drained;
     if (e != hipSuccess) {
         p2s_set_error("p2s_points_remove_close: %s", hipGetErrorString(e));
         return P2S_EHIP;
@@ -349,18 +343,17 @@ extern "C" int p2s_nn_distance_stats(p2s_cloud_t target, const float *query_dev,
     }
     P2S_HIP_CHECK(hipSetDevice(target->device));
     hipStream_t s = (hipStream_t)stream;
-    char *scratch = nullptr;
-    if (hipMalloc(&scratch, (size_t)n * 12 + 64) != hipSuccess) {
-        (void)hipGetLastError();
+    DevBuf<char> scratch;
+    if (!scratch.alloc((size_t)n * 12 + 64)) {
         p2s_set_error("p2s_nn_distance_stats: hipMalloc failed");
         return P2S_ENOMEM;
     }
-    double *dist = (double *)scratch;
+    double *dist = (double *)scratch.get();
     int *ids = (int *)(dist + n);
     double *red = (double *)(((uintptr_t)(ids + n) + 15) & ~(uintptr_t)15);
     int rc = p2s_knn_patch(target, query_dev, n, 1, ids, nullptr, nullptr, stream);      // exact (float64 ranking)
     if (rc) {
-        (void)hipFree(scratch);
+        (void)hipStreamSynchronize(s);      // what the search queued may still write ids: drained before scratch is freed
         return rc;
     }
     hipLaunchKernelGGL(pair_distance_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, query_dev, target->d.pts, ids, (long long)n,
@@ -369,8 +362,8 @@ extern "C" int p2s_nn_distance_stats(p2s_cloud_t target, const float *query_dev,
     double h[2] = {0.0, 0.0};
     hipError_t e = hipMemcpyAsync(h, red, 16, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && dist_out_dev) e = hipMemcpyAsync(dist_out_dev, dist, (size_t)n * 8, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(scratch);
+    const hipError_t drained = hipStreamSynchronize(s);      // whatever e says: scratch is freed when this call returns
+    if (e == hipSuccess) e = drained;
     if (e != hipSuccess) {
         p2s_set_error("p2s_nn_distance_stats: %s", hipGetErrorString(e));
         return P2S_EHIP;

@@ -17,26 +17,6 @@
 #include <cstring>
 #include <cstdlib>
 
-void p2s_pipe_free(p2s_model_s *m) {
-    PipeBuffers &b = m->pipe;
-    for (int i = 0; i < 2; ++i) {
-        if (b.patch[i]) (void)hipFree(b.patch[i]);
-        if (b.radius[i]) (void)hipFree(b.radius[i]);
-        if (b.sub_ids[i]) (void)hipFree(b.sub_ids[i]);
-        if (b.sub[i]) (void)hipFree(b.sub[i]);
-        if (b.qrot[i]) (void)hipFree(b.qrot[i]);
-        if (b.knn_ids[i]) (void)hipFree(b.knn_ids[i]);
-        if (b.perm[i]) (void)hipFree(b.perm[i]);
-        if (b.rot[i]) (void)hipFree(b.rot[i]);
-        if (b.ready[i]) (void)hipEventDestroy(b.ready[i]);
-        if (b.freed[i]) (void)hipEventDestroy(b.freed[i]);
-        if (b.done[i]) (void)hipEventDestroy(b.done[i]);
-        if (b.ball_ready[i]) (void)hipEventDestroy(b.ball_ready[i]);
-    }
-    if (b.grid) (void)hipEventDestroy(b.grid);
-    b = PipeBuffers();
-}
-
 namespace {
 
 int pipe_reserve(p2s_model_s *m, int C, int k, int n, bool small) {
@@ -45,22 +25,16 @@ int pipe_reserve(p2s_model_s *m, int C, int k, int n, bool small) {
     C = std::max(C, b.cap_chunk);
     small = small || b.cap_small;
     P2S_HIP_CHECK(hipDeviceSynchronize());
-    p2s_pipe_free(m);
-    bool ok = hipEventCreateWithFlags(&b.grid, hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < 2 && ok; ++i) {
-        ok = hipMalloc(&b.patch[i], (size_t)C * k * 12) == hipSuccess && hipMalloc(&b.radius[i], (size_t)C * 4) == hipSuccess &&
-             hipMalloc(&b.sub_ids[i], (size_t)C * n * 4) == hipSuccess && hipMalloc(&b.sub[i], (size_t)C * n * 12) == hipSuccess &&
-             hipMalloc(&b.qrot[i], (size_t)C * 12) == hipSuccess && hipMalloc(&b.rot[i], (size_t)C * 72) == hipSuccess &&
-             (!small || (hipMalloc(&b.knn_ids[i], (size_t)C * k * 4) == hipSuccess &&
-                         hipMalloc(&b.perm[i], (size_t)C * n * 4) == hipSuccess)) &&
-             hipEventCreateWithFlags(&b.ready[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&b.freed[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&b.done[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&b.ball_ready[i], hipEventDisableTiming) == hipSuccess;
-    }
+    b = PipeBuffers();
+    const size_t Ck = (size_t)C * k, Cn = (size_t)C * n;
+    bool ok = b.grid.create(hipEventDisableTiming);
+    for (int i = 0; i < 2 && ok; ++i)
+        ok = p2s_alloc_all(b.patch[i], Ck * 3, b.radius[i], C, b.sub_ids[i], Cn, b.sub[i], Cn * 3, b.qrot[i], (size_t)C * 3, b.rot[i],
+                           (size_t)C * 9, b.knn_ids[i], small ? Ck : 0, b.perm[i], small ? Cn : 0) &&
+             b.ready[i].create(hipEventDisableTiming) && b.freed[i].create(hipEventDisableTiming) &&
+             b.done[i].create(hipEventDisableTiming) && b.ball_ready[i].create(hipEventDisableTiming);
     if (!ok) {
-        (void)hipGetLastError();
-        p2s_pipe_free(m);
+        b = PipeBuffers();
         p2s_set_error("p2s pipeline: allocation of the chunk buffers failed (chunk %d)", C);
         return P2S_ENOMEM;
     }
@@ -172,7 +146,7 @@ extern "C" int p2s_random_rotations(p2s_rng_t r, int64_t n, double *rot_out_dev,
         const int rc = p2s_rng_session_raw(r, 6 * cur, s);
         if (rc) return rc;
         long long *meta = p2s_rng_raw_meta(r);
-        hipLaunchKernelGGL(p2s_rand_rot_kernel, dim3((unsigned)((cur + 255) / 256)), dim3(256), 0, s, r->tmp, meta, cap, cur,
+        hipLaunchKernelGGL(p2s_rand_rot_kernel, dim3((unsigned)((cur + 255) / 256)), dim3(256), 0, s, r->tmp.get(), meta, cap, cur,
                            rot_out_dev + (size_t)done * 9, meta + 1);
         hipLaunchKernelGGL(p2s_advance_cursor_kernel, dim3(1), dim3(1), 0, s, meta, 6 * cur);
         P2S_LAUNCH_CHECK("p2s_rand_rot_kernel");
@@ -208,6 +182,17 @@ extern "C" int p2s_debug_fault_chunk(p2s_model_t m, int chunk_index) {
     return P2S_OK;
 }
 
+// a model-owned stream of the highest queue priority
+static int own_stream(DevStream &st) {
+    int lo = 0, hi = 0;
+    P2S_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    if (!st.create(hipStreamNonBlocking, hi)) {
+        p2s_set_error("p2s pipeline: hipStreamCreateWithPriority failed");
+        return P2S_EHIP;
+    }
+    return P2S_OK;
+}
+
 // queries q [nq][3] (nq > 0) through the double-buffered pipeline, consecutive segments segs[i].rows of them on their own
 // generators.  rotate: GT-query pass.  sdf_out [nq], logits_out [nq][output_dim] (may be NULL).  Drains every stream it used
 // before it returns, on success too.
@@ -217,32 +202,25 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, const P2sSegment *segs, 
     const double ball_r = m->cfg.patch_radius;
     const bool ball = ball_r > 0.0;                         // patch = points within a fixed radius (p2s_ball.hip)
     const int k = m->cfg.points_per_patch, n = m->cfg.sub_sample_size;
+    int rc;
     // default chunk: 8192 queries, except the distance-weighted sub-sample next to the fp32 encoders: 4096 (its generator works
     // in batches of 4096 queries; fp32, test shape at 256^3, r05: 2048 / 4096 / 6144 / 8192 queries: 110.8 / 112.1 / 111.6 /
     // 112.2 k queries/s -- the smaller one for its table memory; fp16 pair: 1024 / 2048 / 4096 / 8192: 250.6 / 261.4 / 261.9 /
     // 266.8 k: until r04 the auxiliary stream's chain kernel waited milliseconds for a drained CU and 2048 was best)
     if (chunk <= 0) chunk = (weighted && !m->cfg.encoder_bf16) ? std::min(m->max_chunk, 4096) : m->max_chunk;
     chunk = std::min(chunk, m->max_chunk);
-    if (m->overlap && !m->aux) {
-        // high queue priority: the data-path kernels are tiny next to the encoder kernel and must not queue
-        // behind its ~8k workgroups for a free CU slot.  (Giving the stream its own CUs with a CU mask was
-        // measured slower: the masked compute stream lost far more than the masked-off CUs.)
-        int lo = 0, hi = 0;
-        P2S_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        P2S_HIP_CHECK(hipStreamCreateWithPriority(&m->aux, hipStreamNonBlocking, hi));
-    }
-    hipStream_t sa = m->overlap ? m->aux : s;
+    // high queue priority: the data-path kernels are tiny next to the encoder kernel and must not queue
+    // behind its ~8k workgroups for a free CU slot.  (Giving the stream its own CUs with a CU mask was
+    // measured slower: the masked compute stream lost far more than the masked-off CUs.)
+    if (m->overlap && !m->aux && (rc = own_stream(m->aux))) return rc;
+    hipStream_t sa = m->overlap ? m->aux.get() : s;
     // (kNN + gather of chunk i run on the compute stream, in front of its encoders: on a third stream under the encoders of
     //  chunk i - 1 they were measured to cost the encoder launches exactly what they cost alone -- r03: 177.6 vs 177.3 k
     //  queries/s -- so the simpler order stays and the encoder launch durations (roofline) are those of the kernel alone)
     // fixed radius: the walk along the first generator's stream is ONE wave for tens of ms per chunk; on the auxiliary
     // stream it would sit in front of (or behind) the sub-sample's all-CU kernels, on its own stream it runs beside them
     const bool ball_own = m->cfg.patch_radius > 0.0 && m->overlap;
-    if (ball_own && !m->ball) {
-        int lo = 0, hi = 0;
-        P2S_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        P2S_HIP_CHECK(hipStreamCreateWithPriority(&m->ball, hipStreamNonBlocking, hi));
-    }
+    if (ball_own && !m->ball && (rc = own_stream(m->ball))) return rc;
     // the handle remembers only the CALLER's stream.  The model-owned streams (aux / prep / ball) are drained by this
     // function on every exit (fail(), and the guard below as a backstop): a cloud handle must not keep, let alone
     // synchronise, a stream of a model that may be destroyed before it
@@ -253,8 +231,8 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, const P2sSegment *segs, 
         bool drained = false;
         ~QuietGuard() {
             if (!drained) {        // (the model's own streams: an error here is a real fault and stays pending)
-                if (m->aux) (void)hipStreamSynchronize(m->aux);
-                if (m->ball) (void)hipStreamSynchronize(m->ball);
+                if (m->aux) (void)hipStreamSynchronize(m->aux.get());
+                if (m->ball) (void)hipStreamSynchronize(m->ball.get());
             }
             --c->foreign_streams_quiet;
         }
@@ -269,8 +247,7 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, const P2sSegment *segs, 
                       "GT-query pass) and a cloud with at least sub_sample_size points");
         return P2S_EINVAL;
     }
-    int rc = pipe_reserve(m, C, k, n, small);
-    if (rc) return rc;
+    if ((rc = pipe_reserve(m, C, k, n, small))) return rc;
     rc = p2s_model_reserve(m, C);
     if (rc) return rc;
     PipeBuffers &b = m->pipe;
@@ -281,7 +258,7 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, const P2sSegment *segs, 
         quiet.drained = true;
         const hipError_t e1 = hipStreamSynchronize(s);
         hipError_t e2 = (sa != s) ? hipStreamSynchronize(sa) : hipSuccess;
-        const hipError_t e3 = m->ball ? hipStreamSynchronize(m->ball) : hipSuccess;
+        const hipError_t e3 = m->ball ? hipStreamSynchronize(m->ball.get()) : hipSuccess;
         if (e2 == hipSuccess) e2 = e3;
         if (code == P2S_OK && (e1 != hipSuccess || e2 != hipSuccess)) {
             p2s_set_error("p2s pipeline: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
@@ -297,11 +274,11 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, const P2sSegment *segs, 
             return fail(P2S_EHIP);                                                                         \
         }                                                                                                  \
     } while (0)
-    hipStream_t sbl = ball_own ? m->ball : sa;        // stream of the fixed-radius patch work
+    hipStream_t sbl = ball_own ? m->ball.get() : sa;        // stream of the fixed-radius patch work
     if (sa != s) {
-        PIPE_HIP(hipEventRecord(b.grid, s));
-        PIPE_HIP(hipStreamWaitEvent(sa, b.grid, 0));
-        if (sbl != sa) PIPE_HIP(hipStreamWaitEvent(sbl, b.grid, 0));
+        PIPE_HIP(hipEventRecord(b.grid.get(), s));
+        PIPE_HIP(hipStreamWaitEvent(sa, b.grid.get(), 0));
+        if (sbl != sa) PIPE_HIP(hipStreamWaitEvent(sbl, b.grid.get(), 0));
     }
 
     // fixed radius: the number of points in every query's ball, on the host too (batch sizes and the random words each
@@ -334,13 +311,13 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, const P2sSegment *segs, 
         const int bi = (int)(ci % nbuf);
         const int64_t q0 = ci * C;
         const int cur = (int)std::min<int64_t>(C, nq - q0);
-        if (ci >= nbuf && sa != s) PIPE_HIP(hipStreamWaitEvent(sa, b.freed[bi], 0));
+        if (ci >= nbuf && sa != s) PIPE_HIP(hipStreamWaitEvent(sa, b.freed[bi].get(), 0));
         const int e0 = p2s_prof_mark(m, sa);
         int rc2 = pieces(q0, cur, [&](p2s_rng_s *rs, p2s_rng_s *, int64_t off, int64_t row, int64_t cnt) -> int {
             const float *qp = q + (size_t)row * 3;
-            int32_t *ids = b.sub_ids[bi] + (size_t)off * n;
+            int32_t *ids = b.sub_ids[bi].get() + (size_t)off * n;
             if (small)
-                return p2s_subsample_shuffle_pad(rs, c, cnt, n, b.perm[bi] + (size_t)off * n, ids, sa);
+                return p2s_subsample_shuffle_pad(rs, c, cnt, n, b.perm[bi].get() + (size_t)off * n, ids, sa);
             if (m->cfg.fixed_subsample)       // rng.seed(42) before every draw (reference source/base/utils.py:210-211)
                 return p2s_subsample_fixed(rs, c, weighted ? qp : nullptr, cnt, n, 42u, ids, nullptr, sa);
             return weighted ? p2s_subsample_weighted(rs, c, qp, cnt, n, ids, nullptr, sa)
@@ -348,20 +325,20 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, const P2sSegment *segs, 
         });
         if (rc2) return fail(rc2);
         p2s_prof_span(m, ST_SUB, e0, p2s_prof_mark(m, sa));
-        if (sa != s) PIPE_HIP(hipEventRecord(b.ready[bi], sa));
+        if (sa != s) PIPE_HIP(hipEventRecord(b.ready[bi].get(), sa));
         if (ball) {
             // patch choice (+ the rotation of the GT-query pass): a serial walk along the first generator's stream, under
             // the encoders of the chunks before; the encoders of chunk ci - nbuf read the patch buffer it fills
-            if (ci >= nbuf && sbl != s) PIPE_HIP(hipStreamWaitEvent(sbl, b.done[bi], 0));
+            if (ci >= nbuf && sbl != s) PIPE_HIP(hipStreamWaitEvent(sbl, b.done[bi].get(), 0));
             const int eb0 = p2s_prof_mark(m, sbl);
             rc2 = pieces(q0, cur, [&](p2s_rng_s *, p2s_rng_s *rf, int64_t off, int64_t row, int64_t cnt) -> int {
                 return p2s_ball_patch_counted(rf, c, q + (size_t)row * 3, ball_cd + row, ball_ch + row, cnt, ball_r, k,
-                                              rotate ? 6 : 0, nullptr, b.patch[bi] + (size_t)off * k * 3, b.radius[bi] + off,
-                                              rotate ? b.rot[bi] + (size_t)off * 9 : nullptr, sbl);
+                                              rotate ? 6 : 0, nullptr, b.patch[bi].get() + (size_t)off * k * 3, b.radius[bi].get() + off,
+                                              rotate ? b.rot[bi].get() + (size_t)off * 9 : nullptr, sbl);
             });
             if (rc2) return fail(rc2);
             p2s_prof_span(m, ST_KNN, eb0, p2s_prof_mark(m, sbl));
-            if (sbl != s) PIPE_HIP(hipEventRecord(b.ball_ready[bi], sbl));
+            if (sbl != s) PIPE_HIP(hipEventRecord(b.ball_ready[bi].get(), sbl));
         }
         return P2S_OK;
     };
@@ -375,21 +352,21 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, const P2sSegment *segs, 
         const int ek0 = p2s_prof_mark(m, s);
         int rc2 = P2S_OK;
         if (!ball) {
-            rc2 = small ? p2s_knn_patch(c, qc, cur, k, b.knn_ids[bi], nullptr, nullptr, s)
-                        : p2s_knn_patch_set(c, qc, cur, k, b.patch[bi], b.radius[bi], s);
+            rc2 = small ? p2s_knn_patch(c, qc, cur, k, b.knn_ids[bi].get(), nullptr, nullptr, s)
+                        : p2s_knn_patch_set(c, qc, cur, k, b.patch[bi].get(), b.radius[bi].get(), s);
             if (rc2) return fail(rc2);
             p2s_prof_span(m, ST_KNN, ek0, p2s_prof_mark(m, s));
         }
-        if (sa != s) PIPE_HIP(hipStreamWaitEvent(s, b.ready[bi], 0));
-        if (ball && sbl != s) PIPE_HIP(hipStreamWaitEvent(s, b.ball_ready[bi], 0));
+        if (sa != s) PIPE_HIP(hipStreamWaitEvent(s, b.ready[bi].get(), 0));
+        if (ball && sbl != s) PIPE_HIP(hipStreamWaitEvent(s, b.ball_ready[bi].get(), 0));
         if (small) {       // the patch is gathered from the array as the queries before this one left it
-            rc2 = p2s_patch_from_ids(c, b.knn_ids[bi], b.perm[bi], qc, cur, k, b.patch[bi], b.radius[bi], s);
+            rc2 = p2s_patch_from_ids(c, b.knn_ids[bi].get(), b.perm[bi].get(), qc, cur, k, b.patch[bi].get(), b.radius[bi].get(), s);
             if (rc2) return fail(rc2);
         }
-        rc2 = p2s_gather_points(c, b.sub_ids[bi], (int64_t)cur * n, b.sub[bi], s);
+        rc2 = p2s_gather_points(c, b.sub_ids[bi].get(), (int64_t)cur * n, b.sub[bi].get(), s);
         if (rc2) return fail(rc2);
         // the producer only writes sub_ids: free for chunk ci + nbuf as soon as the gather has read them
-        if (sa != s) PIPE_HIP(hipEventRecord(b.freed[bi], s));
+        if (sa != s) PIPE_HIP(hipEventRecord(b.freed[bi].get(), s));
         return P2S_OK;
     };
 
@@ -410,19 +387,19 @@ static int run_pipeline(p2s_model_s *m, p2s_cloud_s *c, const P2sSegment *segs, 
         if (rotate) {
             // data_loader.py:381-393: rotate sub-sample (model space), patch (patch space) and the query point
             if (!ball && (rc = pieces(q0, cur, [&](p2s_rng_s *, p2s_rng_s *rf, int64_t off, int64_t, int64_t cnt) -> int {
-                    return p2s_random_rotations(rf, cnt, b.rot[bi] + (size_t)off * 9, s);
+                    return p2s_random_rotations(rf, cnt, b.rot[bi].get() + (size_t)off * 9, s);
                 })))
                 return fail(rc);
-            if ((rc = p2s_rotate_points(b.rot[bi], b.sub[bi], n, cur, b.sub[bi], s))) return fail(rc);
-            if ((rc = p2s_rotate_points(b.rot[bi], b.patch[bi], k, cur, b.patch[bi], s))) return fail(rc);
-            if ((rc = p2s_rotate_points(b.rot[bi], qc, 1, cur, b.qrot[bi], s))) return fail(rc);
-            qc = b.qrot[bi];
+            if ((rc = p2s_rotate_points(b.rot[bi].get(), b.sub[bi].get(), n, cur, b.sub[bi].get(), s))) return fail(rc);
+            if ((rc = p2s_rotate_points(b.rot[bi].get(), b.patch[bi].get(), k, cur, b.patch[bi].get(), s))) return fail(rc);
+            if ((rc = p2s_rotate_points(b.rot[bi].get(), qc, 1, cur, b.qrot[bi].get(), s))) return fail(rc);
+            qc = b.qrot[bi].get();
         }
-        rc = p2s_run_chunk(m, p2s_precision(m->cfg), b.patch[bi], b.sub[bi], qc, b.radius[bi], cur,
+        rc = p2s_run_chunk(m, p2s_precision(m->cfg), b.patch[bi].get(), b.sub[bi].get(), qc, b.radius[bi].get(), cur,
                            logits_out ? logits_out + (size_t)q0 * m->cfg.output_dim : nullptr, sdf_out_dev + q0, nullptr, nullptr,
                            s, q0);
         if (rc) return fail(rc);
-        if (use_done) PIPE_HIP(hipEventRecord(b.done[bi], s));
+        if (use_done) PIPE_HIP(hipEventRecord(b.done[bi].get(), s));
         if (ci + nbuf < nchunks) {
             if ((rc = produce(ci + nbuf))) return rc;
         }
@@ -457,15 +434,15 @@ static int run_call(ModelCall &call, p2s_cloud_s *c, const p2s_worker_streams *w
     if (ws) {
         p2s_workers_segments(ws, nq, segs);
         if ((rc = p2s_workers_reserve(m, nq)) ||
-            (rc = p2s_launch_stream_order(ws->first_position, nq, ws->n_streams, ws->batch, q, m->wk.q, m->wk.src, s)))
+            (rc = p2s_launch_stream_order(ws->first_position, nq, ws->n_streams, ws->batch, q, m->wk.q.get(), m->wk.src.get(), s)))
             return call.fail(rc);
-        q = m->wk.q;
-        sdf = m->wk.sdf;
-        logits = logits ? m->wk.logits : nullptr;
+        q = m->wk.q.get();
+        sdf = m->wk.sdf.get();
+        logits = logits ? m->wk.logits.get() : nullptr;
     }
     if ((rc = run_pipeline(m, c, segs.data(), (int)segs.size(), rotate, q, nq, chunk, sdf, logits, s))) return call.fail(rc);
     if ((rc = call.finish(logits, sdf, nq))) return rc;
-    if (ws && ((rc = p2s_launch_unpermute(m->wk.src, nq, sdf, sdf_out, logits, call.logits, m->cfg.output_dim, s)) ||
+    if (ws && ((rc = p2s_launch_unpermute(m->wk.src.get(), nq, sdf, sdf_out, logits, call.logits, m->cfg.output_dim, s)) ||
                (rc = hip_status(hipStreamSynchronize(s), "hipStreamSynchronize"))))
         return call.fail(rc);
     for (const P2sSegment &g : segs) {

@@ -776,29 +776,20 @@ extern "C" int p2s_poisson_reconstruct(const float *points_dev, const float *nor
               *p = scr.get<float>(NF), *ap = scr.get<float>(NF);
         float *vol = vol_out_dev ? vol_out_dev : nullptr;
         if (!vol) vol = scr.get<float>(NF);
-        hipEvent_t ev[2] = {nullptr, nullptr};
         if (!x || !xc || !b || !diag || !r || !p || !ap || !vol) {
             p2s_set_error("%s: out of device memory", who);
             return P2S_ENOMEM;
         }
-        PS_CHECK(hipEventCreate(&ev[0]));
-        if (hipEventCreate(&ev[1]) != hipSuccess) {
-            (void)hipEventDestroy(ev[0]);
+        DevEvent ev[2];
+        if (!ev[0].create() || !ev[1].create()) {
             p2s_set_error("%s: hipEventCreate failed", who);
             return P2S_EHIP;
         }
-        struct EvGuard {
-            hipEvent_t *e;
-            ~EvGuard() {
-                (void)hipEventDestroy(e[0]);
-                (void)hipEventDestroy(e[1]);
-            }
-        } guard{ev};
         double *part_pa = w.part, *part_pb = w.part + PS_MAX_PART, *part_rr = w.part + 2 * PS_MAX_PART, *part_bb = w.part + 3 * PS_MAX_PART;
         double *part_rz[2] = {w.part + 4 * PS_MAX_PART, w.part + 5 * PS_MAX_PART};
         const double tol2 = params->cg_tol * params->cg_tol;
         for (int d = PS_MIN_DEPTH; d <= D; ++d) {
-            PS_CHECK(hipEventRecord(ev[0], s));
+            PS_CHECK(hipEventRecord(ev[0].get(), s));
             PsLevel L;
             if (int rc = ps_level_setup(who, points_dev, normals_dev, (int)n, su, params, d, w, s, &L)) return rc;
             const long long N = (long long)L.bx.R * L.bx.R * L.bx.R;
@@ -829,10 +820,10 @@ extern "C" int p2s_poisson_reconstruct(const float *points_dev, const float *nor
                 PS_CHECK(hipMemcpyAsync(&st, w.status, sizeof(st), hipMemcpyDeviceToHost, s));
                 PS_CHECK(hipStreamSynchronize(s));
             }
-            PS_CHECK(hipEventRecord(ev[1], s));
-            PS_CHECK(hipEventSynchronize(ev[1]));
+            PS_CHECK(hipEventRecord(ev[1].get(), s));
+            PS_CHECK(hipEventSynchronize(ev[1].get()));
             float ms = 0.0f;
-            PS_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            PS_CHECK(hipEventElapsedTime(&ms, ev[0].get(), ev[1].get()));
             double *lv = info + 8 + 5 * (d - PS_MIN_DEPTH);
             lv[0] = L.lambda;
             lv[1] = (double)L.n_occ;

@@ -99,26 +99,14 @@ int p2s_launch_unpermute(const int64_t *src, int64_t n, const float *sdf_in, flo
     return rc;
 }
 
-void p2s_workers_free(p2s_model_s *m) {
-    p2s_model_s::Workers &w = m->wk;
-    if (w.q) (void)hipFree(w.q);
-    if (w.src) (void)hipFree(w.src);
-    if (w.sdf) (void)hipFree(w.sdf);
-    if (w.logits) (void)hipFree(w.logits);
-    w = p2s_model_s::Workers();
-}
-
 int p2s_workers_reserve(p2s_model_s *m, int64_t n) {
     p2s_model_s::Workers &w = m->wk;
     if (w.cap >= n) return P2S_OK;
     P2S_HIP_CHECK(hipDeviceSynchronize());
-    p2s_workers_free(m);
-    const int64_t cap = n + n / 4 + 1024;
+    w = p2s_model_s::Workers();
+    const size_t cap = n + n / 4 + 1024;
     const int dim = std::max(m->cfg.output_dim, 1);
-    if (hipMalloc(&w.q, (size_t)cap * 12) != hipSuccess || hipMalloc(&w.src, (size_t)cap * 8) != hipSuccess ||
-        hipMalloc(&w.sdf, (size_t)cap * 4) != hipSuccess || hipMalloc(&w.logits, (size_t)cap * dim * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        p2s_workers_free(m);
+    if (!p2s_alloc_all(w.q, cap * 3, w.src, cap, w.sdf, cap, w.logits, cap * dim)) {
         p2s_set_error("workers mode: allocation of the stream-order buffers failed (%lld queries)", (long long)cap);
         return P2S_ENOMEM;
     }
@@ -199,37 +187,34 @@ extern "C" int p2s_subsample_workers(p2s_cloud_t c, const p2s_worker_streams *ws
     hipStream_t s = (hipStream_t)stream;
     std::vector<P2sSegment> segs;
     p2s_workers_segments(ws, n_queries, segs);
-    float *q_perm = nullptr;
-    int64_t *src = nullptr;
-    int32_t *ids_perm = nullptr;
+    DevBuf<float> q_perm;
+    DevBuf<int64_t> src;
+    DevBuf<int32_t> ids_perm;
+    // every exit drains the stream before the buffers above go out of scope: kernels queued on it read and write them
     auto release = [&](int code) {
         const hipError_t e = hipStreamSynchronize(s);
-        if (q_perm) (void)hipFree(q_perm);
-        if (src) (void)hipFree(src);
-        if (ids_perm) (void)hipFree(ids_perm);
         if (code == P2S_OK && e != hipSuccess) {
             p2s_set_error("p2s_subsample_workers: %s", hipGetErrorString(e));
             return (int)P2S_EHIP;
         }
         return code;
     };
-    if ((weighted && hipMalloc(&q_perm, (size_t)n_queries * 12) != hipSuccess) || hipMalloc(&src, (size_t)n_queries * 8) != hipSuccess ||
-        (ids_out_dev && hipMalloc(&ids_perm, (size_t)n_queries * n * 4) != hipSuccess)) {
-        (void)hipGetLastError();
+    if (!p2s_alloc_all(q_perm, weighted ? (size_t)n_queries * 3 : 0, src, n_queries, ids_perm,
+                       ids_out_dev ? (size_t)n_queries * n : 0)) {
         p2s_set_error("p2s_subsample_workers: allocation failed (%lld queries)", (long long)n_queries);
         return release(P2S_ENOMEM);
     }
-    if ((rc = p2s_launch_stream_order(ws->first_position, n_queries, ws->n_streams, ws->batch, weighted ? q_dev : nullptr, q_perm, src, s)))
+    if ((rc = p2s_launch_stream_order(ws->first_position, n_queries, ws->n_streams, ws->batch, weighted ? q_dev : nullptr, q_perm.get(), src.get(), s)))
         return release(rc);
     int64_t at = 0;
     for (const P2sSegment &g : segs) {
-        int32_t *ids = ids_perm ? ids_perm + (size_t)at * n : nullptr;
-        rc = weighted ? p2s_subsample_weighted(g.sub, c, q_perm + (size_t)at * 3, g.rows, n, ids, nullptr, s)
+        int32_t *ids = ids_perm ? ids_perm.get() + (size_t)at * n : nullptr;
+        rc = weighted ? p2s_subsample_weighted(g.sub, c, q_perm.get() + (size_t)at * 3, g.rows, n, ids, nullptr, s)
                       : p2s_subsample_uniform(g.sub, c, g.rows, n, ids, nullptr, s);
         if (rc) return release(rc);
         at += g.rows;
     }
-    if (ids_out_dev && (rc = scatter_rows(src, n_queries, n, ids_perm, ids_out_dev, s))) return release(rc);
+    if (ids_out_dev && (rc = scatter_rows(src.get(), n_queries, n, ids_perm.get(), ids_out_dev, s))) return release(rc);
     if (pts_out_dev && (rc = p2s_gather_points(c, ids_out_dev, n_queries * n, pts_out_dev, s))) return release(rc);
     for (const P2sSegment &g : segs)
         if ((rc = p2s_rng_check(g.sub, s))) return release(rc);

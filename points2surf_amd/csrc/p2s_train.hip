@@ -15,6 +15,7 @@
 //   element-wise kernels      batch-norm apply (+ReLU) and its backward, max-pool with argmax and its scatter, losses, SGD
 // No floating-point atomics: every reduction has a fixed order, equal inputs and equal state give equal bytes.
 #include "p2s_common.h"
+#include "p2s_devmem.h"
 #include <cmath>
 #include <cstring>
 #include <initializer_list>
@@ -487,7 +488,13 @@ struct p2s_trainer_s {
     int device = 0, P = 0, S = 0, stn = 0;
     NetP net{};
     long long np = 0, nb = 0;
+    // what the kernels read.  A trainer points them at its own blocks (`own`); the test hooks (DebugCtx) borrow the caller's
+    // arrays for params / grads / pend and own only their scratch
     float *params = nullptr, *grads = nullptr, *mom = nullptr, *bufs = nullptr, *pend = nullptr;
+    struct Owned {
+        DevBuf<float> params, grads, mom, bufs, pend, arena, wpart;
+        DevBuf<double> cpart;
+    } own;
     int64_t nbt = 0;
     bool have_grads = false, first_step = true;
     // per-batch-size arena
@@ -502,7 +509,7 @@ struct p2s_trainer_s {
     long long wpart_floats = 0;
     int profile = 0;
     double fam_ms[FAM_N] = {};
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> events;
+    std::vector<std::pair<int, std::pair<DevEvent, DevEvent>>> events;
     hipStream_t s = nullptr;
 };
 
@@ -511,16 +518,16 @@ namespace {
 typedef p2s_trainer_s T;
 
 struct Prof {
-    T *t; int fam; hipEvent_t a = nullptr, b = nullptr;
+    T *t; int fam; DevEvent a, b;
     Prof(T *t_, int fam_) : t(t_), fam(fam_) {
         if (!t->profile) return;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
-        (void)hipEventRecord(a, t->s);
+        if (!a.create() || !b.create()) { a.reset(); return; }
+        (void)hipEventRecord(a.get(), t->s);
     }
     ~Prof() {
         if (!a) return;
-        (void)hipEventRecord(b, t->s);
-        t->events.push_back({fam, {a, b}});
+        (void)hipEventRecord(b.get(), t->s);
+        t->events.emplace_back(fam, std::make_pair(std::move(a), std::move(b)));
     }
 };
 
@@ -818,14 +825,14 @@ int step_impl(T *t, const float *patch, const float *sub, const float *query, co
               const float *radius, int B, double *losses_host) {
     if (B != t->B || !t->arena) {
         const size_t bytes = plan(t, nullptr, B, patch);
-        if (t->arena) (void)hipFree(t->arena);
+        t->own.arena.reset();
         t->arena = nullptr;
         t->B = 0;
-        if (hipMalloc((void **)&t->arena, bytes) != hipSuccess) {
-            (void)hipGetLastError();
+        if (!t->own.arena.alloc(bytes / 4)) {
             p2s_set_error("trainer: cannot allocate %zu bytes of activations for B = %d", bytes, B);
             return P2S_ENOMEM;
         }
+        t->arena = t->own.arena.get();
         t->arena_floats = bytes / 4;
         t->B = B;
     }
@@ -932,11 +939,12 @@ int p2s_trainer_create(const p2s_model_cfg *cfg, int use_feat_stn, const float *
     t->device = device; t->P = cfg->points_per_patch; t->S = cfg->sub_sample_size; t->stn = use_feat_stn != 0;
     t->net = net; t->np = L.np; t->nb = L.nb; t->nbt = num_batches_tracked;
     const int rc = [&]() -> int {
-        P2S_HIP_CHECK(hipMalloc((void **)&t->params, L.np * 4));
-        P2S_HIP_CHECK(hipMalloc((void **)&t->grads, L.np * 4));
-        P2S_HIP_CHECK(hipMalloc((void **)&t->mom, L.np * 4));
-        P2S_HIP_CHECK(hipMalloc((void **)&t->bufs, L.nb * 4));
-        P2S_HIP_CHECK(hipMalloc((void **)&t->pend, L.nb * 4));
+        p2s_trainer_s::Owned &o = t->own;
+        if (!p2s_alloc_all(o.params, L.np, o.grads, L.np, o.mom, L.np, o.bufs, L.nb, o.pend, L.nb)) {
+            p2s_set_error("p2s_trainer_create: cannot allocate %lld parameters and %lld buffer values", L.np, L.nb);
+            return P2S_ENOMEM;
+        }
+        t->params = o.params.get(); t->grads = o.grads.get(); t->mom = o.mom.get(); t->bufs = o.bufs.get(); t->pend = o.pend.get();
         P2S_HIP_CHECK(hipMemcpy(t->params, params_host, L.np * 4, hipMemcpyHostToDevice));
         P2S_HIP_CHECK(hipMemcpy(t->bufs, buffers_host, L.nb * 4, hipMemcpyHostToDevice));
         P2S_HIP_CHECK(hipMemset(t->grads, 0, L.np * 4));
@@ -955,8 +963,6 @@ int p2s_trainer_create(const p2s_model_cfg *cfg, int use_feat_stn, const float *
 int p2s_trainer_destroy(p2s_trainer_t t) {
     if (!t) return P2S_OK;
     (void)hipSetDevice(t->device);
-    for (float *p : {t->params, t->grads, t->mom, t->bufs, t->pend, t->arena})
-        if (p) (void)hipFree(p);
     delete t;
     return P2S_OK;
 }
@@ -993,9 +999,7 @@ int p2s_trainer_forward_backward(p2s_trainer_t t, const float *patch_ps_dev, con
         (void)hipStreamSynchronize(t->s);
         for (auto &e : t->events) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) t->fam_ms[e.first] += ms;
-            (void)hipEventDestroy(e.second.first);
-            (void)hipEventDestroy(e.second.second);
+            if (hipEventElapsedTime(&ms, e.second.first.get(), e.second.second.get()) == hipSuccess) t->fam_ms[e.first] += ms;
         }
         t->events.clear();
         (void)hipGetLastError();
@@ -1099,11 +1103,6 @@ namespace {
 // shape needs (what plan() provides for the network's layers), freed when the hook returns.
 struct DebugCtx {
     p2s_trainer_s t;
-    ~DebugCtx() {
-        if (t.wpart) (void)hipFree(t.wpart);
-        if (t.cpart) (void)hipFree(t.cpart);
-        if (t.arena) (void)hipFree(t.arena);
-    }
     // every pointer must be device memory of one device, which becomes current
     int open(const char *who, std::initializer_list<const void *> ptrs, void *stream) {
         int dev = -1;
@@ -1126,12 +1125,12 @@ struct DebugCtx {
         const size_t cbytes = (size_t)colsum_slabs(M) * C * 3 * sizeof(double);
         const int slabs = dw_slabs(M);
         t.wpart_floats = slabs > 1 ? slabs * n : 0;
-        if (hipMalloc((void **)&t.cpart, cbytes) != hipSuccess ||
-            (t.wpart_floats > 0 && hipMalloc((void **)&t.wpart, (size_t)t.wpart_floats * 4) != hipSuccess)) {
-            (void)hipGetLastError();
+        if (!p2s_alloc_all(t.own.cpart, cbytes / sizeof(double), t.own.wpart, (size_t)t.wpart_floats)) {
             p2s_set_error("%s: cannot allocate %zu + %lld bytes of scratch", who, cbytes, t.wpart_floats * 4);
             return P2S_ENOMEM;
         }
+        t.cpart = t.own.cpart.get();
+        t.wpart = t.own.wpart.get();
         return P2S_OK;
     }
 };
@@ -1180,14 +1179,14 @@ int p2s_debug_train_bn(const float *y_dev, const float *params_dev, int64_t seco
     DebugCtx c;
     TRY(c.open(who, {y_dev, params_dev, z_dev, mean_dev, invstd_dev, pending_dev, d_dev, grads_dev}, stream));
     TRY(c.scratch(who, M, C, 0));
-    if (hipMalloc((void **)&c.t.arena, 2 * (size_t)C * 4) != hipSuccess) {      // the two means of the backward
-        (void)hipGetLastError();
+    if (!c.t.own.arena.alloc(2 * (size_t)C)) {      // the two means of the backward
         p2s_set_error("%s: cannot allocate %zu bytes of scratch", who, 2 * (size_t)C * 4);
         return P2S_ENOMEM;
     }
     c.t.params = const_cast<float *>(params_dev);
     c.t.grads = grads_dev;
     c.t.pend = pending_dev;
+    c.t.arena = c.t.own.arena.get();
     Blk b{};
     b.bn.C = C; b.bn.g = 0; b.bn.be = second_offset; b.bn.rm = 0; b.bn.rv = second_offset;
     b.relu = relu ? 1 : 0; b.M = M;

@@ -145,28 +145,14 @@ struct WcBatchMem {
 };
 WcBatchMem wc_batch_mem(p2s_rng_s *r) {
     WcBatchMem m;
-    m.S = r->wc_S;
-    m.R = (WcRec *)r->wc_T;
-    m.stot = r->wc_sc;
-    m.base = (long long *)(m.stot + r->wc_cap_q);
-    m.pmax = (float *)(m.base + r->wc_cap_q);
-    m.dsum = m.pmax + 2 * r->wc_cap_q;
-    m.mu = m.dsum + 2 * r->wc_cap_q;
+    m.S = r->wc.S.get();
+    m.R = (WcRec *)r->wc.T.get();
+    m.stot = r->wc.sc.get();
+    m.base = (long long *)(m.stot + r->wc.cap_q);
+    m.pmax = (float *)(m.base + r->wc.cap_q);
+    m.dsum = m.pmax + 2 * r->wc.cap_q;
+    m.mu = m.dsum + 2 * r->wc.cap_q;
     return m;
-}
-
-void wc_free(p2s_rng_s *r) {
-    if (r->wc_S) (void)hipFree(r->wc_S);
-    if (r->wc_T) (void)hipFree(r->wc_T);
-    if (r->wc_sc) (void)hipFree(r->wc_sc);
-    if (r->wc_spec) (void)hipFree(r->wc_spec);
-    if (r->wc_J) (void)hipFree(r->wc_J);
-    r->wc_S = nullptr;
-    r->wc_T = nullptr;
-    r->wc_sc = nullptr;
-    r->wc_spec = nullptr;
-    r->wc_J = nullptr;
-    r->wc_cap_q = r->wc_cap_n = r->wc_cap_k = 0;
 }
 
 constexpr size_t WC_SCRATCH = 160 * 1024;            // >= wc_lds_bytes(n) of every cloud the ids kernel takes
@@ -174,29 +160,23 @@ constexpr size_t WC_SPEC_BYTES = 64 + (size_t)SP_B * 16 + (size_t)SP_B * SP_W + 
                                  WC_SCRATCH;
 
 int wc_reserve(p2s_rng_s *r, size_t nq, size_t n, size_t K) {
-    if (nq <= r->wc_cap_q && n <= r->wc_cap_n && K <= r->wc_cap_k) return P2S_OK;
-    nq = std::max(nq, r->wc_cap_q);
-    n = std::max(n, r->wc_cap_n);
-    K = std::max(K, r->wc_cap_k);
-    wc_free(r);
-    const bool ok = hipMalloc(&r->wc_J, SP_JUMP_ROWS * SP_W * 2) == hipSuccess && hipMalloc(&r->wc_spec, WC_SPEC_BYTES) == hipSuccess &&
-                    hipMalloc(&r->wc_S, nq * n * 8) == hipSuccess && hipMalloc(&r->wc_T, nq * K * sizeof(WcRec)) == hipSuccess &&
-                    hipMalloc(&r->wc_sc, nq * 40) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        wc_free(r);
+    if (nq <= r->wc.cap_q && n <= r->wc.cap_n && K <= r->wc.cap_k) return P2S_OK;
+    nq = std::max(nq, r->wc.cap_q);
+    n = std::max(n, r->wc.cap_n);
+    K = std::max(K, r->wc.cap_k);
+    p2s_rng_s::WChoice &w = r->wc;
+    w = p2s_rng_s::WChoice();
+    if (!p2s_alloc_all(w.J, (size_t)SP_JUMP_ROWS * SP_W, w.spec, WC_SPEC_BYTES, w.S, nq * n, w.T, nq * K * sizeof(WcRec), w.sc, nq * 5)) {
         p2s_set_error("weighted sub-sample: hipMalloc of the per-query tables failed (%zu queries x %zu points)", nq, n);
         return P2S_ENOMEM;
     }
-    r->wc_cap_q = nq;
-    r->wc_cap_n = n;
-    r->wc_cap_k = K;
+    w.cap_q = nq;
+    w.cap_n = n;
+    w.cap_k = K;
     return P2S_OK;
 }
 
 }  // namespace
-
-void p2s_wc_free_rng(p2s_rng_s *r) { wc_free(r); }
 
 static int wc_subsample(p2s_rng_s *r, p2s_cloud_s *c, const float *q_dev, int64_t nq, int n_sel, int32_t *ids_out_dev,
                         float *pts_out_dev, void *stream, bool fixed, uint32_t fixed_seed);
@@ -274,14 +254,14 @@ static int wc_subsample(p2s_rng_s *r, p2s_cloud_s *c, const float *q_dev, int64_
     plan.root = c->wc_root;
     plan.n_nodes = c->wc_nodes;
     WcSpec sp;
-    sp.ctl = (long long *)r->wc_spec;
+    sp.ctl = (long long *)r->wc.spec.get();
     sp.klo = sp.ctl + 8;
     sp.klo1 = sp.klo + SP_B;
     sp.rtab = (unsigned char *)(sp.klo1 + SP_B);
     sp.dtil = (short *)(sp.rtab + (size_t)SP_B * SP_W);
     sp.save = (int *)(((uintptr_t)(sp.dtil + SP_B) + 63) & ~(uintptr_t)63);
     sp.scratch = (unsigned char *)(((uintptr_t)(sp.save + (size_t)SP_B * SP_SAVE) + 63) & ~(uintptr_t)63);
-    sp.jump = r->wc_J;
+    sp.jump = r->wc.J.get();
     const bool serial_only = getenv("P2S_WC_SERIAL") != nullptr;   // development / tests: every query through the in-order remainder path
     // stream skipping (no ids wanted): nothing else runs on the chip, the chain kernel may take the LDS the complete algorithm
     // likes; next to the encoders (ids wanted) it must stay small
@@ -292,9 +272,8 @@ static int wc_subsample(p2s_rng_s *r, p2s_cloud_s *c, const float *q_dev, int64_
         (void)hipFuncSetAttribute((const void *)wc_tables_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (NP_BUFSIZE + WC_MAX_NODES) * 4);
     }
     long long *meta = p2s_rng_raw_meta(r);
-    static long long *stats_dev = nullptr;
-    const bool want_stats = getenv("P2S_WC_STATS") != nullptr;
-    if (want_stats && !stats_dev) (void)hipMalloc(&stats_dev, 16 * 8);
+    const bool want_stats = getenv("P2S_WC_STATS") != nullptr && (r->wc.stats || r->wc.stats.alloc(16));
+    long long *const stats_dev = r->wc.stats.get();
     const WcBatchMem m = wc_batch_mem(r);
     for (int64_t done = 0; done < nq;) {
         const int cur = (int)std::min<int64_t>(per_req, nq - done);
@@ -316,7 +295,7 @@ static int wc_subsample(p2s_rng_s *r, p2s_cloud_s *c, const float *q_dev, int64_
         a.dsum = m.dsum;
         a.pts = c->d.pts;
         a.q = q_dev + (size_t)done * 3;
-        a.words = r->tmp;
+        a.words = r->tmp.get();
         a.cap_words = cap;
         a.n = n;
         a.K = K;
