@@ -569,6 +569,50 @@ int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const int32_t *face
 int p2s_mesh_normalize(const float *verts_dev, int64_t n_verts, float *verts_out_dev, double *info_host, int device, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Simplification of a triangle mesh by quadric vertex clustering (Lindstrom 2000, "Out-of-core simplification of large
+ * polygonal models"): one grid over the mesh, one vertex per occupied cell, placed by the accumulated plane quadrics of the
+ * faces that touch the cell.  The project's own definition -- it does NOT reproduce MeshLab's "Quadric
+ * Edge Collapse Decimation", which the reference's tooling uses; every result is a function of the input alone (integer
+ * atomics only, float64 sums in a fixed order, contraction off): equal inputs give equal bytes.
+ *  a. indices out of range or a non-finite vertex: P2S_EINVAL, before anything dereferences them.  n_faces = 0 (n_verts = 0
+ *     too) is legal and gives the empty result: no vertex, no face, vert_map all -1.
+ *  b. grid: exactly the grid of p2s_prepare_voxel_thin.  lo = the bounding box minimum of ALL input vertices, ext its largest
+ *     extent, cell index per axis i = min(R - 1, floor((p - lo) * (R / ext))) (ext = 0: every vertex in cell 0), cell size
+ *     h = ext / R, cell centre g = lo + (i + 1/2) h.  resolution 1..1024 = R.  resolution 0 (needs max_faces >= 0): with
+ *     n_faces <= max_faces the input is copied bit for bit (unreferenced vertices too; vert_map and face_src the identity;
+ *     report [3] = 0); otherwise lo = 1, hi = 1024; while lo < hi: mid = (lo + hi + 1) / 2; surviving(mid) <= max_faces ?
+ *     lo = mid : hi = mid - 1; R = lo.  surviving is the count of c, BEFORE duplicate removal, so the result never has more
+ *     than max_faces faces (R = 1 always qualifies).  The count is not monotone over grids that do not nest: the search
+ *     is the definition.
+ *  c. a face survives iff its three corners lie in three pairwise different cells.
+ *  d. one output vertex per cell that holds a corner of at least one surviving face, ordered by the smallest input vertex
+ *     id of the cell.  vert_map_out_dev [n_verts] (may be NULL): the output id of the vertex's cell, -1 where the cell has none.
+ *  e. placement 0 (mean) or 1 (quadric), in coordinates relative to g.  m = (sum of (p - g) over the cell's input vertices in
+ *     ascending vertex id) / count.  placement 0: x = m.  placement 1: every input face with at least one corner in the cell
+ *     contributes once, in ASCENDING FACE ID, except faces under the degenerate rule (|ab x ac|^2 <= 2^-90 |ab|^2 |ac|^2 on
+ *     the stored coordinates): with its corners a, b, c relative to g, n = (b - a) x (c - a), d = -(n . a), A += n n^T,
+ *     r += d n (squared-area weighting).  tr(A) = 0: x = m.  Otherwise x = m - (A + epsilon tr(A) I)^-1 (A m + r) by a
+ *     Cholesky factorisation (Tikhonov; no eigenvalue is truncated; condition number <= 1 + 1 / epsilon); epsilon finite in
+ *     [1e-6, 1].  Fallback: max |x| > h gives x = m.  The vertex is g + x, rounded once to float32.
+ *  f. the surviving faces in input order, mapped to the output ids, winding kept; of faces with the same vertex set (any
+ *     rotation or winding) the smallest input face id survives (rule c of p2s_mesh_repair).  face_src_out_dev [cap_faces]
+ *     (may be NULL): the input face id.
+ *  g. cap_verts >= min(n_verts, occupied cells) and cap_faces >= surviving faces suffice, so do n_verts and n_faces.
+ *     Smaller buffers: P2S_EINVAL with the report filled, nothing written.  n_verts, n_faces <= 2^27.  Arguments are checked
+ *     before the device is touched; the message names the offending one.
+ * report_host [16] int64:
+ *   [0] n_verts | n_faces << 32 (the input)   [1] vertices out   [2] faces out   [3] R   [4] occupied cells
+ *   [5] faces collapsed   [6] duplicate faces dropped   [7] degenerate input faces (no quadric)   [8] cells placed by the
+ *   quadric   [9] cells with tr(A) = 0   [10] cells that fell back to the mean ([8]..[10] are 0 for placement 0)
+ *   [11] probes of the search   [12] boundary edges | edges of more than two faces << 32 of the OUTPUT (clustering does not
+ *   preserve topology)   [13] the same of the input   [14], [15] 0.
+ * Scratch comes from the device's block cache and returns to it before the call ends.  Synchronises `stream`. */
+int p2s_mesh_simplify(const float *verts_dev, int64_t n_verts, const int32_t *faces_dev, int64_t n_faces, int resolution,
+                      int64_t max_faces, int placement, double epsilon, float *verts_out_dev, int64_t cap_verts,
+                      int32_t *faces_out_dev, int32_t *face_src_out_dev, int64_t cap_faces, int32_t *vert_map_out_dev,
+                      int64_t *report_host, int device, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * "next" row: the pairs of faces of a handle's mesh that intersect, and its non-manifold vertices -- what
  * the verdict "a volume" of p2s_mesh_repair (trimesh's is_volume) does not see, and what the pseudonormal sign of
  * p2s_mesh_distance assumes absent.  The project's own definition (trimesh offers none); every result is a function of

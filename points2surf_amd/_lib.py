@@ -99,6 +99,8 @@ PROTOTYPES = {
                                       c_void_p]),
     'p2s_mesh_repair': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                 ctypes.POINTER(c_int64), c_int, c_void_p]),
+    'p2s_mesh_simplify': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_int, ctypes.c_double, c_void_p, c_int64,
+                                  c_void_p, c_void_p, c_int64, c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p]),
     'p2s_mesh_check': (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     'p2s_mesh_voxelize': (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     'p2s_surface_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, ctypes.POINTER(ctypes.c_double), c_int,

@@ -37,6 +37,7 @@
 //  7. p2s_meshcheck.inl: the pairs of faces that intersect and the non-manifold vertices, by a fourth walk of the octree
 //  8. p2s_meshvoxel.inl: the occupancy of a closed mesh on the volume's grid, by a fifth walk (one column of voxels per
 //     lane), and the reductions of the reconstruction-quality report
+//  9. p2s_meshsimplify.inl: simplification by quadric vertex clustering, with the repair's face hash and the edge table
 //
 // The pseudonormal sign holds for ONE closed surface that does not intersect itself.  A closed mesh of several connected
 // components may be a union of overlapping solids (the reference's 00011084 is: 170 of its 2,000 GT queries lie just outside
@@ -1094,3 +1095,5 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
 #include "p2s_meshcheck.inl"
 // ---- 8. occupancy on the volume's grid and the reductions of the quality report
 #include "p2s_meshvoxel.inl"
+// ---- 9. simplification by quadric vertex clustering
+#include "p2s_meshsimplify.inl"
