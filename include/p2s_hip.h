@@ -613,6 +613,52 @@ int p2s_mesh_simplify(const float *verts_dev, int64_t n_verts, const int32_t *fa
                       int64_t *report_host, int device, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Connected components of a triangle mesh with their measures, and the sub-mesh of a face mask: what sees
+ * and removes the floating blobs and inner cavities of a reconstruction.  The project's own definition -- not trimesh's
+ * `split`, not MeshLab's "remove isolated pieces"; every result is a function of the input alone (integer atomics only,
+ * float64 sums in an order that the input fixes, contraction off): equal inputs give equal bytes.
+ *
+ * p2s_mesh_components
+ *  a. arguments are checked before the device is touched; the message names the offending one.  An index out of range or a
+ *     non-finite vertex: P2S_EINVAL, before anything dereferences it.  n_verts, n_faces <= 2^27.  n_faces = 0 is legal:
+ *     0 components, nothing but the report written.
+ *  b. two faces are connected iff they share a vertex INDEX; a component is a class of the transitive closure.  Equal
+ *     coordinates under different indices do not connect: unwelded input is out of contract (weld with p2s_mesh_repair
+ *     first).  Unreferenced vertices belong to no component.  A face with a repeated index is legal: it connects its distinct
+ *     indices and has area 0.
+ *  c. the components are ordered by their smallest face id; comp_out_dev [n_faces] is the rank 0 .. C - 1 of the face's component.
+ *  d. counts_out_dev [cap][5] int64: [0] smallest face id  [1] faces  [2] referenced vertices  [3] boundary edges: undirected
+ *     index pairs a != b used by exactly one face  [4] edges used by more than two faces.  (A face uses a pair once, however
+ *     often its repeated index makes it traverse the pair.)
+ *  e. measures_out_dev [cap][8] float64: [0] area  [1] signed volume  [2..4] minimum and [5..7] maximum of the bounding box of
+ *     the referenced vertices (exact).  Per face, from the float64 of the stored corners a, b, c: u = b - a, v = c - a,
+ *     n = (u.y v.z - u.z v.y, u.z v.x - u.x v.z, u.x v.y - u.y v.x), area term 0.5 sqrt((n.x n.x + n.y n.y) + n.z n.z),
+ *     volume term ((a.x (b.y c.z - b.z c.y) + a.y (b.z c.x - b.x c.z)) + a.z (b.x c.y - b.y c.x)) / 6: a numpy float64
+ *     evaluation gives the same bits.  The order of the additions: all faces sorted by (rank, face id) are cut into
+ *     blocks of 256 positions; a component's terms are added in ascending face id within each block; of the blocks
+ *     that the component touches, counted from its first, sum l of 64 adds the blocks l, l + 64, ... in ascending order; the
+ *     64 sums are added in a binary tree (l with l + 32, then with l + 16, ..., l + 1).
+ *  f. report_host [8] int64: [0] n_verts | n_faces << 32  [1] C  [2] faces of the largest component by face count  [3] rank of
+ *     the component of largest area (of equal ones the smallest rank)  [4] unreferenced vertices  [5] hook rounds (a
+ *     diagnostic, not contract)  [6], [7] 0.
+ *  g. cap_components < C: P2S_EINVAL with the report filled and nothing else written.  cap_components = n_faces suffices.
+ *
+ * p2s_mesh_submesh: the faces with keep_dev[f] != 0 in input order, winding kept, and the vertices they reference in input
+ * order, copied bit for bit.  vert_map_out_dev [n_verts] (may be NULL): the output id, or -1.  face_src_out_dev [cap_faces]
+ * (may be NULL): the input face id.  report_host [3]: [0] n_verts | n_faces << 32  [1] vertices out  [2] faces out.  Smaller
+ * buffers than that: P2S_EINVAL with the report filled, nothing written; n_verts and n_faces suffice.  An all-zero mask
+ * gives the empty mesh.  The mask is int32 so that p2s_prepare_gather over a [C] keep table, indexed by comp_out_dev,
+ * produces it on the device.  Validation and limits as in a.
+ *
+ * Both: scratch comes from the device's block cache and returns to it before the call ends.  Both synchronise `stream`. */
+int p2s_mesh_components(const float *verts_dev, int64_t n_verts, const int32_t *faces_dev, int64_t n_faces, int32_t *comp_out_dev,
+                        int64_t cap_components, int64_t *counts_out_dev, double *measures_out_dev, int64_t *report_host, int device,
+                        void *stream);
+int p2s_mesh_submesh(const float *verts_dev, int64_t n_verts, const int32_t *faces_dev, int64_t n_faces, const int32_t *keep_dev,
+                     float *verts_out_dev, int64_t cap_verts, int32_t *faces_out_dev, int32_t *face_src_out_dev, int64_t cap_faces,
+                     int32_t *vert_map_out_dev, int64_t *report_host, int device, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * "next" row: the pairs of faces of a handle's mesh that intersect, and its non-manifold vertices -- what
  * the verdict "a volume" of p2s_mesh_repair (trimesh's is_volume) does not see, and what the pseudonormal sign of
  * p2s_mesh_distance assumes absent.  The project's own definition (trimesh offers none); every result is a function of
@@ -981,6 +1027,17 @@ int p2s_cloudset_subsample_uniform(p2s_rng_t r, p2s_cloudset_t s, const int32_t 
  * [0, n_src) is P2S_EINVAL, nothing usable written.  The random thinning gathers a host-drawn permutation with it.
  *
  * p2s_prepare_restore: out [n][3] float64 = double(v) / scale + centre: a reconstruction back in the scan's own frame.
+ *
+ * p2s_prepare_clusters (a selecting call like the five above): points i != j are linked iff
+ * (dx dx + dy dy) + dz dz <= radius * radius, dx, dy, dz the float64 differences of the float32 coordinates (the predicate of
+ * p2s_ball_count); a cluster is a class of the transitive closure; label_out_dev [n] (may be NULL) receives the smallest point
+ * id of i's cluster.  A cluster is kept iff its size >= min(min_points, size of the largest cluster): the largest always
+ * survives, a non-empty cloud never comes back empty.  radius finite and > 0, min_points >= 1.  info_host [4] int64 (may be
+ * NULL): clusters, size of the largest, label of the largest (of equal ones the smallest label), clusters removed.  The
+ * points are binned into cells of edge radius (1 + 2^-20) over the bounding box and sorted by a 64-bit cell key; every point
+ * tests the points of its 27 neighbouring cells and hooks into a union-find (integer atomicMin).  More than 2^20 cells on an
+ * axis: P2S_EINVAL, "radius too small for this extent".  Memory is O(n).  A radius comparable to the cloud's extent degrades
+ * to O(n^2) pair tests.
  * ------------------------------------------------------------------------------------------ */
 int p2s_prepare_finite(const float *pts_dev, int64_t n, float *pts_out_dev, int32_t *ids_out_dev, int64_t *n_out_host, int device,
                        void *stream);
@@ -995,6 +1052,8 @@ int p2s_prepare_gather(const void *src_dev, int64_t n_src, int width, const int3
                        void *stream);
 int p2s_prepare_restore(const float *verts_dev, int64_t n, const double *centre_host, double scale, double *out_dev, int device,
                         void *stream);
+int p2s_prepare_clusters(const float *pts_dev, int64_t n, double radius, int64_t min_points, int32_t *label_out_dev, float *pts_out_dev,
+                         int32_t *ids_out_dev, int64_t *n_out_host, int64_t *info_host, int device, void *stream);
 
 #ifdef __cplusplus
 }

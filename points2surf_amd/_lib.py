@@ -156,6 +156,12 @@ PROTOTYPES = {
     'p2s_prepare_normalize': (c_int, [c_void_p, c_int64, c_void_p, ctypes.POINTER(ctypes.c_double), c_int, c_void_p]),
     'p2s_prepare_gather': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     'p2s_prepare_restore': (c_int, [c_void_p, c_int64, ctypes.POINTER(ctypes.c_double), ctypes.c_double, c_void_p, c_int, c_void_p]),
+    'p2s_prepare_clusters': (c_int, [c_void_p, c_int64, ctypes.c_double, c_int64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+                                     ctypes.POINTER(c_int64), c_int, c_void_p]),
+    'p2s_mesh_components': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+                                    c_int, c_void_p]),
+    'p2s_mesh_submesh': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                 ctypes.POINTER(c_int64), c_int, c_void_p]),
 }
 
 

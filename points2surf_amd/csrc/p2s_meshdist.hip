@@ -1097,3 +1097,5 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
 #include "p2s_meshvoxel.inl"
 // ---- 9. simplification by quadric vertex clustering
 #include "p2s_meshsimplify.inl"
+// ---- 10. connected components with their measures; the sub-mesh of a face mask
+#include "p2s_meshcomponents.inl"

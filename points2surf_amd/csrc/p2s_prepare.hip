@@ -772,3 +772,6 @@ extern "C" int p2s_prepare_restore(const float *verts_dev, int64_t n, const doub
     PP_CHECK(hipStreamSynchronize(s));
     return P2S_OK;
 }
+
+// ---- the clusters of a cloud and the removal of the small ones
+#include "p2s_prepare_clusters.inl"

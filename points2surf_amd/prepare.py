@@ -1,6 +1,7 @@
 """Raw scans -> a data set the engine reads (what make_pc_dataset.py does in the reference, made robust and
 repeatable): drop non-finite points, crop gross strays, remove statistical outliers, thin to a budget, normalise to the unit
-cube -- and ``restore`` a reconstruction into the scan's own frame.  Everything runs on the device through libp2s_hip.so
+cube -- and ``restore`` a reconstruction into the scan's own frame.  An opt-in stage between the outliers and the thinning removes
+small floating clusters (``min_cluster``; p2s_prepare_clusters).  Everything runs on the device through libp2s_hip.so
 (p2s_prepare_*); torch tensors are containers only; no CPU fallback.
 
     python -m points2surf_amd.prepare --indir RAW --outdir DATASET [--stage prepare|restore|all] [options]
@@ -20,10 +21,13 @@ from . import file_utils
 
 P2S_EFLAT = -7
 THIN = ('random', 'voxel')
-DEFAULTS = dict(crop_quantile=0.01, crop_margin=1.0, k=16, std_ratio=2.0, max_points=150000, thin='random', seed=42)
+DEFAULTS = dict(crop_quantile=0.01, crop_margin=1.0, k=16, std_ratio=2.0, max_points=150000, thin='random', seed=42,
+                min_cluster=0, cluster_radius=0.0, cluster_factor=3.0)
 EXTENSIONS = ('.ply', '.off', '.obj', '.stl', '.xyz', '.txt', '.npy')
 REPORT_COLUMNS = ('file', 'points_in', 'nonfinite', 'cropped', 'outliers', 'thinned', 'points_out', 'R', 'mean', 'std', 'threshold',
                   'centre_x', 'centre_y', 'centre_z', 'scale', 'refused')
+CLUSTER_REPORT_FILE = 'clusters_report.csv'
+CLUSTER_REPORT_COLUMNS = ('file', 'clusters', 'removed_clusters', 'removed_points', 'radius')
 
 
 class Refused(ValueError):
@@ -116,6 +120,27 @@ def voxel_thin(points, max_points=None, resolution=None, want_report=False, devi
     return (out, ids, dict(R=int(info[0]), occupied=int(info[1]))) if want_report else (out, ids)
 
 
+def remove_small_clusters(points, radius, min_points, want_report=False, device=None):
+    """(points, ids[, report]): points i != j are linked iff (dx dx + dy dy) + dz dz <= radius * radius in float64; a cluster is
+    a class of the transitive closure, kept iff its size >= min(min_points, size of the largest cluster) -- the largest always
+    survives.  report: clusters, largest (its size), largest_label (the smallest point id of it), removed_clusters, labels
+    (int32 device tensor [n]: the smallest point id of every point's cluster)"""
+    radius, min_points = float(radius), int(min_points)
+    if not (radius > 0.0 and np.isfinite(radius)):
+        raise ValueError('radius must be a positive finite number (got %r)' % (radius,))
+    if min_points < 1:
+        raise ValueError('min_points must be >= 1 (got %r)' % (min_points,))
+    pts = _points(points, device)
+    labels = torch.empty((pts.shape[0],), dtype=torch.int32, device=pts.device) if want_report else None
+    info = (ctypes.c_int64 * 4)()
+    out, ids = _select('p2s_prepare_clusters', pts, radius, min_points, _engine._ptr(labels) if want_report and pts.shape[0] else None,
+                       tail=(info,))
+    if not want_report:
+        return out, ids
+    return out, ids, dict(clusters=int(info[0]), largest=int(info[1]), largest_label=int(info[2]), removed_clusters=int(info[3]),
+                          labels=labels)
+
+
 def gather(src, ids):
     """rows ``ids`` (int32 device tensor) of the float32 / int32 device tensor ``src`` ([n] or [n, w])"""
     lib = _lib.load()
@@ -174,14 +199,23 @@ def restore(vertices, frame, device=None):
 def prepare(points, device=None, **options):
     """(points float32 [m, 3], kept ids int32 [m] into the input, frame, report) -- device tensors, frame as ``normalize``
     gives it with ``kept`` added.  Options and defaults: ``DEFAULTS``.  The stages in order: non-finite points, crop
-    (crop_quantile 0: off), outliers (std_ratio 0: off), thinning (max_points 0: off; only when more points are left),
-    unit cube.  report: points_in, nonfinite, cropped, outliers, thinned, points_out, R, mean, std, threshold."""
+    (crop_quantile 0: off), outliers (std_ratio 0: off), small clusters (min_cluster 0: off; the radius is cluster_radius, or
+    with 0 cluster_factor times the outlier stage's mean -- before the thinning, which changes the density that this scales
+    by), thinning (max_points 0: off; only when more points are left), unit cube.  report: points_in, nonfinite, cropped,
+    outliers, thinned, points_out, R, mean, std, threshold; with the cluster stage on also clusters, small_clusters (the
+    clusters removed), cluster_points (the points removed with them) and cluster_radius."""
     unknown = set(options) - set(DEFAULTS)
     if unknown:
         raise TypeError('unknown options %s' % sorted(unknown))
     o = dict(DEFAULTS, **options)
     if o['thin'] not in THIN:
         raise ValueError('thin must be one of %s (got %r)' % (THIN, o['thin']))
+    if int(o['min_cluster']) < 0 or not float(o['cluster_radius']) >= 0.0 or not float(o['cluster_factor']) > 0.0:
+        raise ValueError('min_cluster >= 0, cluster_radius >= 0 and cluster_factor > 0 are needed (got %r, %r, %r)'
+                         % (o['min_cluster'], o['cluster_radius'], o['cluster_factor']))
+    if int(o['min_cluster']) > 0 and float(o['cluster_radius']) == 0.0 and float(o['std_ratio']) == 0.0:
+        raise ValueError('with the outlier stage off (std_ratio 0) the cluster stage has no density to scale by: '
+                         'give --cluster_radius')
     pts = _points(points, device)
     rep = dict(points_in=int(pts.shape[0]))
     pts, kept = drop_nonfinite(pts)
@@ -197,6 +231,12 @@ def prepare(points, device=None, **options):
     stage('cropped', crop(pts, o['crop_quantile'], o['crop_margin']))
     info = stage('outliers', remove_outliers(pts, o['k'], o['std_ratio'], want_report=True))
     rep.update(mean=info['mean'], std=info['std'], threshold=info['threshold'])
+    if int(o['min_cluster']) > 0 and pts.shape[0] > 0:
+        radius = float(o['cluster_radius']) or float(o['cluster_factor']) * float(info['mean'])
+        if not radius > 0.0:
+            raise Refused('cluster radius 0 (the mean neighbour distance is 0)')
+        cl = stage('cluster_points', remove_small_clusters(pts, radius, int(o['min_cluster']), want_report=True))
+        rep.update(clusters=cl['clusters'], small_clusters=cl['removed_clusters'], cluster_radius=radius)
     rep['R'] = 0
     if o['max_points'] and pts.shape[0] > int(o['max_points']):
         if o['thin'] == 'random':
@@ -266,7 +306,10 @@ def prepare_dir(indir, outdir, device=None, **options):
     if os.path.isfile(report_path):
         with open(report_path, newline='') as f:
             old = {r['file']: r for r in csv.DictReader(f)}
-    rows, written = [], []
+    rows, written, cluster_rows, old_clusters = [], [], [], {}
+    if os.path.isfile(os.path.join(outdir, CLUSTER_REPORT_FILE)):
+        with open(os.path.join(outdir, CLUSTER_REPORT_FILE), newline='') as f:
+            old_clusters = {r['file']: r for r in csv.DictReader(f)}
     for name in sorted(f for f in os.listdir(indir) if os.path.splitext(f)[1].lower() in EXTENSIONS):
         src, stem = os.path.join(indir, name), _stem(name)
         out_pts, out_frame = os.path.join(pts_dir, stem + '.xyz.npy'), os.path.join(frame_dir, stem + '.npz')
@@ -274,6 +317,8 @@ def prepare_dir(indir, outdir, device=None, **options):
             print('up to date: %s' % name)
             rows.append(old[name])
             written.append(stem)
+            if name in old_clusters:
+                cluster_rows.append(old_clusters[name])
             continue
         try:
             raw = read_cloud(src)
@@ -291,12 +336,20 @@ def prepare_dir(indir, outdir, device=None, **options):
         np.savez(out_frame, centre=frame['centre'], scale=np.float64(frame['scale']), kept=kept.cpu().numpy().astype(np.int32))
         rows.append(_row(name, rep, frame))
         written.append(stem)
+        if 'clusters' in rep:
+            cluster_rows.append(dict(file=name, clusters=rep['clusters'], removed_clusters=rep['small_clusters'],
+                                     removed_points=rep['cluster_points'], radius=repr(rep['cluster_radius'])))
     with open(os.path.join(outdir, 'testset.txt'), 'w') as f:
         f.write(''.join(s + '\n' for s in sorted(written)))
     with open(report_path, 'w', newline='') as f:
         w = csv.DictWriter(f, fieldnames=REPORT_COLUMNS)
         w.writeheader()
         w.writerows(rows)
+    if int(o['min_cluster']) > 0:                    # the cluster stage reports in a file of its own: prepare_report.csv stays as it was
+        with open(os.path.join(outdir, CLUSTER_REPORT_FILE), 'w', newline='') as f:
+            w = csv.DictWriter(f, fieldnames=CLUSTER_REPORT_COLUMNS)
+            w.writeheader()
+            w.writerows(cluster_rows)
     return rows
 
 
@@ -337,6 +390,11 @@ def main(argv=None):
     ap.add_argument('--max_points', type=int, default=DEFAULTS['max_points'], help='0: no thinning')
     ap.add_argument('--thin', choices=THIN, default=DEFAULTS['thin'])
     ap.add_argument('--seed', type=int, default=DEFAULTS['seed'])
+    ap.add_argument('--min_cluster', type=int, default=DEFAULTS['min_cluster'],
+                    help='remove the clusters of fewer points (the largest always stays); 0: off')
+    ap.add_argument('--cluster_radius', type=float, default=DEFAULTS['cluster_radius'],
+                    help='two points within this distance are linked; 0: --cluster_factor times the mean neighbour distance')
+    ap.add_argument('--cluster_factor', type=float, default=DEFAULTS['cluster_factor'], help='a choice, not a measurement')
     ap.add_argument('--meshes', help='restore: directory of <stem>.ply reconstructions in the unit cube')
     ap.add_argument('--restored', help='restore: where the meshes in the scans\' own coordinates go')
     ap.add_argument('--gpu_idx', type=int, default=0)
