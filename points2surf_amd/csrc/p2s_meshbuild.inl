@@ -347,11 +347,7 @@ extern "C" int p2s_trimesh_create(const float *verts_dev, int64_t n_verts, const
         p2s_set_error("p2s_trimesh_create: bad argument (1 <= vertices, faces <= 2^27)");
         return P2S_EINVAL;
     }
-    if (p2s_device_count() <= device || device < 0 || device >= P2S_MAX_DEVICES) {
-        p2s_set_error("p2s_trimesh_create: no such device %d", device);
-        return P2S_ENODEVICE;
-    }
-    P2S_HIP_CHECK(hipSetDevice(device));
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const long long V = n_verts, F = n_faces;
 
@@ -373,7 +369,7 @@ extern "C" int p2s_trimesh_create(const float *verts_dev, int64_t n_verts, const
     m->L = L;
     const size_t persistent = carve_handle(m.get(), nullptr, cells, n_nodes);
     m->arena = (char *)p2s_pool_alloc(device, persistent);
-    MeshScratch pool(device);
+    PoolScratch pool(device, s);
     const BuildWs w = pool.carve([&](char *b) { return carve_build(b, F, cells, cap); });
     if (!m->arena || !w.base) {
         p2s_set_error("p2s_trimesh_create: out of device memory (%zu + %zu bytes)", persistent, w.bytes);
@@ -397,7 +393,7 @@ extern "C" int p2s_trimesh_create(const float *verts_dev, int64_t n_verts, const
 
     // closed? inverted?
     unsigned long long hc[8] = {};
-    MESH_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
+    DEV_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
     if ((rc = build_edges(who, faces_dev, F, w.t, nullptr, nullptr, s)) != P2S_OK) return rc;
     hipLaunchKernelGGL(p2s_md_edge_check_kernel, dim3(blocks(cap, 256)), dim3(256), 0, s, w.t, w.ctr + BC_BAD_EDGES);
     hipLaunchKernelGGL(p2s_md_volume_kernel, dim3(1), dim3(1024), 0, s, verts_dev, faces_dev, F, (double *)(w.ctr + BC_VOLUME));
@@ -412,13 +408,13 @@ extern "C" int p2s_trimesh_create(const float *verts_dev, int64_t n_verts, const
     // the stored triangles and the index
     const SetupArgs a = {verts_dev, faces_dev, F, m->inverted, w.t, m->tri, m->fidx, m->fn, m->adj, (unsigned long long *)m->vn,
                          m->fbad, m->vbad, w.fcell, w.count, {m->lo[0], m->lo[1], m->lo[2]}, m->inv_cell, G};
-    MESH_CHECK(who, hipMemsetAsync(m->vn, 0, (size_t)V * 32, s));
-    MESH_CHECK(who, hipMemsetAsync(m->vbad, 0, (size_t)V * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(w.count, 0, (size_t)cells * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(w.cursor, 0, (size_t)cells * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(m->vn, 0, (size_t)V * 32, s));
+    DEV_CHECK(who, hipMemsetAsync(m->vbad, 0, (size_t)V * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(w.count, 0, (size_t)cells * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(w.cursor, 0, (size_t)cells * 4, s));
     hipLaunchKernelGGL(p2s_md_nodes_init_kernel, dim3(blocks(n_nodes, 256)), dim3(256), 0, s, m->nodes, n_nodes);
     hipLaunchKernelGGL(p2s_md_setup_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, w.count, cells, m->cell_start);
+    hipLaunchKernelGGL(p2s_scan_kernel, dim3(1), dim3(1024), 0, s, w.count, cells, m->cell_start);
     hipLaunchKernelGGL(p2s_md_fill_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, m->tri, w.fcell, F, m->cell_start, w.cursor, m->sface,
                        m->nodes + 6 * leaf_off);
     hipLaunchKernelGGL(p2s_md_cell_sort_kernel, dim3(blocks(cells, 256)), dim3(256), 0, s, m->cell_start, cells, m->sface);
@@ -432,10 +428,10 @@ extern "C" int p2s_trimesh_create(const float *verts_dev, int64_t n_verts, const
     }
     if (m->closed) {                                               // connected components
         int *parent = m->comp;
-        hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, parent, F, 1);
-        rc = until_unchanged(who, "the connected components", w.ctl, s, [&] {
+        hipLaunchKernelGGL(p2s_iota_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, parent, F);
+        rc = until_unchanged(who, "the connected components", 100000, w.ctl, s, [&](long long) {
             hipLaunchKernelGGL(p2s_md_cc_hook_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, m->adj, parent, F, w.ctl);
-            hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, parent, F, 0);
+            hipLaunchKernelGGL(p2s_uf_compress_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, parent, F);
         });
         if (rc != P2S_OK) return rc;
         hipLaunchKernelGGL(p2s_md_cc_count_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, parent, F, w.ctr + BC_COMPONENTS);
@@ -448,18 +444,18 @@ extern "C" int p2s_trimesh_create(const float *verts_dev, int64_t n_verts, const
         const int nc = m->components;
         int hr[16] = {};
         double hv[16] = {};
-        MESH_CHECK(who, hipMemsetAsync(w.ctl, 0, 4, s));
+        DEV_CHECK(who, hipMemsetAsync(w.ctl, 0, 4, s));
         hipLaunchKernelGGL(p2s_md_cc_roots_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, m->comp, F, w.ctl, w.roots);
-        MESH_CHECK(who, hipGetLastError());
-        MESH_CHECK(who, hipMemcpyAsync(hr, w.roots, 64, hipMemcpyDeviceToHost, s));
-        MESH_CHECK(who, hipStreamSynchronize(s));
+        DEV_CHECK(who, hipGetLastError());
+        DEV_CHECK(who, hipMemcpyAsync(hr, w.roots, 64, hipMemcpyDeviceToHost, s));
+        DEV_CHECK(who, hipStreamSynchronize(s));
         std::sort(hr, hr + nc);
-        MESH_CHECK(who, hipMemcpyAsync(w.roots, hr, 64, hipMemcpyHostToDevice, s));
+        DEV_CHECK(who, hipMemcpyAsync(w.roots, hr, 64, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(p2s_md_comp_volume_kernel, dim3((unsigned)nc), dim3(1024), 0, s, m->tri, m->comp, F, w.roots, w.vol);
         hipLaunchKernelGGL(p2s_md_scomp_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, m->comp, m->sface, F, m->scomp);
-        MESH_CHECK(who, hipGetLastError());
-        MESH_CHECK(who, hipMemcpyAsync(hv, w.vol, 128, hipMemcpyDeviceToHost, s));
-        MESH_CHECK(who, hipStreamSynchronize(s));
+        DEV_CHECK(who, hipGetLastError());
+        DEV_CHECK(who, hipMemcpyAsync(hv, w.vol, 128, hipMemcpyDeviceToHost, s));
+        DEV_CHECK(who, hipStreamSynchronize(s));
         for (int k = 0; k < nc; ++k) {
             m->comp_root[k] = hr[k];
             m->comp_orient[k] = hv[k] < 0.0 ? -1 : 1;

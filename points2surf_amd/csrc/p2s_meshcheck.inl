@@ -7,7 +7,7 @@
 //   p2s_mc_vertex_faces_kernel / p2s_mc_fan_kernel   faces per vertex and its smallest face; the fan walk
 //   p2s_mc_flags_kernel        the flag words as bytes, and their counts
 //   p2s_mc_unpack_kernel       the sorted (g, class) words of every face as pairs and class bytes
-// Both pair kernels run twice: a count pass (counters, flags, stored pairs per face), then, behind p2s_md_scan_kernel, a
+// Both pair kernels run twice: a count pass (counters, flags, stored pairs per face), then, behind p2s_scan_kernel, a
 // fill pass that writes (g << 2 | class) into the face's own range; p2s_md_cell_sort_kernel sorts every range, so the
 // pairs are ascending in (f, g) whatever order lanes or atomics arrived in.
 //
@@ -478,14 +478,14 @@ extern "C" int p2s_mesh_check(p2s_trimesh_t m, int method, int64_t cap_pairs, in
     const long long F = m->F, V = m->V;
     unsigned cap = 1024;
     while ((long long)cap < 6 * F) cap <<= 1;
-    MeshScratch pool(m->device);
+    PoolScratch pool(m->device, s);
     const CheckWs w = pool.carve([&](char *b) { return carve_check(b, (size_t)F, (size_t)V, cap); });
-    if (!w.base) return mesh_oom(who, s);
-    MESH_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
-    MESH_CHECK(who, hipMemsetAsync(w.ctr2, 0, MESH_COUNTERS, s));
-    MESH_CHECK(who, hipMemsetAsync(w.count, 0, (size_t)F * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(w.vdeg, 0, (size_t)V * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(w.vmin, 0x7f, (size_t)V * 4, s));
+    if (!w.base) return dev_oom(who, s);
+    DEV_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
+    DEV_CHECK(who, hipMemsetAsync(w.ctr2, 0, MESH_COUNTERS, s));
+    DEV_CHECK(who, hipMemsetAsync(w.count, 0, (size_t)F * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(w.vdeg, 0, (size_t)V * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(w.vmin, 0x7f, (size_t)V * 4, s));
     hipLaunchKernelGGL(p2s_mc_prep_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, m->tri, F, w.fbox, w.deg, w.fflag);
 
     const double S = m->scale;
@@ -526,10 +526,10 @@ extern "C" int p2s_mesh_check(p2s_trimesh_t m, int method, int64_t cap_pairs, in
         return P2S_EINVAL;
     }
     if (pairs_out_dev && stored > 0) {
-        a.packed = (int *)pool.get((size_t)stored * 4);
-        if (!a.packed) return mesh_oom(who, s);
-        MESH_CHECK(who, hipMemsetAsync(w.cursor, 0, (size_t)F * 4, s));
-        hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, w.count, F, w.start);
+        a.packed = pool.get<int>((size_t)stored);
+        if (!a.packed) return dev_oom(who, s);
+        DEV_CHECK(who, hipMemsetAsync(w.cursor, 0, (size_t)F * 4, s));
+        hipLaunchKernelGGL(p2s_scan_kernel, dim3(1), dim3(1024), 0, s, w.count, F, w.start);
         pairs_pass();
         hipLaunchKernelGGL(p2s_md_cell_sort_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, w.start, F, a.packed);
         hipLaunchKernelGGL(p2s_mc_unpack_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, w.start, a.packed, F, pairs_out_dev, class_out_dev);
@@ -537,7 +537,7 @@ extern "C" int p2s_mesh_check(p2s_trimesh_t m, int method, int64_t cap_pairs, in
     if (face_flags_out_dev || vert_flags_out_dev)
         hipLaunchKernelGGL(p2s_mc_flags_kernel, dim3(blocks(std::max(F, V), 256)), dim3(256), 0, s, w.fflag, F, w.vflag, V, face_flags_out_dev,
                            vert_flags_out_dev, (unsigned long long *)nullptr);
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipStreamSynchronize(s));
     return P2S_OK;
 }

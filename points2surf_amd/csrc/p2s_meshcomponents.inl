@@ -1,7 +1,7 @@
 // the connected components of a triangle mesh with their measures, and the sub-mesh of a face mask.
 // Definitions: include/p2s_hip.h (p2s_mesh_components, p2s_mesh_submesh).  Included at the end of p2s_meshdist.hip, behind
 // p2s_meshsimplify.inl: the edge table's layout and hash (EdgeTable, edge_key, edge_hash), the union-find
-// primitives (cc_find, p2s_md_cc_compress_kernel), p2s_rp_used_kernel, p2s_rp_write_verts_kernel, p2s_sm_seg_kernel and
+// primitives (uf_find, p2s_uf_compress_kernel), p2s_rp_used_kernel, p2s_rp_write_verts_kernel, p2s_sm_seg_kernel and
 // the host scaffold are those files', used here and not copied.
 //   p2s_mc_hook_kernel        union-find over the VERTICES: a face hooks (v0, v1) and (v1, v2), the larger root to the
 //                             smaller by atomicMin; a pair whose ends already share a root is skipped
@@ -24,7 +24,7 @@
 // Determinism: roots, first faces and boxes are integer minima and maxima, counts are integer sums, ranks come from an
 // exclusive scan (hipcub), and a component's float64 sums run over keys that a radix sort put in ascending face id: first
 // within each block of 256 sorted keys, then over the blocks as p2s_mc_collect_kernel fixes it.  No floating-point atomic.
-// Termination: cc_find walks strictly decreasing parents.  A round of hooks that changes something turns at least one root
+// Termination: uf_find walks strictly decreasing parents.  A round of hooks that changes something turns at least one root
 // into a non-root (the thread that raised `changed` saw two different roots and lowered the parent of the larger), and a
 // vertex never becomes a root again: after at most V - 1 such rounds and one that changes nothing the host loop ends; more
 // than V + 1 rounds is an internal error.  No thread waits for another.
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void p2s_mc_hook_kernel(const int *__restrict_
     if (f >= F) return;
     const int v[3] = {faces[3 * f], faces[3 * f + 1], faces[3 * f + 2]};
     for (int e = 0; e < 2; ++e) {
-        const int ra = cc_find(parent, v[e]), rb = cc_find(parent, v[e + 1]);
+        const int ra = uf_find(parent, v[e]), rb = uf_find(parent, v[e + 1]);
         if (ra != rb) {
             atomicMin(&parent[max(ra, rb)], min(ra, rb));
             *changed = 1;
@@ -303,11 +303,11 @@ __global__ __launch_bounds__(256) void p2s_mc_validate_kernel(const float *__res
 }
 int mc_validate(const char *who, const float *verts, long long V, const int *faces, long long F, int *ctl, hipStream_t s) {
     int h = 0;
-    MESH_CHECK(who, hipMemsetAsync(ctl, 0, 4, s));
+    DEV_CHECK(who, hipMemsetAsync(ctl, 0, 4, s));
     hipLaunchKernelGGL(p2s_mc_validate_kernel, dim3(blocks(3 * std::max(V, F), 256)), dim3(256), 0, s, verts, V, faces, F, ctl);
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipMemcpyAsync(&h, ctl, 4, hipMemcpyDeviceToHost, s));
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(&h, ctl, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (h) {
         p2s_set_error("%s: %s", who, (h & 2) ? "face index out of range" : "non-finite vertex");
         return P2S_EINVAL;
@@ -410,11 +410,7 @@ extern "C" int p2s_mesh_components(const float *verts_dev, int64_t n_verts, cons
         p2s_set_error("%s: bad argument (%s)", who, bad);
         return P2S_EINVAL;
     }
-    if (p2s_device_count() <= device || device < 0 || device >= P2S_MAX_DEVICES) {
-        p2s_set_error("%s: no such device %d", who, device);
-        return P2S_ENODEVICE;
-    }
-    P2S_HIP_CHECK(hipSetDevice(device));
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const long long V = n_verts, F = n_faces;
     long long rep_out[8] = {};
@@ -423,7 +419,7 @@ extern "C" int p2s_mesh_components(const float *verts_dev, int64_t n_verts, cons
     auto publish = [&]() {
         for (int k = 0; k < 8; ++k) report_host[k] = rep_out[k];
     };
-    MeshScratch pool(device);
+    PoolScratch pool(device, s);
     int rc;
 
     // ---- a. validate
@@ -434,7 +430,7 @@ extern "C" int p2s_mesh_components(const float *verts_dev, int64_t n_verts, cons
     (void)hipcub::DeviceRadixSort::SortKeys(nullptr, t3, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)V, 0, 64, nullptr);
     const size_t tmp_bytes = std::max(t1, std::max(t2, t3)) + 256;
     const McWs W = pool.carve([&](char *b) { return carve_mc(b, (size_t)V, (size_t)F, ecap, tmp_bytes); });
-    if (!W.base) return mesh_oom(who, s);
+    if (!W.base) return dev_oom(who, s);
     if (V > 0 || F > 0) {
         if ((rc = mc_validate(who, verts_dev, V, faces_dev, F, W.ctl, s)) != P2S_OK) return rc;
     }
@@ -444,70 +440,60 @@ extern "C" int p2s_mesh_components(const float *verts_dev, int64_t n_verts, cons
     }
 
     // ---- b. the union-find over the vertices
-    hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, W.parent, V, 1);
-    long long rounds = 0;
-    for (int changed = 1; changed; ++rounds) {
-        if (rounds > V + 1) {                                        // see the head of this file
-            (void)hipStreamSynchronize(s);
-            p2s_set_error("%s: internal error (the connected components did not converge in %lld rounds)", who, rounds);
-            return P2S_EHIP;
-        }
-        MESH_CHECK(who, hipMemsetAsync(W.ctl, 0, 4, s));
+    hipLaunchKernelGGL(p2s_iota_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, W.parent, V);
+    rc = until_unchanged(who, "the connected components", V + 1, W.ctl, s, [&](long long) {      // the cap: see the head of this file
         hipLaunchKernelGGL(p2s_mc_hook_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, faces_dev, F, W.parent, W.ctl);
-        hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, W.parent, V, 0);
-        MESH_CHECK(who, hipGetLastError());
-        MESH_CHECK(who, hipMemcpyAsync(&changed, W.ctl, 4, hipMemcpyDeviceToHost, s));
-        MESH_CHECK(who, hipStreamSynchronize(s));
-    }
-    rep_out[5] = rounds;
+        hipLaunchKernelGGL(p2s_uf_compress_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, W.parent, V);
+    }, &rep_out[5]);
+    if (rc != P2S_OK) return rc;
 
     // ---- c. the order of the components, the ranks
-    MESH_CHECK(who, hipMemsetAsync(W.fmin, 0x7f, (size_t)V * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(W.used, 0, (size_t)V * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(W.flag + F, 0, 4, s));
+    DEV_CHECK(who, hipMemsetAsync(W.fmin, 0x7f, (size_t)V * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(W.used, 0, (size_t)V * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(W.flag + F, 0, 4, s));
     hipLaunchKernelGGL(p2s_mc_first_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, faces_dev, F, W.parent, W.fmin);
     hipLaunchKernelGGL(p2s_mc_flag_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, faces_dev, F, W.parent, W.fmin, W.flag);
     hipLaunchKernelGGL(p2s_rp_used_kernel, dim3(blocks(3 * F, 256)), dim3(256), 0, s, faces_dev, F, W.used);
-    MESH_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipGetLastError());
     size_t tb = tmp_bytes;
-    MESH_CHECK(who, hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, W.flag, W.fstart, (int)(F + 1), s));
+    DEV_CHECK(who, hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, W.flag, W.fstart, (int)(F + 1), s));
     int hC = 0;
-    MESH_CHECK(who, hipMemcpyAsync(&hC, W.fstart + F, 4, hipMemcpyDeviceToHost, s));
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipMemcpyAsync(&hC, W.fstart + F, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     const long long C = hC;
     rep_out[1] = C;
 
     // ---- d, e. counts and measures, into scratch: the report is whole before the capacity decides
     const McOutWs O = pool.carve([&](char *b) { return carve_mc_out(b, (size_t)C); });
-    if (!O.base) return mesh_oom(who, s);
+    if (!O.base) return dev_oom(who, s);
     int end_bit = 33;                                                // 2^(end_bit - 32) - 1 >= C > every rank: SM_NO_KEY stays last
     while ((1ll << (end_bit - 32)) <= C) ++end_bit;
     hipLaunchKernelGGL(p2s_mc_rank_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, faces_dev, F, W.parent, W.fmin, W.fstart, W.comp, W.fkey);
     hipLaunchKernelGGL(p2s_mc_vkeys_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, V, W.used, W.parent, W.fmin, W.fstart, W.vkey);
-    MESH_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipGetLastError());
     tb = tmp_bytes;
-    MESH_CHECK(who, hipcub::DeviceRadixSort::SortKeys(W.tmp, tb, W.fkey, W.fsorted, (int)F, 0, end_bit, s));
+    DEV_CHECK(who, hipcub::DeviceRadixSort::SortKeys(W.tmp, tb, W.fkey, W.fsorted, (int)F, 0, end_bit, s));
     tb = tmp_bytes;
-    MESH_CHECK(who, hipcub::DeviceRadixSort::SortKeys(W.tmp, tb, W.vkey, W.vsorted, (int)V, 0, end_bit, s));
-    MESH_CHECK(who, hipMemsetAsync(O.fseg, 0, (size_t)C * 8, s));
-    MESH_CHECK(who, hipMemsetAsync(O.vseg, 0, (size_t)C * 8, s));
-    MESH_CHECK(who, hipMemsetAsync(O.ecount, 0, (size_t)C * 16, s));
+    DEV_CHECK(who, hipcub::DeviceRadixSort::SortKeys(W.tmp, tb, W.vkey, W.vsorted, (int)V, 0, end_bit, s));
+    DEV_CHECK(who, hipMemsetAsync(O.fseg, 0, (size_t)C * 8, s));
+    DEV_CHECK(who, hipMemsetAsync(O.vseg, 0, (size_t)C * 8, s));
+    DEV_CHECK(who, hipMemsetAsync(O.ecount, 0, (size_t)C * 16, s));
     hipLaunchKernelGGL(p2s_mc_box_init_kernel, dim3(blocks(6 * C, 256)), dim3(256), 0, s, O.boxi, 6 * C);
     hipLaunchKernelGGL(p2s_sm_seg_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, W.fsorted, F, C, O.fseg);
     hipLaunchKernelGGL(p2s_sm_seg_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, W.vsorted, V, C, O.vseg);
     hipLaunchKernelGGL(p2s_mc_face_part_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, verts_dev, faces_dev, W.fsorted, F, W.part);
     hipLaunchKernelGGL(p2s_mc_vert_part_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, verts_dev, W.vsorted, V, O.boxi);
-    MESH_CHECK(who, hipMemsetAsync(W.t.key, 0xff, (size_t)ecap * 8, s));
-    MESH_CHECK(who, hipMemsetAsync(W.t.cnt, 0, (size_t)ecap * 8, s));
+    DEV_CHECK(who, hipMemsetAsync(W.t.key, 0xff, (size_t)ecap * 8, s));
+    DEV_CHECK(who, hipMemsetAsync(W.t.cnt, 0, (size_t)ecap * 8, s));
     hipLaunchKernelGGL(p2s_mc_edges_kernel, dim3(blocks(3 * F, 256)), dim3(256), 0, s, faces_dev, F, W.t);
     hipLaunchKernelGGL(p2s_mc_edge_stats_kernel, dim3(blocks((long long)ecap, 256)), dim3(256), 0, s, W.t, W.parent, W.fmin, W.fstart, O.ecount);
     hipLaunchKernelGGL(p2s_mc_collect_kernel, dim3(blocks(64 * C, 256)), dim3(256), 0, s, C, W.fsorted, O.fseg, O.vseg, W.part, O.boxi, O.ecount,
                        O.counts, O.meas);
     hipLaunchKernelGGL(p2s_mc_best_kernel, dim3(1), dim3(1024), 0, s, C, O.counts, O.meas, W.best);
-    MESH_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipGetLastError());
     long long best[3] = {};
-    MESH_CHECK(who, hipMemcpyAsync(best, W.best, sizeof(best), hipMemcpyDeviceToHost, s));
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipMemcpyAsync(best, W.best, sizeof(best), hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     rep_out[2] = best[0];
     rep_out[3] = best[1];
     rep_out[4] = V - best[2];
@@ -516,10 +502,10 @@ extern "C" int p2s_mesh_components(const float *verts_dev, int64_t n_verts, cons
         p2s_set_error("%s: output buffers too small (%lld components, cap_components = %lld given)", who, C, (long long)cap_components);
         return P2S_EINVAL;
     }
-    MESH_CHECK(who, hipMemcpyAsync(comp_out_dev, W.comp, (size_t)F * 4, hipMemcpyDeviceToDevice, s));
-    MESH_CHECK(who, hipMemcpyAsync(counts_out_dev, O.counts, (size_t)C * 40, hipMemcpyDeviceToDevice, s));
-    MESH_CHECK(who, hipMemcpyAsync(measures_out_dev, O.meas, (size_t)C * 64, hipMemcpyDeviceToDevice, s));
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipMemcpyAsync(comp_out_dev, W.comp, (size_t)F * 4, hipMemcpyDeviceToDevice, s));
+    DEV_CHECK(who, hipMemcpyAsync(counts_out_dev, O.counts, (size_t)C * 40, hipMemcpyDeviceToDevice, s));
+    DEV_CHECK(who, hipMemcpyAsync(measures_out_dev, O.meas, (size_t)C * 64, hipMemcpyDeviceToDevice, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     return P2S_OK;
 }
 
@@ -539,38 +525,34 @@ extern "C" int p2s_mesh_submesh(const float *verts_dev, int64_t n_verts, const i
         p2s_set_error("%s: bad argument (%s)", who, bad);
         return P2S_EINVAL;
     }
-    if (p2s_device_count() <= device || device < 0 || device >= P2S_MAX_DEVICES) {
-        p2s_set_error("%s: no such device %d", who, device);
-        return P2S_ENODEVICE;
-    }
-    P2S_HIP_CHECK(hipSetDevice(device));
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const long long V = n_verts, F = n_faces;
     report_host[0] = V | (F << 32);
     report_host[1] = report_host[2] = 0;
-    MeshScratch pool(device);
+    PoolScratch pool(device, s);
     int rc;
     size_t t1 = 0, t2 = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t1, (int *)nullptr, (int *)nullptr, (int)(V + 1), nullptr);
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t2, (int *)nullptr, (int *)nullptr, (int)(F + 1), nullptr);
     const size_t tmp_bytes = std::max(t1, t2) + 256;
     const McSubWs W = pool.carve([&](char *b) { return carve_mc_sub(b, (size_t)V, (size_t)F, tmp_bytes); });
-    if (!W.base) return mesh_oom(who, s);
+    if (!W.base) return dev_oom(who, s);
     if (V > 0 || F > 0) {
         if ((rc = mc_validate(who, verts_dev, V, faces_dev, F, W.ctl, s)) != P2S_OK) return rc;
     }
-    MESH_CHECK(who, hipMemsetAsync(W.used, 0, (size_t)(V + 1) * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(W.keep01 + F, 0, 4, s));
+    DEV_CHECK(who, hipMemsetAsync(W.used, 0, (size_t)(V + 1) * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(W.keep01 + F, 0, 4, s));
     if (F > 0) hipLaunchKernelGGL(p2s_mc_keep_used_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, faces_dev, F, keep_dev, W.keep01, W.used);
-    MESH_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipGetLastError());
     size_t tb = tmp_bytes;
-    MESH_CHECK(who, hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, W.used, W.vstart, (int)(V + 1), s));
+    DEV_CHECK(who, hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, W.used, W.vstart, (int)(V + 1), s));
     tb = tmp_bytes;
-    MESH_CHECK(who, hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, W.keep01, W.kstart, (int)(F + 1), s));
+    DEV_CHECK(who, hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, W.keep01, W.kstart, (int)(F + 1), s));
     int hV = 0, hF = 0;
-    MESH_CHECK(who, hipMemcpyAsync(&hV, W.vstart + V, 4, hipMemcpyDeviceToHost, s));
-    MESH_CHECK(who, hipMemcpyAsync(&hF, W.kstart + F, 4, hipMemcpyDeviceToHost, s));
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipMemcpyAsync(&hV, W.vstart + V, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipMemcpyAsync(&hF, W.kstart + F, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     report_host[1] = hV;
     report_host[2] = hF;
     if (cap_verts < hV || cap_faces < hF) {
@@ -585,7 +567,7 @@ extern "C" int p2s_mesh_submesh(const float *verts_dev, int64_t n_verts, const i
     }
     if (vert_map_out_dev && V > 0)
         hipLaunchKernelGGL(p2s_mc_vmap_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, V, W.used, W.vstart, vert_map_out_dev);
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipStreamSynchronize(s));
     return P2S_OK;
 }

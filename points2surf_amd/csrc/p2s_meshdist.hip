@@ -14,8 +14,9 @@
 //   p2s_md_validate_kernel    indices in range, vertices finite, bounding box             (before anything dereferences)
 //   p2s_md_edges_kernel / p2s_rp_edge_faces_kernel   undirected edges into an open-addressing table: traversals and faces
 //   p2s_md_volume_kernel / p2s_md_comp_volume_kernel   signed volume, of the mesh and per component (one workgroup, fixed order)
-//   p2s_md_cc_hook_kernel / p2s_md_cc_compress_kernel / p2s_md_cc_count_kernel   connected components (union-find over neighbours)
-//   p2s_md_scan_kernel        exclusive scan (one workgroup)
+//   p2s_md_cc_hook_kernel / p2s_md_cc_count_kernel   connected components (union-find over neighbours)
+//   p2s_devprim.inl           f2o / o2f, uf_find, p2s_uf_compress_kernel, p2s_iota_kernel, p2s_scan_kernel (exclusive scan,
+//                             one workgroup); the host scaffold of the entry points is p2s_devcall.h
 //  2. p2s_mesh_octree.inl: the implicit octree, its node ids, the stack and the counters of its three walks
 //  3. p2s_meshbuild.inl: the handle, p2s_trimesh_create / destroy / info
 //   p2s_md_edge_check_kernel  edges that are not (once forward, once backward)
@@ -56,6 +57,7 @@
 // operations in the same association.
 #include "p2s_common.h"
 #include "p2s_internal.h"
+#include "p2s_devcall.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -67,19 +69,14 @@
 // ---- 1. shared primitives: arithmetic, the kernels that the build and the repair both launch, the host scaffold
 namespace {
 
+#include "p2s_devprim.inl"
+
 constexpr unsigned long long EDGE_EMPTY = ~0ull;
 constexpr double FIX = 1099511627776.0;          // 2^40
 constexpr double DEGENERATE_REL = 8.077935669463161e-28;   // 2^-90
 // a face with a corner sine below 2^-20: its unit normal carries more than 3 * 2^-53 / 2^-20 < 2^-31 of error, which the
 // trust bound of the sign assumes -- queries whose pseudonormal involves such a face go to the winding number
 constexpr double SLIVER_REL = 9.094947017729282e-13;       // 2^-40 (on sin^2)
-
-// order-preserving float <-> int (its own inverse), on the device and on the host
-__host__ __device__ __forceinline__ int f2o(float f) {
-    const int i = __builtin_bit_cast(int, f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__host__ __device__ __forceinline__ float o2f(int i) { return __builtin_bit_cast(float, i >= 0 ? i : i ^ 0x7fffffff); }
 
 __device__ __forceinline__ double dot3(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 __device__ __forceinline__ void cross3(const double *a, const double *b, double *o) {
@@ -205,27 +202,18 @@ __global__ __launch_bounds__(1024) void p2s_md_volume_kernel(const float *__rest
 }
 
 // connected components: union-find with hooking to the smaller root and full compression, repeated until nothing changes
-__device__ __forceinline__ int cc_find(const int *parent, int x) {
-    for (int p = parent[x]; p != x; p = parent[x]) x = p;          // parents only decrease: no cycles
-    return x;
-}
 __global__ __launch_bounds__(256) void p2s_md_cc_hook_kernel(const int *__restrict__ adj, int *parent, long long F, int *changed) {
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
     for (int e = 0; e < 3; ++e) {
         const int g = adj[3 * f + e];
         if (g < 0) continue;
-        const int rf = cc_find(parent, (int)f), rg = cc_find(parent, g);
+        const int rf = uf_find(parent, (int)f), rg = uf_find(parent, g);
         if (rf != rg) {
             atomicMin(&parent[max(rf, rg)], min(rf, rg));
             *changed = 1;
         }
     }
-}
-__global__ __launch_bounds__(256) void p2s_md_cc_compress_kernel(int *parent, long long F, int init) {
-    const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (f >= F) return;
-    parent[f] = init ? (int)f : cc_find(parent, (int)f);
 }
 __global__ __launch_bounds__(256) void p2s_md_cc_count_kernel(const int *__restrict__ parent, long long F, unsigned long long *count) {
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -254,92 +242,8 @@ __global__ __launch_bounds__(1024) void p2s_md_comp_volume_kernel(const double *
     }
 }
 
-// exclusive scan of count [n] into start [n + 1] (one workgroup, chunks of 1024)
-__global__ __launch_bounds__(1024) void p2s_md_scan_kernel(const int *__restrict__ count, long long n, int *__restrict__ start) {
-    __shared__ int ws[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int carry = 0;
-    for (long long b0 = 0; b0 < n; b0 += 1024) {
-        const long long i = b0 + tid;
-        const int c = i < n ? count[i] : 0;
-        int v = c;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int u = __shfl_up(v, d);
-            if (lane >= d) v += u;
-        }
-        if (lane == 63) ws[wave] = v;
-        __syncthreads();
-        int base = carry, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            if (w < wave) base += ws[w];
-            tot += ws[w];
-        }
-        if (i < n) start[i] = base + v - c;
-        carry += tot;
-        __syncthreads();
-    }
-    if (tid == 0) start[n] = carry;
-}
-
-// ---- the host scaffold of every entry point of this unit
-unsigned blocks(long long n, int per) { return (unsigned)std::max<long long>(1, (n + per - 1) / per); }
-
-// A HIP error ends the call: the stream is drained BEFORE the return, so that the guards below (MeshScratch, the handle
-// under construction) hand no block back to the device's cache under a running kernel.  `s` is the call's stream.
-int mesh_hip_error(const char *who, hipError_t e, const char *what, hipStream_t s) {
-    (void)hipStreamSynchronize(s);
-    p2s_set_error("%s: %s (%s)", who, hipGetErrorString(e), what);
-    return P2S_EHIP;
-}
-int mesh_oom(const char *who, hipStream_t s) {
-    (void)hipStreamSynchronize(s);
-    p2s_set_error("%s: out of device memory", who);
-    return P2S_ENOMEM;
-}
-#define MESH_CHECK(who, expr)                                                    \
-    do {                                                                         \
-        hipError_t _e = (expr);                                                  \
-        if (_e != hipSuccess) return mesh_hip_error(who, _e, #expr, s);          \
-    } while (0)
-
-// One workspace layout is one function over a Carver (as carve of p2s_forward.hip): run on a null base it gives the size,
-// on the block the pointers.  The function returns a struct that ends in `char *base; size_t bytes;`.
-struct Carver {
-    char *base;
-    size_t at = 0;
-    template <class T> T *take(size_t count, bool present = true) {      // an absent region: NULL, no room
-        T *p = base && present ? (T *)(base + at) : nullptr;
-        at += present ? (count * sizeof(T) + 255) & ~(size_t)255 : 0;
-        return p;
-    }
-    template <class W> W done(W w) const {                             // the layout, complete
-        w.base = base;
-        w.bytes = at;
-        return w;
-    }
-};
-// the blocks of the device's cache that one call holds, all returned when the call ends
-struct MeshScratch {
-    int device;
-    std::vector<void *> held;
-    explicit MeshScratch(int d) : device(d) {}
-    MeshScratch(const MeshScratch &) = delete;
-    ~MeshScratch() {
-        for (void *p : held) p2s_pool_free(device, p);
-    }
-    char *get(size_t bytes) {
-        void *p = p2s_pool_alloc(device, bytes ? bytes : 256);
-        if (p) held.push_back(p);
-        return (char *)p;
-    }
-    // a block of the layout `layout(base)`; out of memory: base == NULL (and bytes = what was asked for)
-    template <class Fn> auto carve(Fn layout) -> decltype(layout((char *)nullptr)) {
-        const auto size = layout((char *)nullptr);
-        char *p = get(size.bytes);
-        return p ? layout(p) : size;
-    }
-};
-
+// ---- the host scaffold of every entry point of this unit, on top of p2s_devcall.h.  Every entry point still ends drained
+// on success and drains before it sets an error text; PoolScratch drains once more before its blocks return to the cache
 EdgeTable carve_edges(Carver &c, unsigned cap) {
     EdgeTable t;
     t.key = c.take<unsigned long long>(cap);
@@ -351,16 +255,16 @@ EdgeTable carve_edges(Carver &c, unsigned cap) {
 // the edge table of `faces`: p2s_md_edges_kernel, then the two extreme face ids of every edge when asked for
 int build_edges(const char *who, const int *faces, long long F, EdgeTable t, int *fmn, int *fmx, hipStream_t s) {
     const size_t cap = (size_t)t.mask + 1;
-    MESH_CHECK(who, hipMemsetAsync(t.key, 0xff, cap * 8, s));
-    MESH_CHECK(who, hipMemsetAsync(t.cnt, 0, cap * 8, s));
-    MESH_CHECK(who, hipMemsetAsync(t.face, 0xff, cap * 8, s));
+    DEV_CHECK(who, hipMemsetAsync(t.key, 0xff, cap * 8, s));
+    DEV_CHECK(who, hipMemsetAsync(t.cnt, 0, cap * 8, s));
+    DEV_CHECK(who, hipMemsetAsync(t.face, 0xff, cap * 8, s));
     hipLaunchKernelGGL(p2s_md_edges_kernel, dim3(blocks(3 * F, 256)), dim3(256), 0, s, faces, F, t);
     if (fmn) {
-        MESH_CHECK(who, hipMemsetAsync(fmn, 0x7f, cap * 4, s));
-        MESH_CHECK(who, hipMemsetAsync(fmx, 0xff, cap * 4, s));
+        DEV_CHECK(who, hipMemsetAsync(fmn, 0x7f, cap * 4, s));
+        DEV_CHECK(who, hipMemsetAsync(fmx, 0xff, cap * 4, s));
         hipLaunchKernelGGL(p2s_rp_edge_faces_kernel, dim3(blocks(3 * F, 256)), dim3(256), 0, s, faces, F, t, fmn, fmx);
     }
-    MESH_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipGetLastError());
     return P2S_OK;
 }
 
@@ -368,11 +272,11 @@ int build_edges(const char *who, const int *faces, long long F, EdgeTable t, int
 int mesh_validate(const char *who, const float *verts, long long V, const int *faces, long long F, int *ctl, float *box, hipStream_t s) {
     const int init[16] = {0, 0x7f800000, 0x7f800000, 0x7f800000, (int)0x807fffff, (int)0x807fffff, (int)0x807fffff, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     int h[16] = {};
-    MESH_CHECK(who, hipMemcpyAsync(ctl, init, 64, hipMemcpyHostToDevice, s));
+    DEV_CHECK(who, hipMemcpyAsync(ctl, init, 64, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(p2s_md_validate_kernel, dim3(blocks(std::max(V, F), 256)), dim3(256), 0, s, verts, V, faces, F, ctl);
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipMemcpyAsync(h, ctl, 64, hipMemcpyDeviceToHost, s));
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(h, ctl, 64, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (h[0]) {
         p2s_set_error("%s: %s", who, (h[0] & 2) ? "face index out of range" : "non-finite vertex");
         return P2S_EINVAL;
@@ -387,30 +291,11 @@ int mesh_validate(const char *who, const float *verts, long long V, const int *f
 constexpr size_t MESH_COUNTERS = 64;
 int read_counters(const char *who, const unsigned long long *ctr, unsigned long long *host, int overflow, const char *overflow_msg,
                   hipStream_t s) {
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipMemcpyAsync(host, ctr, MESH_COUNTERS, hipMemcpyDeviceToHost, s));
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(host, ctr, MESH_COUNTERS, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (overflow >= 0 && host[overflow]) {
         p2s_set_error("%s: %s", who, overflow_msg);
-        return P2S_EHIP;
-    }
-    return P2S_OK;
-}
-
-// rounds of a union-find (`round` launches them; a kernel that merged two trees raises ctl[0]) until one changes nothing:
-// every round that changes something merges two trees, so it ends; the cap only guards the host loop, and hitting it is
-// an error
-template <class Round> int until_unchanged(const char *who, const char *what, int *ctl, hipStream_t s, Round round) {
-    int changed = 1;
-    for (int it = 0; it < 100000 && changed; ++it) {
-        MESH_CHECK(who, hipMemsetAsync(ctl, 0, 4, s));
-        round();
-        MESH_CHECK(who, hipGetLastError());
-        MESH_CHECK(who, hipMemcpyAsync(&changed, ctl, 4, hipMemcpyDeviceToHost, s));
-        MESH_CHECK(who, hipStreamSynchronize(s));
-    }
-    if (changed) {
-        p2s_set_error("%s: %s did not converge", who, what);
         return P2S_EHIP;
     }
     return P2S_OK;
@@ -992,10 +877,10 @@ extern "C" int p2s_mesh_distance(p2s_trimesh_t m, const float *query_dev, int64_
     long long per = m->F;
     if (method == 1) exhaustive_parts(m->F, n, EX_TILE, &parts, &per);
     const bool per_comp = signed_ && m->components >= 2 && m->components <= 16;
-    MeshScratch pool(m->device);
+    PoolScratch pool(m->device, s);
     const DistWs w = pool.carve([&](char *b) { return carve_dist(b, (size_t)n, parts, per_comp, by_winding); });
-    if (!w.base) return mesh_oom(who, s);
-    MESH_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
+    if (!w.base) return dev_oom(who, s);
+    DEV_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
     const OctreeDev ix = octree_of(m);
     // the nearest face of the whole mesh (comp < 0) or of one component, into best_face or the parts
     auto nearest = [&](int comp, unsigned long long *tests) {
@@ -1027,8 +912,8 @@ extern "C" int p2s_mesh_distance(p2s_trimesh_t m, const float *query_dev, int64_
     if (hc[DC_FLAGGED] > 0) {
         hipLaunchKernelGGL(p2s_md_winding_kernel, dim3((unsigned)hc[DC_FLAGGED]), dim3(256), 0, s, m->tri, m->F, query_dev,
                            (const int *)w.flagged, dist_out_dev, (double *)nullptr, (double *)nullptr);
-        MESH_CHECK(who, hipGetLastError());
-        MESH_CHECK(who, hipStreamSynchronize(s));
+        DEV_CHECK(who, hipGetLastError());
+        DEV_CHECK(who, hipStreamSynchronize(s));
     }
     m->last_tests = (long long)hc[DC_TESTS];
     if (n_winding_host) *n_winding_host = (int64_t)hc[DC_FLAGGED];
@@ -1049,7 +934,7 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
     hipStream_t s = (hipStream_t)stream;
     unsigned long long hc[8] = {}, n_exact = (unsigned long long)n;
     const int *list = nullptr;                                 // the queries of the exact sum: every one, or the walk's undecided
-    MeshScratch pool(m->device);
+    PoolScratch pool(m->device, s);
     if (method == 1) {
         hc[WT_TRIS] = (unsigned long long)n * (unsigned long long)m->F;
     } else {
@@ -1066,8 +951,8 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
             r.ctr = c.take<unsigned long long>(8);
             return c.done(r);
         });
-        if (!w.base) return mesh_oom(who, s);
-        MESH_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
+        if (!w.base) return dev_oom(who, s);
+        DEV_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
         launch_wtree(m, query_dev, (long long)n, tau, w_out_dev, err_out_dev, w.undecided, w.ctr, s);
         const int rc = read_counters(who, w.ctr, hc, WT_OVERFLOW, "the walk overflowed its stack", s);
         if (rc != P2S_OK) return rc;
@@ -1077,8 +962,8 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
     if (n_exact > 0) {                                         // the exact value, bound 0
         hipLaunchKernelGGL(p2s_md_winding_kernel, dim3((unsigned)n_exact), dim3(256), 0, s, m->tri, m->F, query_dev, list,
                            (double *)nullptr, w_out_dev, err_out_dev);
-        MESH_CHECK(who, hipGetLastError());
-        MESH_CHECK(who, hipStreamSynchronize(s));
+        DEV_CHECK(who, hipGetLastError());
+        DEV_CHECK(who, hipStreamSynchronize(s));
     }
     if (stats_host) {
         stats_host[0] = (int64_t)hc[WT_ACCEPTED];

@@ -2,7 +2,7 @@
 // the GT data -- the part of the reference's make_dataset.py that starts one BlenSor process per mesh (:242-380, 5..30
 // scans of 176 x 144 rays) and calls trimesh (source/sdf.py:288-315).  Included at the end of p2s_meshdist.hip: the
 // handle, the octree with its walk helpers (p2s_mesh_octree.inl), the host scaffold, the ordered-integer bounds, dot3 /
-// cross3 / finite3, DEGENERATE_REL and the one-workgroup scan (p2s_md_scan_kernel) are that unit's, used here, not copied.
+// cross3 / finite3, DEGENERATE_REL and the one-workgroup scan (p2s_scan_kernel) are that unit's, used here, not copied.
 //   p2s_mr_index_kernel       first hit per ray: depth-first descent of the octree, children in the ray's front-to-back order
 //   p2s_mr_exhaustive_kernel  every ray against every triangle, faces split over grid.y, prepared triangles staged in LDS
 //   p2s_mr_merge_kernel       the parts of the exhaustive kernel into one answer per ray
@@ -393,13 +393,13 @@ extern "C" int p2s_mesh_raycast(p2s_trimesh_t m, const double *rays_dev, int64_t
     int parts = 0;
     long long per = m->F;
     if (method == 1) exhaustive_parts(m->F, n, RX_TILE, &parts, &per);
-    MeshScratch pool(m->device);
+    PoolScratch pool(m->device, s);
     const CastWs w = pool.carve([&](char *b) {
         Carver c{b};
         return c.done(carve_cast(c, (size_t)n, parts));
     });
-    if (!w.base) return mesh_oom(who, s);
-    MESH_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
+    if (!w.base) return dev_oom(who, s);
+    DEV_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
     ray_cast_launch(m, rays_dev, n, t_max, method, 0, 0, t_out_dev, face_out_dev, w, parts, per, s);
     unsigned long long hc[8] = {};
     const int rc = read_counters(who, w.ctr, hc, RC_OVERFLOW, RAY_OVERFLOW, s);
@@ -486,24 +486,24 @@ extern "C" int p2s_mesh_tof_scan(p2s_trimesh_t m, const double *poses_host, int3
     long long per = m->F;
     if (method == 1) exhaustive_parts(m->F, n, RX_TILE, &parts, &per);
     const long long nb = (n + 1023) / 1024;
-    MeshScratch pool(m->device);
+    PoolScratch pool(m->device, s);
     const ScanWs w = pool.carve([&](char *b) { return carve_scan(b, (size_t)n, (size_t)n_scans, (size_t)nb, parts); });
-    if (!w.base) return mesh_oom(who, s);
-    MESH_CHECK(who, hipMemcpyAsync(w.pose, pose.data(), pose.size() * 8, hipMemcpyHostToDevice, s));
-    MESH_CHECK(who, hipMemsetAsync(w.cast.ctr, 0, MESH_COUNTERS, s));
-    MESH_CHECK(who, hipMemsetAsync(w.scan_count, 0, (size_t)n_scans * 4, s));
+    if (!w.base) return dev_oom(who, s);
+    DEV_CHECK(who, hipMemcpyAsync(w.pose, pose.data(), pose.size() * 8, hipMemcpyHostToDevice, s));
+    DEV_CHECK(who, hipMemsetAsync(w.cast.ctr, 0, MESH_COUNTERS, s));
+    DEV_CHECK(who, hipMemsetAsync(w.scan_count, 0, (size_t)n_scans * 4, s));
     hipLaunchKernelGGL(p2s_mr_rays_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, w.pose, n, W, H, sensor->tan_half_w, sensor->tan_half_h, w.rays);
     ray_cast_launch(m, w.rays, n, sensor->max_distance, method, W, H, w.t, w.face, w.cast, parts, per, s);
     hipLaunchKernelGGL(p2s_mr_count_kernel, dim3((unsigned)nb), dim3(1024), 0, s, w.face, n, per_scan, w.block_count, w.scan_count);
-    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, w.block_count, nb, w.block_start);
+    hipLaunchKernelGGL(p2s_scan_kernel, dim3(1), dim3(1024), 0, s, w.block_count, nb, w.block_start);
     const CompactArgs a = {w.rays, w.t, noise_dev, m->fn, w.face, w.block_start, n, sigma, noisy_out_dev, clean_out_dev, normal_out_dev,
                            face_out_dev};
     hipLaunchKernelGGL(p2s_mr_compact_kernel, dim3((unsigned)nb), dim3(1024), 0, s, a);
     unsigned long long hc[8] = {};
     int total = 0;
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipMemcpyAsync(&total, w.block_start + nb, 4, hipMemcpyDeviceToHost, s));
-    MESH_CHECK(who, hipMemcpyAsync(hits_per_scan_host, w.scan_count, (size_t)n_scans * 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(&total, w.block_start + nb, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipMemcpyAsync(hits_per_scan_host, w.scan_count, (size_t)n_scans * 4, hipMemcpyDeviceToHost, s));
     const int rc = read_counters(who, w.cast.ctr, hc, RC_OVERFLOW, RAY_OVERFLOW, s);
     if (rc != P2S_OK) return rc;
     *n_hits_host = total;

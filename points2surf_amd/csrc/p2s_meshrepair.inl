@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void p2s_rp_hole_fill_kernel(long long V, cons
         cur = nxt[cur];
     }
 }
-// groups of the boundary edges that remain: union-find over the vertices (cc_find, hooking to the smaller root)
+// groups of the boundary edges that remain: union-find over the vertices (uf_find, hooking to the smaller root)
 __global__ __launch_bounds__(256) void p2s_rp_bhook_kernel(const int *__restrict__ faces, long long F, EdgeTable t, int *parent, int *changed) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= 3 * F) return;
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256) void p2s_rp_bhook_kernel(const int *__restrict
     const int a = faces[3 * f + e], b = faces[3 * f + (e + 1) % 3];
     const unsigned h = rp_edge_slot(t, a, b);
     if (t.cnt[2 * h] + t.cnt[2 * h + 1] != 1) return;
-    const int ra = cc_find(parent, a), rb = cc_find(parent, b);
+    const int ra = uf_find(parent, a), rb = uf_find(parent, b);
     if (ra != rb) {
         atomicMin(&parent[max(ra, rb)], min(ra, rb));
         *changed = 1;
@@ -509,11 +509,7 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
         p2s_set_error("p2s_mesh_repair: bad argument (vertices <= 2^27, faces <= 2^25, max_hole_edges in 0..64)");
         return P2S_EINVAL;
     }
-    if (p2s_device_count() <= device || device < 0 || device >= P2S_MAX_DEVICES) {
-        p2s_set_error("p2s_mesh_repair: no such device %d", device);
-        return P2S_ENODEVICE;
-    }
-    P2S_HIP_CHECK(hipSetDevice(device));
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const long long V = n_verts, F = n_faces;
     const int K = max_hole_edges;
@@ -522,13 +518,13 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
     auto publish = [&]() {
         for (int k = 0; k < 16; ++k) report_host[k] = rep_out[k];
     };
-    MeshScratch pool(device);
+    PoolScratch pool(device, s);
     int rc;
 
     // ---- a. validate
     const unsigned vcap = rp_table_cap(V), fcap = rp_table_cap(F);
     const RpWeldWs A = pool.carve([&](char *b) { return carve_weld(b, (size_t)V, (size_t)F, vcap, fcap); });
-    if (!A.base) return mesh_oom(who, s);
+    if (!A.base) return dev_oom(who, s);
     int *ctl = A.ctl;
     unsigned long long *ctr = A.ctr, hc[8] = {};
     if (V > 0 || F > 0) {
@@ -542,18 +538,18 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
     }
 
     // ---- b, c. weld, collapsed and duplicate faces
-    MESH_CHECK(who, hipMemsetAsync(A.vslot, 0xff, (size_t)vcap * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(A.fslot, 0xff, (size_t)fcap * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
+    DEV_CHECK(who, hipMemsetAsync(A.vslot, 0xff, (size_t)vcap * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(A.fslot, 0xff, (size_t)fcap * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
     hipLaunchKernelGGL(p2s_rp_weld_insert_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, verts_dev, V, A.vslot, vcap - 1);
     hipLaunchKernelGGL(p2s_rp_weld_map_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, verts_dev, V, A.vslot, vcap - 1, A.rep, ctr + RP_WELDED);
     hipLaunchKernelGGL(p2s_rp_face_weld_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, faces_dev, F, A.rep, A.wfa, A.keep, ctr + RP_COLLAPSED);
     hipLaunchKernelGGL(p2s_rp_face_insert_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, A.wfa, F, A.keep, A.fslot, fcap - 1);
     hipLaunchKernelGGL(p2s_rp_face_keep_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, A.wfa, F, A.keep, A.fslot, fcap - 1, ctr + RP_DUPLICATE);
-    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, A.keep, F, A.kstart);
+    hipLaunchKernelGGL(p2s_scan_kernel, dim3(1), dim3(1024), 0, s, A.keep, F, A.kstart);
     int hF0 = 0;
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipMemcpyAsync(&hF0, A.kstart + F, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(&hF0, A.kstart + F, 4, hipMemcpyDeviceToHost, s));
     if ((rc = read_counters(who, ctr, hc, -1, nullptr, s)) != P2S_OK) return rc;
     const long long F0 = hF0;
     rep_out[3] = (long long)hc[RP_WELDED];
@@ -567,19 +563,19 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
 
     // ---- d. orient
     const RpOrientWs B = pool.carve([&](char *b) { return carve_orient(b, (size_t)V, (size_t)F0, rp_table_cap(3 * F0)); });
-    if (!B.base) return mesh_oom(who, s);
-    MESH_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
+    if (!B.base) return dev_oom(who, s);
+    DEV_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
     hipLaunchKernelGGL(p2s_rp_gather_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, verts_dev, A.wfa, F, A.keep, A.kstart, B.wf, B.src,
                        ctr + RP_DEGENERATE);
     if ((rc = build_edges(who, B.wf, F0, B.t, B.fmn, B.fmx, s)) != P2S_OK) return rc;
     hipLaunchKernelGGL(p2s_rp_adj_kernel, dim3(blocks(3 * F0, 256)), dim3(256), 0, s, B.wf, F0, B.t, B.fmn, B.fmx, B.adj, B.par);
     hipLaunchKernelGGL(p2s_rp_par_compress_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, B.link, F0, 1);
-    rc = until_unchanged(who, "the orientation", ctl, s, [&] {
+    rc = until_unchanged(who, "the orientation", 100000, ctl, s, [&](long long) {
         hipLaunchKernelGGL(p2s_rp_par_hook_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, B.adj, B.par, B.link, F0, ctl);
         hipLaunchKernelGGL(p2s_rp_par_compress_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, B.link, F0, 0);
     });
     if (rc != P2S_OK) return rc;
-    MESH_CHECK(who, hipMemsetAsync(B.badroot, 0, (size_t)F0 * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(B.badroot, 0, (size_t)F0 * 4, s));
     hipLaunchKernelGGL(p2s_rp_par_check_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, B.adj, B.par, B.link, F0, B.badroot);
     hipLaunchKernelGGL(p2s_rp_par_apply_kernel, dim3(blocks(F0, 256)), dim3(256), 0, s, B.link, B.badroot, F0, B.wf, B.flipped, B.unor,
                        ctr + RP_FLIPPED);                            // and RP_UNORIENTABLE behind it
@@ -587,13 +583,13 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
     // ---- e. holes, on the oriented faces
     if ((rc = build_edges(who, B.wf, F0, B.t, nullptr, nullptr, s)) != P2S_OK) return rc;
     int *outc = B.vtx, *inc = outc + V, *nxt = inc + V, *blocked = nxt + V, *addc = blocked + V;
-    MESH_CHECK(who, hipMemsetAsync(B.vtx, 0, (size_t)V * 4 * 5, s));
+    DEV_CHECK(who, hipMemsetAsync(B.vtx, 0, (size_t)V * 4 * 5, s));
     hipLaunchKernelGGL(p2s_rp_boundary_kernel, dim3(blocks(3 * F0, 256)), dim3(256), 0, s, B.wf, F0, B.t, B.unor, outc, inc, nxt, blocked);
     hipLaunchKernelGGL(p2s_rp_hole_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, V, K, outc, inc, nxt, blocked, addc, ctr + RP_HOLES);
-    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, addc, V, B.addstart);
+    hipLaunchKernelGGL(p2s_scan_kernel, dim3(1), dim3(1024), 0, s, addc, V, B.addstart);
     int h_added = 0;
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipMemcpyAsync(&h_added, B.addstart + V, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(&h_added, B.addstart + V, 4, hipMemcpyDeviceToHost, s));
     if ((rc = read_counters(who, ctr, hc, -1, nullptr, s)) != P2S_OK) return rc;
     rep_out[6] = (long long)hc[RP_DEGENERATE];
     rep_out[7] = (long long)hc[RP_FLIPPED];
@@ -605,37 +601,37 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
     // ---- f. components of the filled mesh, inversion
     const unsigned ecap1 = rp_table_cap(3 * F1);
     const RpFillWs C = pool.carve([&](char *b) { return carve_fill(b, (size_t)V, (size_t)F1, ecap1); });
-    if (!C.base) return mesh_oom(who, s);
-    MESH_CHECK(who, hipMemcpyAsync(C.wf, B.wf, (size_t)F0 * 12, hipMemcpyDeviceToDevice, s));
+    if (!C.base) return dev_oom(who, s);
+    DEV_CHECK(who, hipMemcpyAsync(C.wf, B.wf, (size_t)F0 * 12, hipMemcpyDeviceToDevice, s));
     if (h_added) hipLaunchKernelGGL(p2s_rp_hole_fill_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, V, nxt, addc, B.addstart, F0, C.wf);
-    MESH_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
+    DEV_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
     if ((rc = build_edges(who, C.wf, F1, C.t, C.fmn, C.fmx, s)) != P2S_OK) return rc;
     hipLaunchKernelGGL(p2s_rp_edge_stats_kernel, dim3(blocks(ecap1, 256)), dim3(256), 0, s, C.t, ctr + RP_BOUNDARY);      // .. RP_INCONSISTENT
     hipLaunchKernelGGL(p2s_rp_adj_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, C.wf, F1, C.t, C.fmn, C.fmx, C.adj, (unsigned char *)nullptr);
-    hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.parent, F1, 1);
-    hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, B.bparent, V, 1);
-    rc = until_unchanged(who, "the connected components", ctl, s, [&] {
+    hipLaunchKernelGGL(p2s_iota_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.parent, F1);
+    hipLaunchKernelGGL(p2s_iota_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, B.bparent, V);
+    rc = until_unchanged(who, "the connected components", 100000, ctl, s, [&](long long) {
         hipLaunchKernelGGL(p2s_md_cc_hook_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.adj, C.parent, F1, ctl);
-        hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.parent, F1, 0);
+        hipLaunchKernelGGL(p2s_uf_compress_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.parent, F1);
         hipLaunchKernelGGL(p2s_rp_bhook_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, C.wf, F1, C.t, B.bparent, ctl);
-        hipLaunchKernelGGL(p2s_md_cc_compress_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, B.bparent, V, 0);
+        hipLaunchKernelGGL(p2s_uf_compress_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, B.bparent, V);
     });
     if (rc != P2S_OK) return rc;
-    MESH_CHECK(who, hipMemsetAsync(C.flag, 0, (size_t)F1 * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(C.onb, 0, (size_t)V * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(C.flag, 0, (size_t)F1 * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(C.onb, 0, (size_t)V * 4, s));
     hipLaunchKernelGGL(p2s_rp_open_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, C.wf, F1, C.t, C.parent, C.flag);
     hipLaunchKernelGGL(p2s_rp_bmark_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, C.wf, F1, C.t, C.onb);
     hipLaunchKernelGGL(p2s_rp_bcount_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, B.bparent, C.onb, V, ctr + RP_BGROUPS);
     hipLaunchKernelGGL(p2s_md_cc_count_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.parent, F1, ctr + RP_COMPONENTS);
     hipLaunchKernelGGL(p2s_rp_roots_flag_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.parent, F1, C.flag);
-    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, C.flag, F1, C.rstart);
+    hipLaunchKernelGGL(p2s_scan_kernel, dim3(1), dim3(1024), 0, s, C.flag, F1, C.rstart);
     int n_closed = 0;
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipMemcpyAsync(&n_closed, C.rstart + F1, 4, hipMemcpyDeviceToHost, s));
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(&n_closed, C.rstart + F1, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (n_closed > 0) {
         const RpVolumeWs D = pool.carve([&](char *b) { return carve_volume(b, (size_t)F1, (size_t)n_closed); });
-        if (!D.base) return mesh_oom(who, s);
+        if (!D.base) return dev_oom(who, s);
         hipLaunchKernelGGL(p2s_rp_roots_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.flag, C.rstart, F1, D.roots);
         hipLaunchKernelGGL(p2s_rp_tri_kernel, dim3(blocks(9 * F1, 256)), dim3(256), 0, s, verts_dev, C.wf, F1, D.tri);
         hipLaunchKernelGGL(p2s_md_comp_volume_kernel, dim3((unsigned)n_closed), dim3(1024), 0, s, D.tri, C.parent, F1, D.roots, D.vol);
@@ -643,13 +639,13 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
                            ctr + RP_INVERTED);
     }
     // ---- g. compaction, h. report
-    MESH_CHECK(who, hipMemsetAsync(C.used, 0, (size_t)V * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(C.used, 0, (size_t)V * 4, s));
     hipLaunchKernelGGL(p2s_rp_used_kernel, dim3(blocks(3 * F1, 256)), dim3(256), 0, s, C.wf, F1, C.used);
-    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, C.used, V, C.vstart);
+    hipLaunchKernelGGL(p2s_scan_kernel, dim3(1), dim3(1024), 0, s, C.used, V, C.vstart);
     hipLaunchKernelGGL(p2s_md_volume_kernel, dim3(1), dim3(1024), 0, s, verts_dev, C.wf, F1, (double *)(ctr + RP_VOLUME));
     int hV1 = 0;
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipMemcpyAsync(&hV1, C.vstart + V, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(&hV1, C.vstart + V, 4, hipMemcpyDeviceToHost, s));
     if ((rc = read_counters(who, ctr, hc, -1, nullptr, s)) != P2S_OK) return rc;      // also: every block of `pool` is idle from here on
     double vol6;
     memcpy(&vol6, &hc[RP_VOLUME], 8);
@@ -670,8 +666,8 @@ extern "C" int p2s_mesh_repair(const float *verts_dev, int64_t n_verts, const in
     hipLaunchKernelGGL(p2s_rp_write_verts_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, verts_dev, V, C.used, C.vstart, verts_out_dev);
     hipLaunchKernelGGL(p2s_rp_write_faces_kernel, dim3(blocks(F1, 256)), dim3(256), 0, s, C.wf, B.src, F1, F0, C.vstart, faces_out_dev,
                        face_src_out_dev);
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipStreamSynchronize(s));
     return P2S_OK;
 }
 
@@ -681,15 +677,11 @@ extern "C" int p2s_mesh_normalize(const float *verts_dev, int64_t n_verts, float
         p2s_set_error("p2s_mesh_normalize: bad argument (1 <= vertices <= 2^27)");
         return P2S_EINVAL;
     }
-    if (p2s_device_count() <= device || device < 0 || device >= P2S_MAX_DEVICES) {
-        p2s_set_error("p2s_mesh_normalize: no such device %d", device);
-        return P2S_ENODEVICE;
-    }
-    P2S_HIP_CHECK(hipSetDevice(device));
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    MeshScratch pool(device);
-    int *ctl = (int *)pool.get(256);
-    if (!ctl) return mesh_oom(who, s);
+    PoolScratch pool(device, s);
+    int *ctl = pool.get<int>(64);
+    if (!ctl) return dev_oom(who, s);
     float box[6];
     const int rc = mesh_validate(who, verts_dev, (long long)n_verts, (const int *)nullptr, 0ll, ctl, box, s);
     if (rc != P2S_OK) return rc;
@@ -708,8 +700,8 @@ extern "C" int p2s_mesh_normalize(const float *verts_dev, int64_t n_verts, float
     const double sc = 1.0 / ext;
     hipLaunchKernelGGL(p2s_rp_normalize_kernel, dim3(blocks(3 * n_verts, 256)), dim3(256), 0, s, verts_dev, (long long)n_verts, c[0], c[1], c[2],
                        sc, verts_out_dev);
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (info_host) {
         info_host[0] = c[0];
         info_host[1] = c[1];

@@ -14,7 +14,7 @@
 //   p2s_sm_seg_kernel          where an output id's run begins and ends in the sorted keys
 //   p2s_sm_place_kernel        one thread per output vertex: the mean, the quadric, the solve, the fallback
 //   p2s_sm_faces_kernel        the surviving faces in input order, mapped
-//   p2s_sm_iota_kernel         the identity maps of a copied mesh
+//   p2s_iota_kernel            (p2s_devprim.inl) the identity maps of a copied mesh
 // Determinism: the tables hold the smallest id of a class (atomicMin), counters are integer sums, positions come from
 // exclusive scans (hipcub), and a cell's float64 sums run over keys that a radix sort put in ascending id.  One thread
 // walks a cell's list: a few entries at useful R, 10^5 at R = 2 -- slow there, and finite.
@@ -219,10 +219,6 @@ __global__ __launch_bounds__(256) void p2s_sm_faces_kernel(const int *__restrict
     for (int k = 0; k < 3; ++k) wf[3 * at + k] = vstart[wfa[3 * f + k]];
     src[at] = (int)f;
 }
-__global__ __launch_bounds__(256) void p2s_sm_iota_kernel(int *__restrict__ out, long long n) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = (int)i;
-}
 
 enum SimplifyCtr {
     SM_BOUNDARY = 0, SM_NONMANIFOLD, SM_INCONSISTENT,                                        // p2s_rp_edge_stats_kernel
@@ -329,11 +325,7 @@ extern "C" int p2s_mesh_simplify(const float *verts_dev, int64_t n_verts, const 
         p2s_set_error("%s: bad argument (%s)", who, bad);
         return P2S_EINVAL;
     }
-    if (p2s_device_count() <= device || device < 0 || device >= P2S_MAX_DEVICES) {
-        p2s_set_error("%s: no such device %d", who, device);
-        return P2S_ENODEVICE;
-    }
-    P2S_HIP_CHECK(hipSetDevice(device));
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const long long V = n_verts, F = n_faces;
     long long rep_out[16] = {};
@@ -347,13 +339,13 @@ extern "C" int p2s_mesh_simplify(const float *verts_dev, int64_t n_verts, const 
                       v_need, f_need, (long long)cap_verts, (long long)cap_faces);
         return P2S_EINVAL;
     };
-    MeshScratch pool(device);
+    PoolScratch pool(device, s);
     int rc;
 
     // ---- a. validate; the edges of the input
     const unsigned ecap = rp_table_cap(3 * F);
     const SmEdgeWs E = pool.carve([&](char *b) { return carve_sm_edges(b, ecap); });
-    if (!E.base) return mesh_oom(who, s);
+    if (!E.base) return dev_oom(who, s);
     int *ctl = E.ctl;
     unsigned long long *ctr = E.ctr, hc[8] = {};
     float box[6] = {};
@@ -362,13 +354,13 @@ extern "C" int p2s_mesh_simplify(const float *verts_dev, int64_t n_verts, const 
     }
     if (F == 0) {                                                    // the empty result
         if (vert_map_out_dev && V > 0) {
-            MESH_CHECK(who, hipMemsetAsync(vert_map_out_dev, 0xff, (size_t)V * 4, s));
-            MESH_CHECK(who, hipStreamSynchronize(s));
+            DEV_CHECK(who, hipMemsetAsync(vert_map_out_dev, 0xff, (size_t)V * 4, s));
+            DEV_CHECK(who, hipStreamSynchronize(s));
         }
         publish();
         return P2S_OK;
     }
-    MESH_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
+    DEV_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
     if ((rc = sm_edge_word(who, faces_dev, F, E.t, ctr, hc, &rep_out[13], s)) != P2S_OK) return rc;
 
     // ---- b. the grid
@@ -390,19 +382,19 @@ extern "C" int p2s_mesh_simplify(const float *verts_dev, int64_t n_verts, const 
             rep_out[12] = rep_out[13];
             publish();
             if (cap_verts < V || cap_faces < F) return too_small(V, F);
-            MESH_CHECK(who, hipMemcpyAsync(verts_out_dev, verts_dev, (size_t)V * 12, hipMemcpyDeviceToDevice, s));
-            MESH_CHECK(who, hipMemcpyAsync(faces_out_dev, faces_dev, (size_t)F * 12, hipMemcpyDeviceToDevice, s));
-            if (face_src_out_dev) hipLaunchKernelGGL(p2s_sm_iota_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, face_src_out_dev, F);
-            if (vert_map_out_dev) hipLaunchKernelGGL(p2s_sm_iota_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, vert_map_out_dev, V);
-            MESH_CHECK(who, hipGetLastError());
-            MESH_CHECK(who, hipStreamSynchronize(s));
+            DEV_CHECK(who, hipMemcpyAsync(verts_out_dev, verts_dev, (size_t)V * 12, hipMemcpyDeviceToDevice, s));
+            DEV_CHECK(who, hipMemcpyAsync(faces_out_dev, faces_dev, (size_t)F * 12, hipMemcpyDeviceToDevice, s));
+            if (face_src_out_dev) hipLaunchKernelGGL(p2s_iota_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, face_src_out_dev, F);
+            if (vert_map_out_dev) hipLaunchKernelGGL(p2s_iota_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, vert_map_out_dev, V);
+            DEV_CHECK(who, hipGetLastError());
+            DEV_CHECK(who, hipStreamSynchronize(s));
             return P2S_OK;
         }
         // surviving(R) is not monotone over grids that do not nest: this search IS the definition of R
         int lo = 1, hi = 1024;
         while (lo < hi) {
             const int mid = (lo + hi + 1) / 2;
-            MESH_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
+            DEV_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
             hipLaunchKernelGGL(p2s_sm_count_kernel, dim3(std::min(blocks(F, 256), 2048u)), dim3(256), 0, s, verts_dev, faces_dev, F, grid(mid), ctr + SM_SURVIVING);
             if ((rc = read_counters(who, ctr, hc, -1, nullptr, s)) != P2S_OK) return rc;
             ++rep_out[11];
@@ -423,13 +415,13 @@ extern "C" int p2s_mesh_simplify(const float *verts_dev, int64_t n_verts, const 
     (void)hipcub::DeviceRadixSort::SortKeys(nullptr, t4, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)(3 * F), 0, 64, nullptr);
     const size_t scan_tmp = std::max(t1, t2) + 256, sort_tmp = std::max(t3, t4) + 256;
     const SmClusterWs C = pool.carve([&](char *b) { return carve_sm_cluster(b, (size_t)V, (size_t)F, vcap, fcap, scan_tmp); });
-    if (!C.base) return mesh_oom(who, s);
-    MESH_CHECK(who, hipMemsetAsync(C.ckey, 0xff, (size_t)vcap * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(C.cmin, 0x7f, (size_t)vcap * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(C.fslot, 0xff, (size_t)fcap * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(C.used, 0, (size_t)(V + 1) * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(C.keep + F, 0, 4, s));
-    MESH_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
+    if (!C.base) return dev_oom(who, s);
+    DEV_CHECK(who, hipMemsetAsync(C.ckey, 0xff, (size_t)vcap * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(C.cmin, 0x7f, (size_t)vcap * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(C.fslot, 0xff, (size_t)fcap * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(C.used, 0, (size_t)(V + 1) * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(C.keep + F, 0, 4, s));
+    DEV_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
     hipLaunchKernelGGL(p2s_sm_cell_insert_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, verts_dev, V, g, C.ckey, vcap - 1, C.cmin, C.vslot,
                        ctr + SM_OCCUPIED);
     hipLaunchKernelGGL(p2s_sm_rep_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, V, C.vslot, C.cmin, C.rep);
@@ -439,14 +431,14 @@ extern "C" int p2s_mesh_simplify(const float *verts_dev, int64_t n_verts, const 
     hipLaunchKernelGGL(p2s_rp_face_keep_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, C.wfa, F, C.keep, C.fslot, fcap - 1, ctr + SM_DUPLICATE);
     hipLaunchKernelGGL(p2s_sm_fkeys_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, verts_dev, faces_dev, F, C.rep, C.used, C.vstart,
                        (unsigned long long *)nullptr, ctr + SM_DEGENERATE);
-    MESH_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipGetLastError());
     size_t tb = scan_tmp;
-    MESH_CHECK(who, hipcub::DeviceScan::ExclusiveSum(C.tmp, tb, C.used, C.vstart, (int)(V + 1), s));
+    DEV_CHECK(who, hipcub::DeviceScan::ExclusiveSum(C.tmp, tb, C.used, C.vstart, (int)(V + 1), s));
     tb = scan_tmp;
-    MESH_CHECK(who, hipcub::DeviceScan::ExclusiveSum(C.tmp, tb, C.keep, C.kstart, (int)(F + 1), s));
+    DEV_CHECK(who, hipcub::DeviceScan::ExclusiveSum(C.tmp, tb, C.keep, C.kstart, (int)(F + 1), s));
     int hV1 = 0, hF0 = 0;
-    MESH_CHECK(who, hipMemcpyAsync(&hV1, C.vstart + V, 4, hipMemcpyDeviceToHost, s));
-    MESH_CHECK(who, hipMemcpyAsync(&hF0, C.kstart + F, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipMemcpyAsync(&hV1, C.vstart + V, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipMemcpyAsync(&hF0, C.kstart + F, 4, hipMemcpyDeviceToHost, s));
     if ((rc = read_counters(who, ctr, hc, -1, nullptr, s)) != P2S_OK) return rc;
     const long long V1 = hV1, F0 = hF0;
     rep_out[1] = V1;
@@ -458,22 +450,22 @@ extern "C" int p2s_mesh_simplify(const float *verts_dev, int64_t n_verts, const 
 
     // ---- e. placement, f. the faces: into scratch, the report is whole before the capacity decides
     const SmPlaceWs D = pool.carve([&](char *b) { return carve_sm_place(b, (size_t)V, (size_t)F, (size_t)V1, (size_t)F0, placement == 1, sort_tmp); });
-    if (!D.base) return mesh_oom(who, s);
-    MESH_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
+    if (!D.base) return dev_oom(who, s);
+    DEV_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
     hipLaunchKernelGGL(p2s_sm_vkeys_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, V, C.rep, C.used, C.vstart, C.vmap, D.vkey);
     if (F0 > 0) {
-        MESH_CHECK(who, hipMemsetAsync(D.vseg, 0, (size_t)V1 * 8, s));
+        DEV_CHECK(who, hipMemsetAsync(D.vseg, 0, (size_t)V1 * 8, s));
         tb = sort_tmp;
         int end_bit = 33;                                            // 2^(end_bit - 32) - 1 >= V1 > every output id: SM_NO_KEY stays last
         while ((1ll << (end_bit - 32)) <= V1) ++end_bit;
-        MESH_CHECK(who, hipcub::DeviceRadixSort::SortKeys(D.tmp, tb, D.vkey, D.vsorted, (int)V, 0, end_bit, s));
+        DEV_CHECK(who, hipcub::DeviceRadixSort::SortKeys(D.tmp, tb, D.vkey, D.vsorted, (int)V, 0, end_bit, s));
         hipLaunchKernelGGL(p2s_sm_seg_kernel, dim3(blocks(V, 256)), dim3(256), 0, s, D.vsorted, V, V1, D.vseg);
         if (placement == 1) {
-            MESH_CHECK(who, hipMemsetAsync(D.fseg, 0, (size_t)V1 * 8, s));
+            DEV_CHECK(who, hipMemsetAsync(D.fseg, 0, (size_t)V1 * 8, s));
             hipLaunchKernelGGL(p2s_sm_fkeys_kernel, dim3(blocks(F, 256)), dim3(256), 0, s, verts_dev, faces_dev, F, C.rep, C.used, C.vstart, D.fkey,
                                (unsigned long long *)nullptr);       // the degenerate faces were counted above
             tb = sort_tmp;
-            MESH_CHECK(who, hipcub::DeviceRadixSort::SortKeys(D.tmp, tb, D.fkey, D.fsorted, (int)(3 * F), 0, end_bit, s));
+            DEV_CHECK(who, hipcub::DeviceRadixSort::SortKeys(D.tmp, tb, D.fkey, D.fsorted, (int)(3 * F), 0, end_bit, s));
             hipLaunchKernelGGL(p2s_sm_seg_kernel, dim3(blocks(3 * F, 256)), dim3(256), 0, s, D.fsorted, 3 * F, V1, D.fseg);
         }
         hipLaunchKernelGGL(p2s_sm_place_kernel, dim3(blocks(V1, 256)), dim3(256), 0, s, verts_dev, faces_dev, g, V1, D.vsorted, D.vseg, D.fsorted,
@@ -491,13 +483,13 @@ extern "C" int p2s_mesh_simplify(const float *verts_dev, int64_t n_verts, const 
         (void)hipStreamSynchronize(s);
         return too_small(V1, F0);
     }
-    if (V1 > 0) MESH_CHECK(who, hipMemcpyAsync(verts_out_dev, D.vout, (size_t)V1 * 12, hipMemcpyDeviceToDevice, s));
+    if (V1 > 0) DEV_CHECK(who, hipMemcpyAsync(verts_out_dev, D.vout, (size_t)V1 * 12, hipMemcpyDeviceToDevice, s));
     if (F0 > 0) {
-        MESH_CHECK(who, hipMemcpyAsync(faces_out_dev, D.wf, (size_t)F0 * 12, hipMemcpyDeviceToDevice, s));
-        if (face_src_out_dev) MESH_CHECK(who, hipMemcpyAsync(face_src_out_dev, D.src, (size_t)F0 * 4, hipMemcpyDeviceToDevice, s));
+        DEV_CHECK(who, hipMemcpyAsync(faces_out_dev, D.wf, (size_t)F0 * 12, hipMemcpyDeviceToDevice, s));
+        if (face_src_out_dev) DEV_CHECK(who, hipMemcpyAsync(face_src_out_dev, D.src, (size_t)F0 * 4, hipMemcpyDeviceToDevice, s));
     }
-    if (vert_map_out_dev) MESH_CHECK(who, hipMemcpyAsync(vert_map_out_dev, C.vmap, (size_t)V * 4, hipMemcpyDeviceToDevice, s));
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    if (vert_map_out_dev) DEV_CHECK(who, hipMemcpyAsync(vert_map_out_dev, C.vmap, (size_t)V * 4, hipMemcpyDeviceToDevice, s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipStreamSynchronize(s));
     return P2S_OK;
 }

@@ -9,7 +9,7 @@
 //   p2s_ss_partial_kernel / p2s_ss_final_kernel   the sums, the maximum and the counts of the surface samples
 //   p2s_oc_counts_kernel       |A|, |B|, |A and B| of two occupancy arrays
 // Both column kernels run twice, like the pair kernels of the check: a count pass (counters, crossings per column, the
-// undecided columns), then, behind p2s_md_scan_kernel, a fill pass that writes the crossing faces (f for sigma = +1, ~f
+// undecided columns), then, behind p2s_scan_kernel, a fill pass that writes the crossing faces (f for sigma = +1, ~f
 // for sigma = -1) into the column's own range.  The order inside a range is whatever the atomics give: the winding number
 // is a sum of integers and "undecided" an OR, so no result depends on it.  The voxel kernel runs twice too: a count pass
 // (voxels inside, singly undecided voxels), after which U is known and the capacity rule is applied BEFORE any output is
@@ -313,7 +313,7 @@ extern "C" int p2s_mesh_voxelize(p2s_trimesh_t m, int grid_res, int method, int6
     P2S_HIP_CHECK(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
     const long long R = grid_res, cols = R * R, voxels = cols * R, F = m->F;
-    MeshScratch pool(m->device);
+    PoolScratch pool(m->device, s);
     const VoxelWs w = pool.carve([&](char *b) {
         Carver c{b};
         VoxelWs r;
@@ -325,14 +325,14 @@ extern "C" int p2s_mesh_voxelize(p2s_trimesh_t m, int grid_res, int method, int6
         r.ctr = c.take<unsigned long long>(8);
         return c.done(r);
     });
-    if (!w.base) return mesh_oom(who, s);
+    if (!w.base) return dev_oom(who, s);
     std::vector<float> centre((size_t)R);
     for (long long i = 0; i < R; ++i) centre[(size_t)i] = (float)((((double)i + 0.5) / (double)R) * 2.0 - 1.0);
-    MESH_CHECK(who, hipMemcpyAsync(w.centre, centre.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
-    MESH_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
-    MESH_CHECK(who, hipMemsetAsync(w.count, 0, (size_t)cols * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(w.cursor, 0, (size_t)cols * 4, s));
-    MESH_CHECK(who, hipMemsetAsync(w.ucol, 0, (size_t)cols * 4, s));
+    DEV_CHECK(who, hipMemcpyAsync(w.centre, centre.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+    DEV_CHECK(who, hipMemsetAsync(w.ctr, 0, MESH_COUNTERS, s));
+    DEV_CHECK(who, hipMemsetAsync(w.count, 0, (size_t)cols * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(w.cursor, 0, (size_t)cols * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(w.ucol, 0, (size_t)cols * 4, s));
 
     const double S = std::max(m->scale, 1.0);
     ColumnArgs ca = {w.centre, grid_res, (S * S) * 7.105427357601002e-15, w.count, w.ucol, w.start, w.cursor, nullptr, w.ctr};      // 2^-47
@@ -351,10 +351,10 @@ extern "C" int p2s_mesh_voxelize(p2s_trimesh_t m, int grid_res, int method, int6
         p2s_set_error("p2s_mesh_voxelize: %llu crossings, more than the layout holds", hc[VX_CROSSINGS]);
         return P2S_ECAPACITY;
     }
-    hipLaunchKernelGGL(p2s_md_scan_kernel, dim3(1), dim3(1024), 0, s, w.count, cols, w.start);
+    hipLaunchKernelGGL(p2s_scan_kernel, dim3(1), dim3(1024), 0, s, w.count, cols, w.start);
     if (hc[VX_CROSSINGS] > 0) {
-        ca.list = (int *)pool.get((size_t)hc[VX_CROSSINGS] * 4);
-        if (!ca.list) return mesh_oom(who, s);
+        ca.list = pool.get<int>((size_t)hc[VX_CROSSINGS]);
+        if (!ca.list) return dev_oom(who, s);
         columns_pass();
     }
     VoxelArgs va = {m->tri, w.centre, grid_res, ((S * S) * S) * 1.1368683772161603e-13, w.start, ca.list, w.ucol,      // 2^-43
@@ -383,7 +383,7 @@ extern "C" int p2s_mesh_voxelize(p2s_trimesh_t m, int grid_res, int method, int6
             r.w = c.take<double>((size_t)U);
             return c.done(r);
         });
-        if (!fw.base) return mesh_oom(who, s);
+        if (!fw.base) return dev_oom(who, s);
     }
     va.occ = occ_out_dev;
     va.flags = flags_out_dev;
@@ -416,9 +416,9 @@ extern "C" int p2s_surface_stats(p2s_trimesh_t from, p2s_trimesh_t to, const dou
     }
     P2S_HIP_CHECK(hipSetDevice(from->device));
     hipStream_t s = (hipStream_t)stream;
-    MeshScratch pool(from->device);
-    double *part = (double *)pool.get((size_t)(SS_BLOCKS + 1) * SS_SLOTS * 8);
-    if (!part) return mesh_oom(who, s);
+    PoolScratch pool(from->device, s);
+    double *part = pool.get<double>((size_t)(SS_BLOCKS + 1) * SS_SLOTS);
+    if (!part) return dev_oom(who, s);
     SurfaceTaus taus = {};
     taus.n = n_taus;
     for (int t = 0; t < n_taus; ++t) taus.tau[t] = taus_host[t];
@@ -426,9 +426,9 @@ extern "C" int p2s_surface_stats(p2s_trimesh_t from, p2s_trimesh_t to, const dou
     hipLaunchKernelGGL(p2s_ss_partial_kernel, dim3(SS_BLOCKS), dim3(256), 0, s, dist_dev, face_from_dev, face_to_dev, (long long)n, from->fn,
                        from->F, to->fn, to->F, taus, part);
     hipLaunchKernelGGL(p2s_ss_final_kernel, dim3(1), dim3(256), 0, s, (const double *)part, out);
-    MESH_CHECK(who, hipGetLastError());
-    MESH_CHECK(who, hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, s));
-    MESH_CHECK(who, hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     for (int k = 0; k < 4; ++k) out_host[k] = h[k];
     *nc_pairs_host = (int64_t)h[4];
     for (int t = 0; t < n_taus; ++t) out_host[4 + t] = h[5 + t];
@@ -444,10 +444,10 @@ extern "C" int p2s_occupancy_counts(const uint8_t *occ_a_dev, const uint8_t *occ
     }
     P2S_HIP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
-    MeshScratch pool(device);
-    unsigned long long *ctr = (unsigned long long *)pool.get(MESH_COUNTERS), hc[8] = {};
-    if (!ctr) return mesh_oom(who, s);
-    MESH_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
+    PoolScratch pool(device, s);
+    unsigned long long *ctr = pool.get<unsigned long long>(MESH_COUNTERS / 8), hc[8] = {};
+    if (!ctr) return dev_oom(who, s);
+    DEV_CHECK(who, hipMemsetAsync(ctr, 0, MESH_COUNTERS, s));
     hipLaunchKernelGGL(p2s_oc_counts_kernel, dim3((unsigned)std::min<long long>(blocks((n + 7) / 8, 256), 4096)), dim3(256), 0, s, occ_a_dev,
                        occ_b_dev, (long long)n, ctr);
     const int rc = read_counters(who, ctr, hc, -1, nullptr, s);

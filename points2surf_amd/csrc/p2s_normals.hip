@@ -11,6 +11,7 @@
 // All float64 with contraction off: tests/normals_model.py performs the same operations for d, the only value whose bits
 // decide anything.  Scratch comes from the device's block cache and returns to it before a call ends.
 #include "p2s_internal.h"
+#include "p2s_devcall.h"
 #include <algorithm>
 #include <vector>
 
@@ -25,35 +26,6 @@ constexpr int NR_BATCH = 4;        // Boruvka rounds between two reads of the ho
 constexpr int NR_MAX_ROUNDS = 32;  // 2^rounds <= n <= 2^30, rounded up to whole batches
 // ctl: [0] non-finite normal, [2] components, [3] normals flipped, [NR_CTL_ROUND + r] hooks of round r
 constexpr int NR_CTL_ROUND = 4, NR_CTL = NR_CTL_ROUND + NR_MAX_ROUNDS + NR_BATCH;
-
-unsigned nr_blocks(long long n) { return (unsigned)std::max<long long>(1, (n + 255) / 256); }
-
-struct NrScratch {               // blocks of the device's cache held by one call
-    int device;
-    hipStream_t s;
-    std::vector<void *> held;
-    NrScratch(int d, hipStream_t st) : device(d), s(st) {}
-    NrScratch(const NrScratch &) = delete;
-    ~NrScratch() {
-        (void)hipStreamSynchronize(s);               // nothing of this call still runs on a block that returns to the cache
-        for (void *p : held) p2s_pool_free(device, p);
-    }
-    template <class T> T *get(size_t count) {
-        void *p = p2s_pool_alloc(device, std::max<size_t>(count * sizeof(T), 256));
-        if (p) held.push_back(p);
-        return (T *)p;
-    }
-};
-
-#define NR_CHECK(expr)                                                                        \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            (void)hipStreamSynchronize(s);                                                    \
-            p2s_set_error("%s: %s (%s)", who, hipGetErrorString(_e), #expr);                  \
-            return P2S_EHIP;                                                                  \
-        }                                                                                     \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // estimate: one thread per point
@@ -344,12 +316,9 @@ int nr_args(const char *who, p2s_cloud_t c, int k) {
 }
 
 // the k nearest points of every point of the cloud, [n][k], ascending (distance, id)
-int nr_neighbours(const char *who, p2s_cloud_t c, int k, NrScratch &scr, hipStream_t s, int **ids) {
+int nr_neighbours(const char *who, p2s_cloud_t c, int k, PoolScratch &scr, hipStream_t s, int **ids) {
     *ids = scr.get<int>((size_t)c->d.n * k);
-    if (!*ids) {
-        p2s_set_error("%s: out of device memory", who);
-        return P2S_ENOMEM;
-    }
+    if (!*ids) return dev_oom(who, s);
     return p2s_knn_patch(c, c->d.pts, c->d.n, k, *ids, nullptr, nullptr, s);
 }
 
@@ -365,12 +334,12 @@ extern "C" int p2s_normals_estimate(p2s_cloud_t c, int k, float *normals_out_dev
     P2S_HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     p2s_cloud_note_stream(c, s);
-    NrScratch scr(c->device, s);
+    PoolScratch scr(c->device, s);
     int *ids = nullptr;
     if (int rc = nr_neighbours(who, c, k, scr, s, &ids)) return rc;
-    hipLaunchKernelGGL(nr_pca_kernel, dim3(nr_blocks(c->d.n)), dim3(256), 0, s, c->d.pts, ids, c->d.n, k, normals_out_dev, variation_out_dev);
-    NR_CHECK(hipGetLastError());
-    NR_CHECK(hipStreamSynchronize(s));
+    hipLaunchKernelGGL(nr_pca_kernel, dim3(blocks(c->d.n)), dim3(256), 0, s, c->d.pts, ids, c->d.n, k, normals_out_dev, variation_out_dev);
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipStreamSynchronize(s));
     return P2S_OK;
 }
 
@@ -387,23 +356,20 @@ extern "C" int p2s_normals_orient(p2s_cloud_t c, int k, const float *normals_in_
     p2s_cloud_note_stream(c, s);
     const int n = c->d.n;
     const long long E = (long long)n * k;
-    NrScratch scr(c->device, s);
+    PoolScratch scr(c->device, s);
     int *link[2] = {scr.get<int>(n), scr.get<int>(n)}, *neg = scr.get<int>(n), *min_id = scr.get<int>(n), *ctl = scr.get<int>(NR_CTL);
     unsigned long long *best_w = scr.get<unsigned long long>(n), *best_e = scr.get<unsigned long long>(n), *cnt = scr.get<unsigned long long>(1);
-    if (!link[0] || !link[1] || !neg || !min_id || !ctl || !best_w || !best_e || !cnt) {
-        p2s_set_error("%s: out of device memory", who);
-        return P2S_ENOMEM;
-    }
+    if (!link[0] || !link[1] || !neg || !min_id || !ctl || !best_w || !best_e || !cnt) return dev_oom(who, s);
     int *ids = nullptr;
     if (int rc = nr_neighbours(who, c, k, scr, s, &ids)) return rc;
     int host[NR_CTL] = {};
-    NR_CHECK(hipMemsetAsync(ctl, 0, sizeof(host), s));
-    NR_CHECK(hipMemsetAsync(cnt, 0, 8, s));
-    hipLaunchKernelGGL(nr_init_kernel, dim3(nr_blocks(n)), dim3(256), 0, s, normals_in_dev, n, link[0], ctl);
-    hipLaunchKernelGGL(nr_count_edges_kernel, dim3(nr_blocks(E)), dim3(256), 0, s, ids, n, k, cnt);
-    NR_CHECK(hipGetLastError());
-    NR_CHECK(hipMemcpyAsync(host, ctl, sizeof(host), hipMemcpyDeviceToHost, s));
-    NR_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipMemsetAsync(ctl, 0, sizeof(host), s));
+    DEV_CHECK(who, hipMemsetAsync(cnt, 0, 8, s));
+    hipLaunchKernelGGL(nr_init_kernel, dim3(blocks(n)), dim3(256), 0, s, normals_in_dev, n, link[0], ctl);
+    hipLaunchKernelGGL(nr_count_edges_kernel, dim3(blocks(E)), dim3(256), 0, s, ids, n, k, cnt);
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(host, ctl, sizeof(host), hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (host[0]) {
         p2s_set_error("%s: non-finite normal", who);
         return P2S_EINVAL;
@@ -417,33 +383,33 @@ extern "C" int p2s_normals_orient(p2s_cloud_t c, int k, const float *normals_in_
             return P2S_EHIP;
         }
         for (int r = rounds; r < rounds + NR_BATCH; ++r, cur ^= 1) {
-            hipLaunchKernelGGL(nr_reset_kernel, dim3(nr_blocks(n)), dim3(256), 0, s, n, best_w, best_e);
-            hipLaunchKernelGGL(nr_min_edge_kernel<0>, dim3(nr_blocks(E)), dim3(256), 0, s, normals_in_dev, ids, n, k, link[cur], best_w, best_e);
-            hipLaunchKernelGGL(nr_min_edge_kernel<1>, dim3(nr_blocks(E)), dim3(256), 0, s, normals_in_dev, ids, n, k, link[cur], best_w, best_e);
-            hipLaunchKernelGGL(nr_hook_kernel, dim3(nr_blocks(n)), dim3(256), 0, s, normals_in_dev, n, link[cur], best_e, link[cur ^ 1],
+            hipLaunchKernelGGL(nr_reset_kernel, dim3(blocks(n)), dim3(256), 0, s, n, best_w, best_e);
+            hipLaunchKernelGGL(nr_min_edge_kernel<0>, dim3(blocks(E)), dim3(256), 0, s, normals_in_dev, ids, n, k, link[cur], best_w, best_e);
+            hipLaunchKernelGGL(nr_min_edge_kernel<1>, dim3(blocks(E)), dim3(256), 0, s, normals_in_dev, ids, n, k, link[cur], best_w, best_e);
+            hipLaunchKernelGGL(nr_hook_kernel, dim3(blocks(n)), dim3(256), 0, s, normals_in_dev, n, link[cur], best_e, link[cur ^ 1],
                                ctl + NR_CTL_ROUND + r);
-            hipLaunchKernelGGL(nr_compress_kernel, dim3(nr_blocks(n)), dim3(256), 0, s, link[cur ^ 1], n);
+            hipLaunchKernelGGL(nr_compress_kernel, dim3(blocks(n)), dim3(256), 0, s, link[cur ^ 1], n);
         }
-        NR_CHECK(hipGetLastError());
-        NR_CHECK(hipMemcpyAsync(host, ctl, sizeof(host), hipMemcpyDeviceToHost, s));
-        NR_CHECK(hipStreamSynchronize(s));
+        DEV_CHECK(who, hipGetLastError());
+        DEV_CHECK(who, hipMemcpyAsync(host, ctl, sizeof(host), hipMemcpyDeviceToHost, s));
+        DEV_CHECK(who, hipStreamSynchronize(s));
         for (int r = 0; r < NR_BATCH && open; ++r) {
             if (host[NR_CTL_ROUND + rounds]) ++rounds;
             else open = false;
         }
     }
     unsigned long long *seed = best_w;               // free again
-    NR_CHECK(hipMemsetAsync(seed, 0, (size_t)n * 8, s));
-    NR_CHECK(hipMemsetAsync(min_id, 0x7f, (size_t)n * 4, s));
-    hipLaunchKernelGGL(nr_seed_kernel, dim3(nr_blocks(n)), dim3(256), 0, s, c->d.pts, n, link[cur], seed, min_id);
-    hipLaunchKernelGGL(nr_component_kernel, dim3(nr_blocks(n)), dim3(256), 0, s, normals_in_dev, n, link[cur], seed, neg, ctl);
-    hipLaunchKernelGGL(nr_apply_kernel, dim3(nr_blocks(n)), dim3(256), 0, s, normals_in_dev, n, link[cur], neg, min_id, normals_out_dev,
+    DEV_CHECK(who, hipMemsetAsync(seed, 0, (size_t)n * 8, s));
+    DEV_CHECK(who, hipMemsetAsync(min_id, 0x7f, (size_t)n * 4, s));
+    hipLaunchKernelGGL(nr_seed_kernel, dim3(blocks(n)), dim3(256), 0, s, c->d.pts, n, link[cur], seed, min_id);
+    hipLaunchKernelGGL(nr_component_kernel, dim3(blocks(n)), dim3(256), 0, s, normals_in_dev, n, link[cur], seed, neg, ctl);
+    hipLaunchKernelGGL(nr_apply_kernel, dim3(blocks(n)), dim3(256), 0, s, normals_in_dev, n, link[cur], neg, min_id, normals_out_dev,
                        component_out_dev, ctl);
     unsigned long long edges = 0;
-    NR_CHECK(hipGetLastError());
-    NR_CHECK(hipMemcpyAsync(host, ctl, sizeof(host), hipMemcpyDeviceToHost, s));
-    NR_CHECK(hipMemcpyAsync(&edges, cnt, 8, hipMemcpyDeviceToHost, s));
-    NR_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(host, ctl, sizeof(host), hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipMemcpyAsync(&edges, cnt, 8, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (info_host) {
         for (int a = 0; a < 8; ++a) info_host[a] = 0;
         info_host[0] = host[2];

@@ -28,6 +28,7 @@
 //   ps_prolong         trilinear prolongation                      ps_iso    sum of (W chi)_p, float64 weights
 //   ps_finish          chi - iso, the border rule                  ps_vertex_map   lo + h v
 #include "p2s_internal.h"
+#include "p2s_devcall.h"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <cmath>
@@ -35,6 +36,8 @@
 #include <vector>
 
 namespace {
+
+#include "p2s_devprim.inl"          // f2o / o2f
 
 constexpr int PS_MIN_DEPTH = 3, PS_MAX_DEPTH = 9;
 constexpr int PS_TX = 8, PS_TY = 8, PS_TZ = 32;                  // stencil tile: axis 0, 1, 2 (axis 2 fastest)
@@ -72,17 +75,6 @@ __device__ __forceinline__ double ps_sum_partials(const double *__restrict__ par
     return ps_block_sum(v);
 }
 
-__device__ __forceinline__ int ps_f2o(float f) {                 // order-preserving float -> int
-    const int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-inline float ps_o2f(int o) {
-    const int i = o >= 0 ? o : o ^ 0x7fffffff;
-    float f;
-    memcpy(&f, &i, 4);
-    return f;
-}
-
 // ctl: [0..2] min, [3..5] max (ordered ints), [6] bit 0 non-finite point, bit 1 non-finite normal, [7] a normal is not zero
 __global__ __launch_bounds__(256) void ps_validate_kernel(const float *__restrict__ pts, const float *__restrict__ nrm, long long n,
                                                           int *__restrict__ ctl) {
@@ -93,8 +85,8 @@ __global__ __launch_bounds__(256) void ps_validate_kernel(const float *__restric
             const float p = pts[3 * i + a], q = nrm[3 * i + a];
             if (!(fabsf(p) <= 3.4028235e38f)) bad |= 1;
             else {
-                mn[a] = min(mn[a], ps_f2o(p));
-                mx[a] = max(mx[a], ps_f2o(p));
+                mn[a] = min(mn[a], f2o(p));
+                mx[a] = max(mx[a], f2o(p));
             }
             if (!(fabsf(q) <= 3.4028235e38f)) bad |= 2;
             else if (q != 0.0f) nz = 1;
@@ -481,42 +473,13 @@ __global__ __launch_bounds__(256) void ps_vertex_map_kernel(float *__restrict__ 
 }
 
 // ---- host side
-unsigned ps_blocks(long long n, int per = 256) { return (unsigned)std::max<long long>(1, (n + per - 1) / per); }
-
-struct PsScratch {               // blocks of the device's cache held by one call
-    int device;
-    hipStream_t s;
-    std::vector<void *> held;
-    PsScratch(int d, hipStream_t st) : device(d), s(st) {}
-    PsScratch(const PsScratch &) = delete;
-    ~PsScratch() {
-        (void)hipStreamSynchronize(s);               // nothing of this call still runs on a block that returns to the cache
-        for (void *p : held) p2s_pool_free(device, p);
-    }
-    template <class T> T *get(size_t count) {
-        void *p = p2s_pool_alloc(device, std::max<size_t>(count * sizeof(T), 256));
-        if (p) held.push_back(p);
-        return (T *)p;
-    }
-};
-
-#define PS_CHECK(expr)                                                                        \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            (void)hipStreamSynchronize(s);                                                    \
-            p2s_set_error("%s: %s (%s)", who, hipGetErrorString(_e), #expr);                  \
-            return P2S_EHIP;                                                                  \
-        }                                                                                     \
-    } while (0)
-
 struct PsSetup {                 // what the validation leaves on the host
     double centre[3], side;
 };
 
 // the arguments every entry point shares; the box of the cloud
 int ps_validate(const char *who, const float *pts, const float *nrm, int64_t n, const p2s_poisson_params_t *prm, int device,
-                hipStream_t s, PsScratch &scr, PsSetup *out) {
+                hipStream_t s, PoolScratch &scr, PsSetup *out) {
     if (!pts || !nrm || !prm || n < 1 || n > (1 << 24)) {
         p2s_set_error("%s: bad argument (n = %lld)", who, (long long)n);
         return P2S_EINVAL;
@@ -528,24 +491,21 @@ int ps_validate(const char *who, const float *pts, const float *nrm, int64_t n, 
         return P2S_EINVAL;
     }
     int *ctl = scr.get<int>(8);
-    if (!ctl) {
-        p2s_set_error("%s: out of device memory", who);
-        return P2S_ENOMEM;
-    }
+    if (!ctl) return dev_oom(who, s);
     const int init[8] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0, 0};
     int h[8];
-    PS_CHECK(hipMemcpyAsync(ctl, init, sizeof(init), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(ps_validate_kernel, dim3(std::min(ps_blocks(n), 1024u)), dim3(256), 0, s, pts, nrm, (long long)n, ctl);
-    PS_CHECK(hipGetLastError());
-    PS_CHECK(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));
-    PS_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipMemcpyAsync(ctl, init, sizeof(init), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(ps_validate_kernel, dim3(std::min(blocks(n), 1024u)), dim3(256), 0, s, pts, nrm, (long long)n, ctl);
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (h[6] || !h[7]) {
         p2s_set_error("%s: %s", who, (h[6] & 1) ? "non-finite point" : (h[6] & 2) ? "non-finite normal" : "every normal is zero");
         return P2S_EINVAL;
     }
     double ext = 0.0;
     for (int a = 0; a < 3; ++a) {
-        const double lo = (double)ps_o2f(h[a]), hi = (double)ps_o2f(h[3 + a]);
+        const double lo = (double)o2f(h[a]), hi = (double)o2f(h[3 + a]);
         out->centre[a] = (lo + hi) / 2.0;
         ext = std::max(ext, hi - lo);
     }
@@ -586,7 +546,7 @@ struct PsWork {                  // buffers sized for the finest level the call 
     PsStatus *status;
 };
 
-int ps_work_alloc(const char *who, PsScratch &scr, int n, PsWork *w) {
+int ps_work_alloc(const char *who, PoolScratch &scr, int n, PsWork *w) {
     const size_t e = (size_t)8 * n;
     size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t1, (unsigned *)nullptr, (unsigned *)nullptr, (int *)nullptr, (int *)nullptr, n, 0, 32, nullptr);
@@ -614,10 +574,8 @@ int ps_work_alloc(const char *who, PsScratch &scr, int n, PsWork *w) {
     w->part = scr.get<double>((size_t)6 * PS_MAX_PART);
     w->status = scr.get<PsStatus>(1);
     if (!w->key || !w->skey || !w->id || !w->sid || !w->ekey || !w->sekey || !w->eval || !w->sval || !w->row_node || !w->row_start ||
-        !w->row_cnt || !w->pbase || !w->pw || !w->pn || !w->u || !w->counters || !w->tmp || !w->part || !w->status) {
-        p2s_set_error("%s: out of device memory", who);
-        return P2S_ENOMEM;
-    }
+        !w->row_cnt || !w->pbase || !w->pw || !w->pn || !w->u || !w->counters || !w->tmp || !w->part || !w->status)
+        return dev_oom(who, scr.s);
     return P2S_OK;
 }
 
@@ -626,23 +584,23 @@ int ps_level_setup(const char *who, const float *pts, const float *nrm, int n, c
                    PsWork &w, hipStream_t s, PsLevel *L) {
     const PsBox bx = ps_box(su, d);
     const int e = 8 * n;
-    PS_CHECK(hipMemsetAsync(w.counters, 0, 16, s));
-    PS_CHECK(hipMemsetAsync(w.row_cnt, 0, (size_t)e * 4, s));
-    hipLaunchKernelGGL(ps_keys_kernel, dim3(ps_blocks(n)), dim3(256), 0, s, pts, n, bx, w.key, w.id);
+    DEV_CHECK(who, hipMemsetAsync(w.counters, 0, 16, s));
+    DEV_CHECK(who, hipMemsetAsync(w.row_cnt, 0, (size_t)e * 4, s));
+    hipLaunchKernelGGL(ps_keys_kernel, dim3(blocks(n)), dim3(256), 0, s, pts, n, bx, w.key, w.id);
     size_t tb = w.tmp_bytes;
-    PS_CHECK(hipcub::DeviceRadixSort::SortPairs(w.tmp, tb, w.key, w.skey, w.id, w.sid, n, 0, 3 * d, s));
-    hipLaunchKernelGGL(ps_points_kernel, dim3(ps_blocks(n)), dim3(256), 0, s, pts, nrm, n, bx, w.skey, w.sid, w.pbase, w.pw, w.pn, w.ekey,
+    DEV_CHECK(who, hipcub::DeviceRadixSort::SortPairs(w.tmp, tb, w.key, w.skey, w.id, w.sid, n, 0, 3 * d, s));
+    hipLaunchKernelGGL(ps_points_kernel, dim3(blocks(n)), dim3(256), 0, s, pts, nrm, n, bx, w.skey, w.sid, w.pbase, w.pw, w.pn, w.ekey,
                        w.eval, w.counters);
     tb = w.tmp_bytes;
-    PS_CHECK(hipcub::DeviceRadixSort::SortPairs(w.tmp, tb, w.ekey, w.sekey, w.eval, w.sval, e, 0, 3 * d + 3, s));
+    DEV_CHECK(who, hipcub::DeviceRadixSort::SortPairs(w.tmp, tb, w.ekey, w.sekey, w.eval, w.sval, e, 0, 3 * d + 3, s));
     tb = w.tmp_bytes;
-    PS_CHECK(hipcub::DeviceRunLengthEncode::Encode(w.tmp, tb, w.sekey, w.row_node, w.row_cnt, w.counters + 1, e, s));
+    DEV_CHECK(who, hipcub::DeviceRunLengthEncode::Encode(w.tmp, tb, w.sekey, w.row_node, w.row_cnt, w.counters + 1, e, s));
     tb = w.tmp_bytes;
-    PS_CHECK(hipcub::DeviceScan::ExclusiveSum(w.tmp, tb, w.row_cnt, w.row_start, e, s));
+    DEV_CHECK(who, hipcub::DeviceScan::ExclusiveSum(w.tmp, tb, w.row_cnt, w.row_start, e, s));
     int host[2] = {0, 0};
-    PS_CHECK(hipGetLastError());
-    PS_CHECK(hipMemcpyAsync(host, w.counters, 8, hipMemcpyDeviceToHost, s));
-    PS_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(host, w.counters, 8, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     L->bx = bx;
     L->n = n;
     L->n_occ = host[0];
@@ -663,45 +621,37 @@ int ps_level_setup(const char *who, const float *pts, const float *nrm, int n, c
     L->tiles_z = (bx.R + PS_TZ - 1) / PS_TZ;
     L->n_tiles = ((bx.R + PS_TX - 1) / PS_TX) * L->tiles_y * L->tiles_z;
     L->g_stencil = std::min(L->n_tiles, PS_MAX_PART);
-    L->g_screen = (int)std::min(ps_blocks(e, 256), (unsigned)PS_MAX_PART);      // 32 rows per workgroup and pass, at most 8 n rows
-    L->g_vec = (int)std::min(ps_blocks((long long)bx.R * bx.R * bx.R, 1024), (unsigned)PS_MAX_PART);
+    L->g_screen = (int)std::min(blocks(e, 256), (unsigned)PS_MAX_PART);      // 32 rows per workgroup and pass, at most 8 n rows
+    L->g_vec = (int)std::min(blocks((long long)bx.R * bx.R * bx.R, 1024), (unsigned)PS_MAX_PART);
     return P2S_OK;
 }
 
-unsigned ps_row_blocks(const PsLevel &L) { return ps_blocks((long long)8 * L.n * 8, 256); }       // 8 lanes per row, at most 8 n rows
+unsigned ps_row_blocks(const PsLevel &L) { return blocks((long long)8 * L.n * 8, 256); }       // 8 lanes per row, at most 8 n rows
 
 // b and diag(A); vx, vy, vz: three grids of scratch
 int ps_level_system(const char *who, const PsLevel &L, float *vx, float *vy, float *vz, float *b, float *diag, hipStream_t s) {
     const long long N = (long long)L.bx.R * L.bx.R * L.bx.R;
     const double h = L.bx.h;
-    PS_CHECK(hipMemsetAsync(vx, 0, (size_t)N * 4, s));
-    PS_CHECK(hipMemsetAsync(vy, 0, (size_t)N * 4, s));
-    PS_CHECK(hipMemsetAsync(vz, 0, (size_t)N * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(vx, 0, (size_t)N * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(vy, 0, (size_t)N * 4, s));
+    DEV_CHECK(who, hipMemsetAsync(vz, 0, (size_t)N * 4, s));
     hipLaunchKernelGGL(ps_splat_kernel, dim3(ps_row_blocks(L)), dim3(256), 0, s, L.n_rows, L.row_node, L.row_start, L.row_cnt, L.sval, L.pw,
                        L.pn, L.area / (h * h * h), vx, vy, vz);
-    hipLaunchKernelGGL(ps_rhs_kernel, dim3(ps_blocks(N)), dim3(256), 0, s, vx, vy, vz, L.bx.R, L.c, b);
-    hipLaunchKernelGGL(ps_diag_kernel, dim3(ps_blocks(N)), dim3(256), 0, s, L.bx.R, L.c, diag);
+    hipLaunchKernelGGL(ps_rhs_kernel, dim3(blocks(N)), dim3(256), 0, s, vx, vy, vz, L.bx.R, L.c, b);
+    hipLaunchKernelGGL(ps_diag_kernel, dim3(blocks(N)), dim3(256), 0, s, L.bx.R, L.c, diag);
     hipLaunchKernelGGL(ps_diag_screen_kernel, dim3(ps_row_blocks(L)), dim3(256), 0, s, L.n_rows, L.row_node, L.row_start, L.row_cnt, L.sval,
                        L.pw, L.lambda, diag);
-    PS_CHECK(hipGetLastError());
+    DEV_CHECK(who, hipGetLastError());
     return P2S_OK;
 }
 
 // y = A x; part_a [g_stencil], part_b [g_screen]: the shares of x . y; st: skip when the level has converged (may be NULL)
 int ps_apply(const char *who, const PsLevel &L, const PsStatus *st, const float *x, float *y, double *part_a, double *part_b, hipStream_t s) {
-    hipLaunchKernelGGL(ps_gather_kernel, dim3(ps_blocks(L.n)), dim3(256), 0, s, st, x, L.bx.R, L.n, L.pbase, L.pw, L.u);
+    hipLaunchKernelGGL(ps_gather_kernel, dim3(blocks(L.n)), dim3(256), 0, s, st, x, L.bx.R, L.n, L.pbase, L.pw, L.u);
     hipLaunchKernelGGL(ps_stencil_kernel, dim3(L.g_stencil), dim3(256), 0, s, st, x, L.bx.R, L.c, L.tiles_y, L.tiles_z, L.n_tiles, y, part_a);
     hipLaunchKernelGGL(ps_screen_kernel, dim3(L.g_screen), dim3(256), 0, s, st, L.n_rows, L.row_node, L.row_start, L.row_cnt, L.sval, L.pw,
                        L.u, L.lambda, x, y, part_b);
-    PS_CHECK(hipGetLastError());
-    return P2S_OK;
-}
-
-int ps_device(const char *who, int device) {
-    if (p2s_device_count() <= device || device < 0 || device >= P2S_MAX_DEVICES) {
-        p2s_set_error("%s: no HIP device %d", who, device);
-        return P2S_ENODEVICE;
-    }
+    DEV_CHECK(who, hipGetLastError());
     return P2S_OK;
 }
 
@@ -715,10 +665,9 @@ extern "C" int p2s_poisson_system(const float *points_dev, const float *normals_
         p2s_set_error("%s: bad argument (level %d)", who, level);
         return P2S_EINVAL;
     }
-    if (int rc = ps_device(who, device)) return rc;
-    P2S_HIP_CHECK(hipSetDevice(device));
+    if (int rc = select_device(who, device, "no HIP device")) return rc;
     hipStream_t s = (hipStream_t)stream;
-    PsScratch scr(device, s);
+    PoolScratch scr(device, s);
     PsSetup su;
     if (int rc = ps_validate(who, points_dev, normals_dev, n, params, device, s, scr, &su)) return rc;
     PsWork w;
@@ -727,16 +676,13 @@ extern "C" int p2s_poisson_system(const float *points_dev, const float *normals_
     if (int rc = ps_level_setup(who, points_dev, normals_dev, (int)n, su, params, level, w, s, &L)) return rc;
     const size_t N = (size_t)L.bx.R * L.bx.R * L.bx.R;
     float *vx = scr.get<float>(N), *vy = scr.get<float>(N), *vz = scr.get<float>(N), *b = scr.get<float>(N), *diag = scr.get<float>(N);
-    if (!vx || !vy || !vz || !b || !diag) {
-        p2s_set_error("%s: out of device memory", who);
-        return P2S_ENOMEM;
-    }
+    if (!vx || !vy || !vz || !b || !diag) return dev_oom(who, s);
     if (int rc = ps_level_system(who, L, vx, vy, vz, b, diag, s)) return rc;
-    if (b_out_dev) PS_CHECK(hipMemcpyAsync(b_out_dev, b, N * 4, hipMemcpyDeviceToDevice, s));
-    if (diag_out_dev) PS_CHECK(hipMemcpyAsync(diag_out_dev, diag, N * 4, hipMemcpyDeviceToDevice, s));
+    if (b_out_dev) DEV_CHECK(who, hipMemcpyAsync(b_out_dev, b, N * 4, hipMemcpyDeviceToDevice, s));
+    if (diag_out_dev) DEV_CHECK(who, hipMemcpyAsync(diag_out_dev, diag, N * 4, hipMemcpyDeviceToDevice, s));
     if (ax_out_dev)
         if (int rc = ps_apply(who, L, nullptr, x_in_dev, ax_out_dev, w.part, w.part + PS_MAX_PART, s)) return rc;
-    PS_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (info_host) {
         for (int k = 0; k < P2S_POISSON_INFO; ++k) info_host[k] = 0.0;
         for (int a = 0; a < 3; ++a) info_host[a] = L.bx.lo[a];
@@ -757,14 +703,13 @@ extern "C" int p2s_poisson_reconstruct(const float *points_dev, const float *nor
         p2s_set_error("%s: bad argument", who);
         return P2S_EINVAL;
     }
-    if (int rc = ps_device(who, device)) return rc;
-    P2S_HIP_CHECK(hipSetDevice(device));
+    if (int rc = select_device(who, device, "no HIP device")) return rc;
     hipStream_t s = (hipStream_t)stream;
     double info[P2S_POISSON_INFO] = {};
     int rc_mc = P2S_OK;
     PsBox fine;
     {
-        PsScratch scr(device, s);
+        PoolScratch scr(device, s);
         PsSetup su;
         if (int rc = ps_validate(who, points_dev, normals_dev, n, params, device, s, scr, &su)) return rc;
         const int D = params->depth;
@@ -776,10 +721,7 @@ extern "C" int p2s_poisson_reconstruct(const float *points_dev, const float *nor
               *p = scr.get<float>(NF), *ap = scr.get<float>(NF);
         float *vol = vol_out_dev ? vol_out_dev : nullptr;
         if (!vol) vol = scr.get<float>(NF);
-        if (!x || !xc || !b || !diag || !r || !p || !ap || !vol) {
-            p2s_set_error("%s: out of device memory", who);
-            return P2S_ENOMEM;
-        }
+        if (!x || !xc || !b || !diag || !r || !p || !ap || !vol) return dev_oom(who, s);
         DevEvent ev[2];
         if (!ev[0].create() || !ev[1].create()) {
             p2s_set_error("%s: hipEventCreate failed", who);
@@ -789,19 +731,19 @@ extern "C" int p2s_poisson_reconstruct(const float *points_dev, const float *nor
         double *part_rz[2] = {w.part + 4 * PS_MAX_PART, w.part + 5 * PS_MAX_PART};
         const double tol2 = params->cg_tol * params->cg_tol;
         for (int d = PS_MIN_DEPTH; d <= D; ++d) {
-            PS_CHECK(hipEventRecord(ev[0].get(), s));
+            DEV_CHECK(who, hipEventRecord(ev[0].get(), s));
             PsLevel L;
             if (int rc = ps_level_setup(who, points_dev, normals_dev, (int)n, su, params, d, w, s, &L)) return rc;
             const long long N = (long long)L.bx.R * L.bx.R * L.bx.R;
             if (int rc = ps_level_system(who, L, r, p, ap, b, diag, s)) return rc;          // r, p, ap: the grids of v until the CG starts
             if (d == PS_MIN_DEPTH) {
-                PS_CHECK(hipMemsetAsync(x, 0, (size_t)N * 4, s));
+                DEV_CHECK(who, hipMemsetAsync(x, 0, (size_t)N * 4, s));
             } else {
-                PS_CHECK(hipMemcpyAsync(xc, x, (size_t)((L.bx.R + 1) / 2) * ((L.bx.R + 1) / 2) * ((L.bx.R + 1) / 2) * 4, hipMemcpyDeviceToDevice, s));
-                hipLaunchKernelGGL(ps_prolong_kernel, dim3(ps_blocks(N)), dim3(256), 0, s, xc, (L.bx.R + 1) / 2, x, L.bx.R);
+                DEV_CHECK(who, hipMemcpyAsync(xc, x, (size_t)((L.bx.R + 1) / 2) * ((L.bx.R + 1) / 2) * ((L.bx.R + 1) / 2) * 4, hipMemcpyDeviceToDevice, s));
+                hipLaunchKernelGGL(ps_prolong_kernel, dim3(blocks(N)), dim3(256), 0, s, xc, (L.bx.R + 1) / 2, x, L.bx.R);
             }
             const PsStatus st0 = {0.0, 0.0, -1, 0};
-            PS_CHECK(hipMemcpyAsync(w.status, &st0, sizeof(st0), hipMemcpyHostToDevice, s));
+            DEV_CHECK(who, hipMemcpyAsync(w.status, &st0, sizeof(st0), hipMemcpyHostToDevice, s));
             if (int rc = ps_apply(who, L, nullptr, x, ap, part_pa, part_pb, s)) return rc;
             hipLaunchKernelGGL(ps_cg_init_kernel, dim3(L.g_vec), dim3(256), 0, s, b, ap, diag, N, r, p, part_rr, part_rz[0], part_bb);
             PsStatus st = st0;
@@ -816,14 +758,14 @@ extern "C" int p2s_poisson_reconstruct(const float *points_dev, const float *nor
                     hipLaunchKernelGGL(ps_cg_direction_kernel, dim3(L.g_vec), dim3(256), 0, s, w.status, it + 1, tol2, rz_old, rz_new, part_rr,
                                        part_bb, L.g_vec, r, diag, N, p);
                 }
-                PS_CHECK(hipGetLastError());
-                PS_CHECK(hipMemcpyAsync(&st, w.status, sizeof(st), hipMemcpyDeviceToHost, s));
-                PS_CHECK(hipStreamSynchronize(s));
+                DEV_CHECK(who, hipGetLastError());
+                DEV_CHECK(who, hipMemcpyAsync(&st, w.status, sizeof(st), hipMemcpyDeviceToHost, s));
+                DEV_CHECK(who, hipStreamSynchronize(s));
             }
-            PS_CHECK(hipEventRecord(ev[1].get(), s));
-            PS_CHECK(hipEventSynchronize(ev[1].get()));
+            DEV_CHECK(who, hipEventRecord(ev[1].get(), s));
+            DEV_CHECK(who, hipEventSynchronize(ev[1].get()));
             float ms = 0.0f;
-            PS_CHECK(hipEventElapsedTime(&ms, ev[0].get(), ev[1].get()));
+            DEV_CHECK(who, hipEventElapsedTime(&ms, ev[0].get(), ev[1].get()));
             double *lv = info + 8 + 5 * (d - PS_MIN_DEPTH);
             lv[0] = L.lambda;
             lv[1] = (double)L.n_occ;
@@ -832,17 +774,17 @@ extern "C" int p2s_poisson_reconstruct(const float *points_dev, const float *nor
             lv[4] = (double)ms;
         }
         // iso = the mean of chi at the points; the volume with its border rule
-        const int g_iso = (int)std::min(ps_blocks(n), (unsigned)PS_MAX_PART);
+        const int g_iso = (int)std::min(blocks(n), (unsigned)PS_MAX_PART);
         hipLaunchKernelGGL(ps_iso_kernel, dim3(g_iso), dim3(256), 0, s, points_dev, (int)n, fine, x, part_pa);
         std::vector<double> hp(g_iso);
-        PS_CHECK(hipGetLastError());
-        PS_CHECK(hipMemcpyAsync(hp.data(), part_pa, (size_t)g_iso * 8, hipMemcpyDeviceToHost, s));
-        PS_CHECK(hipStreamSynchronize(s));
+        DEV_CHECK(who, hipGetLastError());
+        DEV_CHECK(who, hipMemcpyAsync(hp.data(), part_pa, (size_t)g_iso * 8, hipMemcpyDeviceToHost, s));
+        DEV_CHECK(who, hipStreamSynchronize(s));
         double sum = 0.0;
         for (double v : hp) sum += v;
         const double iso = sum / (double)n;
-        hipLaunchKernelGGL(ps_finish_kernel, dim3(ps_blocks((long long)NF)), dim3(256), 0, s, x, fine.R, iso, vol);
-        PS_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(ps_finish_kernel, dim3(blocks((long long)NF)), dim3(256), 0, s, x, fine.R, iso, vol);
+        DEV_CHECK(who, hipGetLastError());
         for (int a = 0; a < 3; ++a) info[a] = fine.lo[a];
         info[3] = fine.h;
         info[4] = iso;
@@ -851,9 +793,9 @@ extern "C" int p2s_poisson_reconstruct(const float *points_dev, const float *nor
         // the iso-surface at 0 (inside: value > 0), array-index coordinates; holds the volume scratch of its own
         rc_mc = p2s_marching_cubes(vol, fine.R, verts_out_dev, cap_verts, faces_out_dev, cap_faces, n_verts, n_faces, 0, 1, nullptr, device, stream);
         if (rc_mc == P2S_OK && *n_verts > 0) {
-            hipLaunchKernelGGL(ps_vertex_map_kernel, dim3(ps_blocks(3 * *n_verts)), dim3(256), 0, s, verts_out_dev, (long long)(3 * *n_verts), fine);
-            PS_CHECK(hipGetLastError());
-            PS_CHECK(hipStreamSynchronize(s));
+            hipLaunchKernelGGL(ps_vertex_map_kernel, dim3(blocks(3 * *n_verts)), dim3(256), 0, s, verts_out_dev, (long long)(3 * *n_verts), fine);
+            DEV_CHECK(who, hipGetLastError());
+            DEV_CHECK(who, hipStreamSynchronize(s));
         }
     }
     return rc_mc;

@@ -2,16 +2,18 @@
 // statistical outliers (the PCL / Open3D definition over the exact kNN of p2s_knn_patch), thin to at most one point per cell of
 // an R^3 grid, normalise to the unit cube -- and the way back (restore).
 //
-//  pp_compact        the one stable compaction behind every selecting stage: flags -> per-block counts -> one-block scan ->
-//                    scatter of the surviving rows and their ids.
+//  pp_compact        the one stable compaction behind every selecting stage: flags -> per-block counts -> one-block scan
+//                    (p2s_scan_kernel of p2s_devprim.inl, in place) -> scatter of the surviving rows and their ids.
 //  rank bisection    the order statistic of rank r is the smallest ordered key K with count(key <= K) > r: built bit by bit from
 //                    the top, 32 counting passes (six thresholds at once: two bounds on three axes), no read-back in between.
 //  voxel             occupied cells live in an open-addressing hash set of linear cell ids (integer CAS); the winner of a cell is
 //                    an integer atomicMin over the float64 distance's bit pattern, then over the id: no order can change it.
 //
 // All selection logic is float64 with contraction off: tests/prepare_model.py performs the same operations in numpy.  No
-// floating-point atomics.  Scratch comes from the device's block cache and returns to it before a call ends.
+// floating-point atomics.  Scratch comes from the device's block cache and returns to it before a call ends (PoolScratch,
+// p2s_devcall.h).
 #include "p2s_internal.h"
+#include "p2s_devcall.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -21,43 +23,11 @@
 
 namespace {
 
+#include "p2s_devprim.inl"
+
 constexpr long long PP_MAX_N = 1ll << 27;
 constexpr int PP_MAX_K = 64, PP_MAX_R = 1024;
 constexpr int PP_EMPTY = -1;
-
-unsigned pp_blocks(long long n) { return (unsigned)std::max<long long>(1, (n + 255) / 256); }
-
-struct PpScratch {               // blocks of the device's cache held by one call
-    int device;
-    hipStream_t s;
-    std::vector<void *> held;
-    PpScratch(int d, hipStream_t st) : device(d), s(st) {}
-    PpScratch(const PpScratch &) = delete;
-    ~PpScratch() {
-        (void)hipStreamSynchronize(s);               // nothing of this call still runs on a block that returns to the cache
-        for (void *p : held) p2s_pool_free(device, p);
-    }
-    template <class T> T *get(size_t count) {
-        void *p = p2s_pool_alloc(device, std::max<size_t>(count * sizeof(T), 256));
-        if (p) held.push_back(p);
-        return (T *)p;
-    }
-};
-
-#define PP_CHECK(expr)                                                                        \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            (void)hipStreamSynchronize(s);                                                    \
-            p2s_set_error("%s: %s (%s)", who, hipGetErrorString(_e), #expr);                  \
-            return P2S_EHIP;                                                                  \
-        }                                                                                     \
-    } while (0)
-
-int pp_oom(const char *who) {
-    p2s_set_error("%s: out of device memory", who);
-    return P2S_ENOMEM;
-}
 
 // float32 -> unsigned key in the order of the values; -0 counts as +0
 __device__ __forceinline__ unsigned pp_key(float x) {
@@ -80,33 +50,6 @@ __global__ __launch_bounds__(256) void p2s_pp_block_count_kernel(const int *__re
     const int cnt = __syncthreads_count(i < n && flags[i] != 0);
     if (threadIdx.x == 0) blk[blockIdx.x] = cnt;
 }
-// blk [nb] counts -> exclusive prefix sums in place, blk[nb] = total; one block
-__global__ __launch_bounds__(1024) void p2s_pp_block_scan_kernel(int *blk, int nb) {
-    __shared__ int wsum[16];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    int carry = 0;
-    for (int base = 0; base < nb; base += 1024) {
-        const int i = base + t;
-        const int v = i < nb ? blk[i] : 0;
-        int x = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int j = 0; j < 16; ++j) {
-            const int q = wsum[j];
-            before += j < w ? q : 0;
-            total += q;
-        }
-        if (i < nb) blk[i] = carry + before + x - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (t == 0) blk[nb] = carry;
-}
 __global__ __launch_bounds__(256) void p2s_pp_scatter_kernel(const float *__restrict__ pts, const int *__restrict__ flags, int n,
                                                              const int *__restrict__ off, float *__restrict__ pts_out,
                                                              int *__restrict__ ids_out) {
@@ -125,35 +68,30 @@ __global__ __launch_bounds__(256) void p2s_pp_scatter_kernel(const float *__rest
     pts_out[3 * (long long)o + 2] = pts[3 * (long long)i + 2];
     ids_out[o] = i;
 }
-__global__ __launch_bounds__(256) void p2s_pp_iota_kernel(int *__restrict__ ids, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) ids[i] = i;
-}
-
 // flags [n] -> the surviving rows and ids, in input order; synchronises s
-int pp_compact(const char *who, PpScratch &scr, hipStream_t s, const float *pts, const int *flags, int n, float *pts_out, int *ids_out,
+int pp_compact(const char *who, PoolScratch &scr, hipStream_t s, const float *pts, const int *flags, int n, float *pts_out, int *ids_out,
                int64_t *m_out) {
-    const int nb = (int)pp_blocks(n);
+    const int nb = (int)blocks(n);
     int *blk = scr.get<int>((size_t)nb + 1);
-    if (!blk) return pp_oom(who);
+    if (!blk) return dev_oom(who, s);
     hipLaunchKernelGGL(p2s_pp_block_count_kernel, dim3(nb), dim3(256), 0, s, flags, n, blk);
-    hipLaunchKernelGGL(p2s_pp_block_scan_kernel, dim3(1), dim3(1024), 0, s, blk, nb);
+    hipLaunchKernelGGL(p2s_scan_kernel, dim3(1), dim3(1024), 0, s, blk, (long long)nb, blk);      // in place; blk[nb] = the total
     hipLaunchKernelGGL(p2s_pp_scatter_kernel, dim3(nb), dim3(256), 0, s, pts, flags, n, blk, pts_out, ids_out);
     int m = 0;
-    PP_CHECK(hipGetLastError());
-    PP_CHECK(hipMemcpyAsync(&m, blk + nb, 4, hipMemcpyDeviceToHost, s));
-    PP_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(&m, blk + nb, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     *m_out = m;
     return P2S_OK;
 }
 // a stage that is switched off: the input's bytes and 0 .. n - 1
 int pp_identity(const char *who, hipStream_t s, const float *pts, int n, float *pts_out, int *ids_out, int64_t *m_out) {
     if (n > 0) {
-        PP_CHECK(hipMemcpyAsync(pts_out, pts, (size_t)n * 12, hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(p2s_pp_iota_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, ids_out, n);
-        PP_CHECK(hipGetLastError());
+        DEV_CHECK(who, hipMemcpyAsync(pts_out, pts, (size_t)n * 12, hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(p2s_iota_kernel, dim3(blocks(n)), dim3(256), 0, s, ids_out, n);
+        DEV_CHECK(who, hipGetLastError());
     }
-    PP_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     *m_out = n;
     return P2S_OK;
 }
@@ -207,11 +145,11 @@ __global__ __launch_bounds__(256) void p2s_pp_finite_flag_kernel(const float *__
 // the bounding box of finite points as floats: lo[3], hi[3]; a non-finite coordinate: P2S_EINVAL.  ctl: 8 words of scratch
 int pp_box(const char *who, hipStream_t s, const float *pts, int n, unsigned *ctl, float box[6]) {
     unsigned host[8] = {~0u, ~0u, ~0u, 0u, 0u, 0u, 0u, 0u};
-    PP_CHECK(hipMemcpyAsync(ctl, host, sizeof(host), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(p2s_pp_box_kernel, dim3(std::min(pp_blocks(n), 1024u)), dim3(256), 0, s, pts, n, ctl, (int *)(ctl + 6));
-    PP_CHECK(hipGetLastError());
-    PP_CHECK(hipMemcpyAsync(host, ctl, sizeof(host), hipMemcpyDeviceToHost, s));
-    PP_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipMemcpyAsync(ctl, host, sizeof(host), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(p2s_pp_box_kernel, dim3(std::min(blocks(n), 1024u)), dim3(256), 0, s, pts, n, ctl, (int *)(ctl + 6));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(host, ctl, sizeof(host), hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (host[6]) {
         p2s_set_error("%s: non-finite point (p2s_prepare_finite drops them)", who);
         return P2S_EINVAL;
@@ -448,15 +386,6 @@ int pp_select_args(const char *who, const float *pts, int64_t n, const float *pt
     }
     return pp_count_arg(who, n);
 }
-int pp_device(const char *who, int device) {
-    if (device < 0 || device >= P2S_MAX_DEVICES || p2s_device_count() <= device) {
-        p2s_set_error("%s: no such device %d", who, device);
-        return P2S_ENODEVICE;
-    }
-    P2S_HIP_CHECK(hipSetDevice(device));
-    return P2S_OK;
-}
-
 struct PpCloud {                 // the cloud handle of one outlier call
     p2s_cloud_t c = nullptr;
     ~PpCloud() {
@@ -470,14 +399,14 @@ extern "C" int p2s_prepare_finite(const float *pts_dev, int64_t n, float *pts_ou
                                   void *stream) {
     const char *who = "p2s_prepare_finite";
     if (int rc = pp_select_args(who, pts_dev, n, pts_out_dev, ids_out_dev, n_out_host)) return rc;
-    if (int rc = pp_device(who, device)) return rc;
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     *n_out_host = 0;
     if (n == 0) return P2S_OK;
-    PpScratch scr(device, s);
+    PoolScratch scr(device, s);
     int *flags = scr.get<int>((size_t)n);
-    if (!flags) return pp_oom(who);
-    hipLaunchKernelGGL(p2s_pp_finite_flag_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, pts_dev, (int)n, flags);
+    if (!flags) return dev_oom(who, s);
+    hipLaunchKernelGGL(p2s_pp_finite_flag_kernel, dim3(blocks(n)), dim3(256), 0, s, pts_dev, (int)n, flags);
     return pp_compact(who, scr, s, pts_dev, flags, (int)n, pts_out_dev, ids_out_dev, n_out_host);
 }
 
@@ -493,19 +422,19 @@ extern "C" int p2s_prepare_crop(const float *pts_dev, int64_t n, double quantile
         p2s_set_error("%s: bad argument (margin = %g is negative or not finite)", who, margin);
         return P2S_EINVAL;
     }
-    if (int rc = pp_device(who, device)) return rc;
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     *n_out_host = 0;
     if (bounds_host) std::fill(bounds_host, bounds_host + 12, 0.0);
     if (n == 0) return P2S_OK;
-    PpScratch scr(device, s);
+    PoolScratch scr(device, s);
     unsigned *ctl = scr.get<unsigned>(64);
-    if (!ctl) return pp_oom(who);
+    if (!ctl) return dev_oom(who, s);
     float box[6];
     if (int rc = pp_box(who, s, pts_dev, (int)n, ctl, box)) return rc;
     if (quantile == 0.0) return pp_identity(who, s, pts_dev, (int)n, pts_out_dev, ids_out_dev, n_out_host);
     int *flags = scr.get<int>((size_t)n);
-    if (!flags) return pp_oom(who);
+    if (!flags) return dev_oom(who, s);
     // ctl: K [6], T [6], cnt [6], rank [6]
     const int r_lo = (int)std::floor(quantile * (double)(n - 1)), r_hi = (int)std::ceil((1.0 - quantile) * (double)(n - 1));
     unsigned host[24];
@@ -515,14 +444,14 @@ extern "C" int p2s_prepare_crop(const float *pts_dev, int64_t n, double quantile
         host[12 + j] = 0u;
         host[18 + j] = (unsigned)((j & 1) ? r_hi : r_lo);
     }
-    PP_CHECK(hipMemcpyAsync(ctl, host, sizeof(host), hipMemcpyHostToDevice, s));
+    DEV_CHECK(who, hipMemcpyAsync(ctl, host, sizeof(host), hipMemcpyHostToDevice, s));
     for (int bit = 31; bit >= 0; --bit) {
-        hipLaunchKernelGGL(p2s_pp_rank_count_kernel, dim3(std::min(pp_blocks(n), 1024u)), dim3(256), 0, s, pts_dev, (int)n, ctl + 6, (int *)(ctl + 12));
+        hipLaunchKernelGGL(p2s_pp_rank_count_kernel, dim3(std::min(blocks(n), 1024u)), dim3(256), 0, s, pts_dev, (int)n, ctl + 6, (int *)(ctl + 12));
         hipLaunchKernelGGL(p2s_pp_rank_step_kernel, dim3(1), dim3(64), 0, s, ctl, ctl + 6, (int *)(ctl + 12), (const int *)(ctl + 18), bit);
     }
-    PP_CHECK(hipGetLastError());
-    PP_CHECK(hipMemcpyAsync(host, ctl, 24, hipMemcpyDeviceToHost, s));
-    PP_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(host, ctl, 24, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     PpBox b;
     double stat[6];
     for (int a = 0; a < 3; ++a) {
@@ -541,7 +470,7 @@ extern "C" int p2s_prepare_crop(const float *pts_dev, int64_t n, double quantile
             bounds_host[9 + a] = b.hi[a];
         }
     }
-    hipLaunchKernelGGL(p2s_pp_crop_flag_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, pts_dev, (int)n, b, flags);
+    hipLaunchKernelGGL(p2s_pp_crop_flag_kernel, dim3(blocks(n)), dim3(256), 0, s, pts_dev, (int)n, b, flags);
     return pp_compact(who, scr, s, pts_dev, flags, (int)n, pts_out_dev, ids_out_dev, n_out_host);
 }
 
@@ -557,24 +486,24 @@ extern "C" int p2s_prepare_outliers(const float *pts_dev, int64_t n, int k, doub
         p2s_set_error("%s: bad argument (std_ratio = %g is negative or not finite)", who, std_ratio);
         return P2S_EINVAL;
     }
-    if (int rc = pp_device(who, device)) return rc;
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     *n_out_host = 0;
     if (info_host) std::fill(info_host, info_host + 4, 0.0);
     if (n == 0) return P2S_OK;
-    PpScratch scr(device, s);
+    PoolScratch scr(device, s);
     if (std_ratio == 0.0 || n < 2) {
         unsigned *ctl = scr.get<unsigned>(64);
-        if (!ctl) return pp_oom(who);
+        if (!ctl) return dev_oom(who, s);
         float box[6];
         if (int rc = pp_box(who, s, pts_dev, (int)n, ctl, box)) return rc;
         return pp_identity(who, s, pts_dev, (int)n, pts_out_dev, ids_out_dev, n_out_host);
     }
     k = (int)std::min<int64_t>(k, n - 1);
-    const int k1 = k + 1, nb = (int)pp_blocks(n);
+    const int k1 = k + 1, nb = (int)blocks(n);
     int *flags = scr.get<int>((size_t)n), *ids = scr.get<int>((size_t)n * k1);
     double *d = d_out_dev ? d_out_dev : scr.get<double>((size_t)n), *partial = scr.get<double>((size_t)nb + 1);
-    if (!flags || !ids || !d || !partial) return pp_oom(who);
+    if (!flags || !ids || !d || !partial) return dev_oom(who, s);
     PpCloud cloud;
     if (int rc = p2s_cloud_create(pts_dev, (int)n, device, stream, &cloud.c)) return rc;      // refuses non-finite points
     if (int rc = p2s_knn_patch(cloud.c, cloud.c->d.pts, n, k1, ids, nullptr, nullptr, stream)) return rc;
@@ -582,15 +511,15 @@ extern "C" int p2s_prepare_outliers(const float *pts_dev, int64_t n, int k, doub
     double sum = 0.0, sq = 0.0;
     hipLaunchKernelGGL(p2s_pp_sum_kernel<0>, dim3(nb), dim3(256), 0, s, d, (int)n, 0.0, partial);
     hipLaunchKernelGGL(p2s_pp_sum_final_kernel, dim3(1), dim3(256), 0, s, partial, nb, partial + nb);
-    PP_CHECK(hipGetLastError());
-    PP_CHECK(hipMemcpyAsync(&sum, partial + nb, 8, hipMemcpyDeviceToHost, s));
-    PP_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(&sum, partial + nb, 8, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     const double mean = sum / (double)n;
     hipLaunchKernelGGL(p2s_pp_sum_kernel<1>, dim3(nb), dim3(256), 0, s, d, (int)n, mean, partial);
     hipLaunchKernelGGL(p2s_pp_sum_final_kernel, dim3(1), dim3(256), 0, s, partial, nb, partial + nb);
-    PP_CHECK(hipGetLastError());
-    PP_CHECK(hipMemcpyAsync(&sq, partial + nb, 8, hipMemcpyDeviceToHost, s));
-    PP_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(&sq, partial + nb, 8, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     const double sd = std::sqrt(sq / (double)n);
     const double spread = std_ratio * sd;
     const double thr = mean + spread;
@@ -613,14 +542,14 @@ extern "C" int p2s_prepare_voxel_thin(const float *pts_dev, int64_t n, int64_t m
                       resolution == 0 ? " and no max_points >= 1 to search one for" : "");
         return P2S_EINVAL;
     }
-    if (int rc = pp_device(who, device)) return rc;
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     *n_out_host = 0;
     if (info_host) info_host[0] = info_host[1] = 0;
     if (n == 0) return P2S_OK;
-    PpScratch scr(device, s);
+    PoolScratch scr(device, s);
     unsigned *ctl = scr.get<unsigned>(64);
-    if (!ctl) return pp_oom(who);
+    if (!ctl) return dev_oom(who, s);
     float box[6];
     if (int rc = pp_box(who, s, pts_dev, (int)n, ctl, box)) return rc;
     if (resolution == 0 && n <= max_points) return pp_identity(who, s, pts_dev, (int)n, pts_out_dev, ids_out_dev, n_out_host);
@@ -640,15 +569,15 @@ extern "C" int p2s_prepare_voxel_thin(const float *pts_dev, int64_t n, int64_t m
     int *flags = scr.get<int>((size_t)n), *slot_of = scr.get<int>((size_t)n), *keys = scr.get<int>(cap), *best_id = scr.get<int>(cap);
     unsigned long long *best_d = scr.get<unsigned long long>(cap);
     int *occ_dev = (int *)(ctl + 8);
-    if (!flags || !slot_of || !keys || !best_id || !best_d) return pp_oom(who);
+    if (!flags || !slot_of || !keys || !best_id || !best_d) return dev_oom(who, s);
     int occupied = 0;
     auto insert = [&](int R, int *slots) -> int {
-        PP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)cap * 4, s));
-        PP_CHECK(hipMemsetAsync(occ_dev, 0, 4, s));
-        hipLaunchKernelGGL(p2s_pp_vox_insert_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, pts_dev, (int)n, grid(R), keys, log2_slots, slots, occ_dev);
-        PP_CHECK(hipGetLastError());
-        PP_CHECK(hipMemcpyAsync(&occupied, occ_dev, 4, hipMemcpyDeviceToHost, s));
-        PP_CHECK(hipStreamSynchronize(s));
+        DEV_CHECK(who, hipMemsetAsync(keys, 0xff, (size_t)cap * 4, s));
+        DEV_CHECK(who, hipMemsetAsync(occ_dev, 0, 4, s));
+        hipLaunchKernelGGL(p2s_pp_vox_insert_kernel, dim3(blocks(n)), dim3(256), 0, s, pts_dev, (int)n, grid(R), keys, log2_slots, slots, occ_dev);
+        DEV_CHECK(who, hipGetLastError());
+        DEV_CHECK(who, hipMemcpyAsync(&occupied, occ_dev, 4, hipMemcpyDeviceToHost, s));
+        DEV_CHECK(who, hipStreamSynchronize(s));
         return P2S_OK;
     };
     int R = resolution;
@@ -665,11 +594,11 @@ extern "C" int p2s_prepare_voxel_thin(const float *pts_dev, int64_t n, int64_t m
     }
     if (int rc = insert(R, slot_of)) return rc;
     const PpGrid g = grid(R);
-    PP_CHECK(hipMemsetAsync(best_d, 0xff, (size_t)cap * 8, s));
-    PP_CHECK(hipMemsetAsync(best_id, 0x7f, (size_t)cap * 4, s));
-    hipLaunchKernelGGL(p2s_pp_vox_min_kernel<0>, dim3(pp_blocks(n)), dim3(256), 0, s, pts_dev, (int)n, g, slot_of, best_d, best_id);
-    hipLaunchKernelGGL(p2s_pp_vox_min_kernel<1>, dim3(pp_blocks(n)), dim3(256), 0, s, pts_dev, (int)n, g, slot_of, best_d, best_id);
-    hipLaunchKernelGGL(p2s_pp_vox_flag_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, (int)n, slot_of, best_id, flags);
+    DEV_CHECK(who, hipMemsetAsync(best_d, 0xff, (size_t)cap * 8, s));
+    DEV_CHECK(who, hipMemsetAsync(best_id, 0x7f, (size_t)cap * 4, s));
+    hipLaunchKernelGGL(p2s_pp_vox_min_kernel<0>, dim3(blocks(n)), dim3(256), 0, s, pts_dev, (int)n, g, slot_of, best_d, best_id);
+    hipLaunchKernelGGL(p2s_pp_vox_min_kernel<1>, dim3(blocks(n)), dim3(256), 0, s, pts_dev, (int)n, g, slot_of, best_d, best_id);
+    hipLaunchKernelGGL(p2s_pp_vox_flag_kernel, dim3(blocks(n)), dim3(256), 0, s, (int)n, slot_of, best_id, flags);
     if (info_host) {
         info_host[0] = R;
         info_host[1] = occupied;
@@ -687,11 +616,11 @@ extern "C" int p2s_prepare_normalize(const float *pts_dev, int64_t n, float *pts
         p2s_set_error("%s: bad argument (n = %lld outside 1 .. 2^27)", who, (long long)n);
         return P2S_EINVAL;
     }
-    if (int rc = pp_device(who, device)) return rc;
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    PpScratch scr(device, s);
+    PoolScratch scr(device, s);
     unsigned *ctl = scr.get<unsigned>(64);
-    if (!ctl) return pp_oom(who);
+    if (!ctl) return dev_oom(who, s);
     float box[6];
     if (int rc = pp_box(who, s, pts_dev, (int)n, ctl, box)) return rc;
     double c[3], ext = 0.0;
@@ -705,10 +634,10 @@ extern "C" int p2s_prepare_normalize(const float *pts_dev, int64_t n, float *pts
         return P2S_EFLAT;
     }
     const double sc = 1.0 / ext;
-    hipLaunchKernelGGL(p2s_pp_normalize_kernel, dim3(pp_blocks(3 * n)), dim3(256), 0, s, pts_dev, (long long)(3 * n), c[0], c[1], c[2], sc,
+    hipLaunchKernelGGL(p2s_pp_normalize_kernel, dim3(blocks(3 * n)), dim3(256), 0, s, pts_dev, (long long)(3 * n), c[0], c[1], c[2], sc,
                        pts_out_dev);
-    PP_CHECK(hipGetLastError());
-    PP_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (info_host) {
         info_host[0] = c[0];
         info_host[1] = c[1];
@@ -731,19 +660,19 @@ extern "C" int p2s_prepare_gather(const void *src_dev, int64_t n_src, int width,
     }
     if (int rc = pp_count_arg(who, n_src)) return rc;
     if (int rc = pp_count_arg(who, n_ids)) return rc;
-    if (int rc = pp_device(who, device)) return rc;
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (n_ids == 0) return P2S_OK;
-    PpScratch scr(device, s);
+    PoolScratch scr(device, s);
     int *bad = scr.get<int>(1);
-    if (!bad) return pp_oom(who);
+    if (!bad) return dev_oom(who, s);
     int host = 0;
-    PP_CHECK(hipMemsetAsync(bad, 0, 4, s));
-    hipLaunchKernelGGL(p2s_pp_gather_kernel, dim3(pp_blocks(n_ids * width)), dim3(256), 0, s, (const unsigned *)src_dev, (long long)n_src, width,
+    DEV_CHECK(who, hipMemsetAsync(bad, 0, 4, s));
+    hipLaunchKernelGGL(p2s_pp_gather_kernel, dim3(blocks(n_ids * width)), dim3(256), 0, s, (const unsigned *)src_dev, (long long)n_src, width,
                        ids_dev, (long long)n_ids, (unsigned *)out_dev, bad);
-    PP_CHECK(hipGetLastError());
-    PP_CHECK(hipMemcpyAsync(&host, bad, 4, hipMemcpyDeviceToHost, s));
-    PP_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(&host, bad, 4, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (host) {
         p2s_set_error("%s: an id outside [0, %lld)", who, (long long)n_src);
         return P2S_EINVAL;
@@ -763,13 +692,13 @@ extern "C" int p2s_prepare_restore(const float *verts_dev, int64_t n, const doub
         return P2S_EINVAL;
     }
     if (int rc = pp_count_arg(who, n)) return rc;
-    if (int rc = pp_device(who, device)) return rc;
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) return P2S_OK;
-    hipLaunchKernelGGL(p2s_pp_restore_kernel, dim3(pp_blocks(3 * n)), dim3(256), 0, s, verts_dev, (long long)(3 * n), centre_host[0],
+    hipLaunchKernelGGL(p2s_pp_restore_kernel, dim3(blocks(3 * n)), dim3(256), 0, s, verts_dev, (long long)(3 * n), centre_host[0],
                        centre_host[1], centre_host[2], scale, out_dev);
-    PP_CHECK(hipGetLastError());
-    PP_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipStreamSynchronize(s));
     return P2S_OK;
 }
 

@@ -8,7 +8,7 @@
 //                              is tested once, by its earlier end; behind the first round two ends that already share a parent
 //                              are skipped before the distance is computed; a linked pair hooks the larger root to the smaller
 //                              (atomicMin)
-//   p2s_pp_cl_compress_kernel  parent[i] = root, between the rounds
+//   p2s_uf_compress_kernel     (p2s_devprim.inl) parent[i] = root, between the rounds
 //   p2s_pp_cl_size_kernel      points per root: the lanes of a wave that share a root count among themselves
 //   p2s_pp_cl_stats_kernel     clusters; the largest, of equal ones the smallest label (integer atomicMax over a packed word)
 //   p2s_pp_cl_flag_kernel      the keep flags for pp_compact; the clusters removed
@@ -16,7 +16,7 @@
 // (a difference, a quotient, together below 2^-32 of a cell at 2^20 cells on an axis), and with the margin two linked
 // points always lie in cells whose indices differ by at most one on every axis.  Memory is O(n).  A radius comparable to
 // the cloud's extent puts every point into a few cells: the pair tests then number O(n^2).
-// Termination: pp_cl_find walks strictly decreasing parents; a round that changes something turns at least one root into
+// Termination: uf_find walks strictly decreasing parents; a round that changes something turns at least one root into
 // a non-root for good, so the host loop ends after at most n - 1 such rounds and one that changes nothing; more than
 // n + 1 rounds is an internal error.  No thread waits for another.
 #include <hipcub/hipcub.hpp>
@@ -28,10 +28,6 @@ struct PpClGrid {
     double cell;
     int n[3];
 };
-__device__ __forceinline__ int pp_cl_find(const int *parent, int x) {
-    for (int p = parent[x]; p != x; p = parent[x]) x = p;
-    return x;
-}
 __device__ __forceinline__ unsigned long long pp_cl_key(int cx, int cy, int cz) {
     return ((unsigned long long)cx << 40) | ((unsigned long long)cy << 20) | (unsigned long long)cz;
 }
@@ -85,7 +81,7 @@ __global__ __launch_bounds__(256) void p2s_pp_cl_pair_kernel(const float *__rest
                     const double dx = px - (double)spts[3 * (long long)k], dy = py - (double)spts[3 * (long long)k + 1],
                                  dz = pz - (double)spts[3 * (long long)k + 2];
                     if (!((dx * dx + dy * dy) + dz * dz <= r2)) continue;
-                    const int ra = pp_cl_find(parent, i), rb = pp_cl_find(parent, o);
+                    const int ra = uf_find(parent, i), rb = uf_find(parent, o);
                     if (ra != rb) {
                         atomicMin(&parent[max(ra, rb)], min(ra, rb));
                         *changed = 1;
@@ -93,10 +89,6 @@ __global__ __launch_bounds__(256) void p2s_pp_cl_pair_kernel(const float *__rest
                 }
             }
     }
-}
-__global__ __launch_bounds__(256) void p2s_pp_cl_compress_kernel(int *parent, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) parent[i] = pp_cl_find(parent, i);
 }
 __global__ __launch_bounds__(256) void p2s_pp_cl_size_kernel(const int *__restrict__ parent, int n, int *size) {
     const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
@@ -156,14 +148,14 @@ extern "C" int p2s_prepare_clusters(const float *pts_dev, int64_t n, double radi
         p2s_set_error("%s: bad argument (min_points = %lld < 1)", who, (long long)min_points);
         return P2S_EINVAL;
     }
-    if (int rc = pp_device(who, device)) return rc;
+    if (int rc = select_device(who, device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     *n_out_host = 0;
     if (info_host) std::fill(info_host, info_host + 4, (int64_t)0);
     if (n == 0) return P2S_OK;
-    PpScratch scr(device, s);
+    PoolScratch scr(device, s);
     unsigned *ctl = scr.get<unsigned>(64);
-    if (!ctl) return pp_oom(who);
+    if (!ctl) return dev_oom(who, s);
     float box[6];
     if (int rc = pp_box(who, s, pts_dev, (int)n, ctl, box)) return rc;
     PpClGrid g;
@@ -188,40 +180,31 @@ extern "C" int p2s_prepare_clusters(const float *pts_dev, int64_t n, double radi
     float *spts = scr.get<float>((size_t)n * 3);
     char *tmp = scr.get<char>(tmp_bytes + 256);
     unsigned long long *ctr = (unsigned long long *)(ctl + 16);      // [0] clusters [1] the largest [2] removed
-    if (!key || !skey || !id || !sid || !parent || !size || !flags || !spts || !tmp) return pp_oom(who);
-    PP_CHECK(hipMemsetAsync(ctr, 0, 32, s));
-    PP_CHECK(hipMemsetAsync(size, 0, (size_t)n * 4, s));
-    hipLaunchKernelGGL(p2s_pp_cl_key_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, pts_dev, N, g, key, id);
-    PP_CHECK(hipGetLastError());
-    PP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, key, skey, id, sid, N, 0, 60, s));
-    hipLaunchKernelGGL(p2s_pp_cl_gather_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, pts_dev, sid, N, spts);
-    hipLaunchKernelGGL(p2s_pp_iota_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, parent, N);
+    if (!key || !skey || !id || !sid || !parent || !size || !flags || !spts || !tmp) return dev_oom(who, s);
+    DEV_CHECK(who, hipMemsetAsync(ctr, 0, 32, s));
+    DEV_CHECK(who, hipMemsetAsync(size, 0, (size_t)n * 4, s));
+    hipLaunchKernelGGL(p2s_pp_cl_key_kernel, dim3(blocks(n)), dim3(256), 0, s, pts_dev, N, g, key, id);
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, key, skey, id, sid, N, 0, 60, s));
+    hipLaunchKernelGGL(p2s_pp_cl_gather_kernel, dim3(blocks(n)), dim3(256), 0, s, pts_dev, sid, N, spts);
+    hipLaunchKernelGGL(p2s_iota_kernel, dim3(blocks(n)), dim3(256), 0, s, parent, N);
     const double r2 = radius * radius;
-    long long rounds = 0;
-    for (int changed = 1; changed; ++rounds) {
-        if (rounds > n + 1) {                                        // see the head of this file
-            (void)hipStreamSynchronize(s);
-            p2s_set_error("%s: internal error (the clusters did not converge in %lld rounds)", who, rounds);
-            return P2S_EHIP;
-        }
-        PP_CHECK(hipMemsetAsync(ctl, 0, 4, s));
-        hipLaunchKernelGGL(p2s_pp_cl_pair_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, spts, skey, sid, N, g, r2, rounds == 0, parent, (int *)ctl);
-        hipLaunchKernelGGL(p2s_pp_cl_compress_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, parent, N);
-        PP_CHECK(hipGetLastError());
-        PP_CHECK(hipMemcpyAsync(&changed, ctl, 4, hipMemcpyDeviceToHost, s));
-        PP_CHECK(hipStreamSynchronize(s));
-    }
-    hipLaunchKernelGGL(p2s_pp_cl_size_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, parent, N, size);
-    hipLaunchKernelGGL(p2s_pp_cl_stats_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, parent, size, N, ctr);
+    const int rc = until_unchanged(who, "the clusters", n + 1, (int *)ctl, s, [&](long long round) {      // the cap: see the head of this file
+        hipLaunchKernelGGL(p2s_pp_cl_pair_kernel, dim3(blocks(n)), dim3(256), 0, s, spts, skey, sid, N, g, r2, round == 0, parent, (int *)ctl);
+        hipLaunchKernelGGL(p2s_uf_compress_kernel, dim3(blocks(n)), dim3(256), 0, s, parent, N);
+    });
+    if (rc != P2S_OK) return rc;
+    hipLaunchKernelGGL(p2s_pp_cl_size_kernel, dim3(blocks(n)), dim3(256), 0, s, parent, N, size);
+    hipLaunchKernelGGL(p2s_pp_cl_stats_kernel, dim3(blocks(n)), dim3(256), 0, s, parent, size, N, ctr);
     unsigned long long hc[4] = {};
-    PP_CHECK(hipGetLastError());
-    PP_CHECK(hipMemcpyAsync(hc, ctr, 32, hipMemcpyDeviceToHost, s));
-    PP_CHECK(hipStreamSynchronize(s));
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(hc, ctr, 32, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     const long long largest = (long long)(hc[1] >> 32), least = std::min<long long>(min_points, largest);
-    hipLaunchKernelGGL(p2s_pp_cl_flag_kernel, dim3(pp_blocks(n)), dim3(256), 0, s, parent, size, N, (int)least, flags, label_out_dev, ctr);
-    PP_CHECK(hipGetLastError());
-    PP_CHECK(hipMemcpyAsync(hc, ctr, 32, hipMemcpyDeviceToHost, s));
-    PP_CHECK(hipStreamSynchronize(s));
+    hipLaunchKernelGGL(p2s_pp_cl_flag_kernel, dim3(blocks(n)), dim3(256), 0, s, parent, size, N, (int)least, flags, label_out_dev, ctr);
+    DEV_CHECK(who, hipGetLastError());
+    DEV_CHECK(who, hipMemcpyAsync(hc, ctr, 32, hipMemcpyDeviceToHost, s));
+    DEV_CHECK(who, hipStreamSynchronize(s));
     if (info_host) {
         info_host[0] = (int64_t)hc[0];
         info_host[1] = largest;

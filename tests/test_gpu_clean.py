@@ -107,7 +107,11 @@ def test_five_hole_is_left_at_four_and_filled_at_five():
 #   511 / 512 / 513    the face table (2 F passes 1024 at F = 513) and two workgroups
 #   682 / 683          6 F passes 4096
 #   1280               the closed sphere; as a soup 3840 vertices: the vertex table at 8192
-SPHERE_FACES = [170, 171, 172, 255, 256, 257, 341, 342, 511, 512, 513, 682, 683, 1280]
+#   1023 / 1024 / 1025 and 2047 / 2048 / 2049    the one-workgroup scan (p2s_scan_kernel) walks its input in chunks of 1024
+#                      with a carry: the kept faces [F] and the closed roots [F1] end one below, at and one above the first
+#                      and the second chunk; every face survives, so the positions behind the carry are all used (a sphere
+#                      cut from 5120 faces keeps its 2562 vertices: the used vertices [V] take three chunks)
+SPHERE_FACES = [170, 171, 172, 255, 256, 257, 341, 342, 511, 512, 513, 682, 683, 1280, 1023, 1024, 1025, 2047, 2048, 2049]
 
 
 @pytest.mark.parametrize('n', SPHERE_FACES)

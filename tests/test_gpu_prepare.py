@@ -32,6 +32,26 @@ def _same_bytes(a, b):
     return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
+# ---- the compaction behind every selecting stage ------------------------------------------------------------------------
+
+# pp_compact scans its per-block counts IN PLACE with the shared one-workgroup scan (p2s_scan_kernel), which walks them in chunks
+# of 1024 with a carry.  A block is 256 points: 1 / 255 / 256 / 257 are one block, its last point, and the second block;
+# 262143 / 262144 / 262145 are 1024 blocks (one chunk, exactly) and 1025 (the second chunk and its carry).
+@pytest.mark.parametrize('n', (1, 255, 256, 257, 262143, 262144, 262145))
+def test_compaction_scans_in_place_across_its_chunks(n):
+    from points2surf_amd import prepare
+    i = np.arange(n)
+    rows = np.stack([i, -i, 0.5 * i], axis=1).astype(np.float32)           # exact below 2^24: every row names its index
+    patterns = {'all': np.ones(n, bool), 'none': np.zeros(n, bool), 'every third': i % 3 == 0, 'all but every third': i % 3 != 0}
+    for name, keep in patterns.items():
+        p = rows.copy()
+        p[~keep, (i % 3)[~keep]] = np.where(i[~keep] % 2 == 0, np.nan, np.inf)       # one non-finite coordinate drops the row
+        out, ids = prepare.drop_nonfinite(p)
+        assert out.shape == (int(keep.sum()), 3) and ids.shape == (int(keep.sum()),), name       # the count that was returned
+        assert ids.dtype == torch.int32 and np.array_equal(_np(ids), np.flatnonzero(keep)), name
+        assert _same_bytes(_np(out), rows[keep]), name
+
+
 # ---- crop ---------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize('q', (0.01, 0.1, 0.49))
