@@ -659,6 +659,49 @@ int p2s_mesh_submesh(const float *verts_dev, int64_t n_verts, const int32_t *fac
                      int32_t *vert_map_out_dev, int64_t *report_host, int device, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A triangle mesh made 2-manifold: faces removed at the edges of more than two faces, vertices split where
+ * their faces do not form one fan -- the defects that p2s_mesh_repair, p2s_mesh_simplify and p2s_mesh_components count and
+ * p2s_mesh_check flags.  The project's own definition -- NOT vcglib's / MeshLab's "Repair non Manifold Edges by removing
+ * faces", "... by splitting vertices" or "Repair non Manifold Vertices by splitting", whose place in the reference's
+ * hole_filling_mesh_simp.mlx it takes.  Every result is a function of the input alone (integer atomics only): equal inputs
+ * give equal bytes.  Vertices are connected by INDEX; coordinates are never compared, and output coordinates are copied bit
+ * for bit.
+ *  a. arguments are checked before the device is touched; the message names the offending one.  An index out of range, a
+ *     non-finite vertex or a face with a repeated index: P2S_EINVAL, before anything dereferences it.  n_verts, n_faces <=
+ *     2^27.  mode is 1, 2 or 3.  n_faces = 0 is legal and gives the empty result.  Two faces with the same vertex set are
+ *     legal; each counts as a face.
+ *  b. mode & 1, remove.  Per face, from the float64 of the stored corners, with u, v, n as in rule e of p2s_mesh_components:
+ *     q = (n.x n.x + n.y n.y) + n.z n.z (contraction off).  The faces are ordered by (q descending, face id ascending).  At
+ *     every undirected edge used by more than two faces the first two of its faces in that order are the edge's keepers.  A
+ *     face is removed iff at least one of its edges has more than two faces and it is not a keeper there.  This is ONE pass,
+ *     not a greedy sequence: a face that one edge rejects may have taken a keeper's place at another edge, and that edge may
+ *     then end with one face.  Afterwards no edge has more than two faces: every edge retains at most its two keepers.
+ *  c. mode & 2, split, on the faces that b left.  The elements are the 3 F face corners (f, i).  For every undirected edge
+ *     {a, b} used by exactly two faces f and g the corner of f at a is united with the corner of g at a, and likewise at b;
+ *     edges of one face or of more than two faces unite nothing.  Every class of corners becomes one output vertex with the
+ *     coordinates of its input vertex.  Without mode & 2 all corners at one input vertex form one class.
+ *  d. output vertices are ordered by (input vertex id, smallest face id of the class); input vertices that no surviving face
+ *     references are dropped.  vert_src_out_dev [cap_verts] (may be NULL): the input vertex id.  Surviving faces keep their
+ *     input order and their winding; face_src_out_dev [cap_faces] (may be NULL): the input face id.  cap_verts = 3 n_faces
+ *     and cap_faces = n_faces always suffice.  Smaller buffers than needed: P2S_EINVAL with the report filled and nothing
+ *     else written.
+ *  e. report_host [16] int64: [0] n_verts | n_faces << 32   [1] vertices out   [2] faces out   [3] edges of more than two
+ *     faces in the input   [4] faces removed   [5] input vertices that got more than one class   [6] vertices added: [1]
+ *     minus the input vertices that the surviving faces reference   [7] input vertices dropped: n_verts minus those, so
+ *     [1] - [6] + [7] = n_verts   [8] boundary edges of the input   [9] boundary edges of the output   [10] output edges of
+ *     exactly two faces that lie on an input edge of more than two faces ("rejoined")   [11] hook rounds (a diagnostic, not
+ *     contract)   [12..15] 0.
+ *  f. after mode & 2 every edge has at most two faces and every vertex's faces form one fan under p2s_mesh_check's definition
+ *     (proof: csrc/p2s_meshmanifold.inl); after mode 1 every edge has at most two faces.  The call is idempotent: applied to
+ *     its own output it returns the same vertex and face bytes.  Two tetrahedra that share an edge come out of mode 2 as two
+ *     separate closed tetrahedra of 8 vertices.  The split leaves vertices of equal coordinates: a later weld
+ *     (p2s_mesh_repair) merges them again.
+ * Scratch comes from the device's block cache and returns to it before the call ends.  Synchronises `stream`. */
+int p2s_mesh_manifold(const float *verts_dev, int64_t n_verts, const int32_t *faces_dev, int64_t n_faces, int mode,
+                      float *verts_out_dev, int64_t cap_verts, int32_t *faces_out_dev, int64_t cap_faces,
+                      int32_t *vert_src_out_dev, int32_t *face_src_out_dev, int64_t *report_host, int device, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * "next" row: the pairs of faces of a handle's mesh that intersect, and its non-manifold vertices -- what
  * the verdict "a volume" of p2s_mesh_repair (trimesh's is_volume) does not see, and what the pseudonormal sign of
  * p2s_mesh_distance assumes absent.  The project's own definition (trimesh offers none); every result is a function of

@@ -162,6 +162,8 @@ PROTOTYPES = {
                                     c_int, c_void_p]),
     'p2s_mesh_submesh': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                  ctypes.POINTER(c_int64), c_int, c_void_p]),
+    'p2s_mesh_manifold': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                  ctypes.POINTER(c_int64), c_int, c_void_p]),
 }
 
 

@@ -39,6 +39,8 @@
 //  8. p2s_meshvoxel.inl: the occupancy of a closed mesh on the volume's grid, by a fifth walk (one column of voxels per
 //     lane), and the reductions of the reconstruction-quality report
 //  9. p2s_meshsimplify.inl: simplification by quadric vertex clustering, with the repair's face hash and the edge table
+// 10. p2s_meshcomponents.inl: connected components with their measures, the sub-mesh of a face mask
+// 11. p2s_meshmanifold.inl: faces removed at edges of more than two faces, non-manifold vertices split
 //
 // The pseudonormal sign holds for ONE closed surface that does not intersect itself.  A closed mesh of several connected
 // components may be a union of overlapping solids (the reference's 00011084 is: 170 of its 2,000 GT queries lie just outside
@@ -984,3 +986,5 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
 #include "p2s_meshsimplify.inl"
 // ---- 10. connected components with their measures; the sub-mesh of a face mask
 #include "p2s_meshcomponents.inl"
+// ---- 11. 2-manifold repair: faces removed at edges of more than two faces, non-manifold vertices split
+#include "p2s_meshmanifold.inl"
