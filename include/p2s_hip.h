@@ -702,6 +702,55 @@ int p2s_mesh_manifold(const float *verts_dev, int64_t n_verts, const int32_t *fa
                       int32_t *vert_src_out_dev, int32_t *face_src_out_dev, int64_t *report_host, int device, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The holes of a triangle mesh closed: every simple boundary loop of at most max_hole_edges edges gets the
+ * MINIMUM-AREA TRIANGULATION of its vertices (Barequet & Sharir 1995; the first stage of Liepa 2003).  No vertex is added or
+ * moved.  The project's own definition -- NOT vcglib's / MeshLab's "Close Holes" (ear cutting with its own weights), whose
+ * place in the reference's hole_filling_mesh_simp.mlx it takes, and not the fan of p2s_mesh_repair (rule e there), which
+ * stays as it is.  Every result is a function of the input alone (integer atomics only): equal inputs give equal bytes.
+ * Vertices are connected by INDEX; the call neither welds nor orients: its contract is oriented, index-connected input
+ * (p2s_mesh_repair first; p2s_mesh_manifold mode 2 where boundary vertices are not simple).
+ *  a. arguments are checked before the device is touched; the message names the offending one.  An index out of range, a
+ *     non-finite vertex or a face with a repeated index: P2S_EINVAL, before anything dereferences it.  n_verts, n_faces <=
+ *     2^27.  max_hole_edges in 0 .. 128.  n_faces = 0 is legal: the report is filled and nothing else is written.
+ *  b. loops, as in rule e of p2s_mesh_repair.  A boundary edge is an undirected edge of exactly one face, directed a -> b as
+ *     that face traverses it.  A vertex is simple if it has exactly one outgoing and one incoming boundary edge.  A loop is
+ *     a cycle v0 -> v1 -> ... -> v(n-1) -> v0 of simple vertices along these edges, written from its smallest vertex v0.
+ *     Loops of 3 <= n <= max_hole_edges edges are candidates (a loop has at least 3).  Everything else is left and counted:
+ *     longer loops, and boundaries through a vertex that is not simple -- two holes that touch, or a neighbour of the
+ *     opposite orientation, whose boundary edge runs against the others.
+ *  c. weight: float64 from the stored float32 corners p_0 .. p_(n-1) of the loop, contraction off, a correctly rounded square
+ *     root.  For positions i < k < j: A(i, k, j) = 0.5 * sqrt((n.x n.x + n.y n.y) + n.z n.z) with n = (p_k - p_i) x (p_j -
+ *     p_i), the cross product of the whole unit.  W(i, i + 1) = 0; W(i, j) = min over i < k < j of ((W(i, k) + W(k, j)) +
+ *     A(i, k, j)), a tie to the smallest k.  A chord (i, j), j - i >= 2, other than (0, n - 1), whose {v_i, v_j} is ALREADY
+ *     AN EDGE of the mesh (of any face count) is forbidden: W(i, j) = +inf -- which is what keeps the fill from making an
+ *     edge of more than two faces.  If W(0, n - 1) is infinite the hole is left and counted as blocked.
+ *  d. output: the input faces in their order, then the added faces hole by hole in ascending v0; within a hole the pre-order
+ *     of the split tree: emit(i, j) writes the face of k = the split of (i, j), then emit(i, k), then emit(k, j).  An added
+ *     face is (v_i, v_j, v_k): against the loop, so consistent with its neighbours; for n = 3 the face that the fan of
+ *     p2s_mesh_repair writes.  face_src_out_dev [cap_faces] (may be NULL): the input face id, or -1 for an added face.
+ *     Per loop in ascending v0, candidates and longer loops alike (both may be NULL): holes_out_dev [cap_holes][4] int32:
+ *     v0, n, the id of its first added face or -1, the reason (0 filled, 1 too long, 2 blocked); hole_area_out_dev
+ *     [cap_holes] float64: W(0, n - 1), or 0 where the loop is left.  Boundaries through vertices that are not simple are
+ *     no loops: they appear in report [9] only.  cap_faces = n_faces + boundary edges - 2 loops always suffices; cap_holes
+ *     counts only where one of the two per-loop outputs is given.  Smaller buffers than needed: P2S_EINVAL with the report
+ *     filled ([1] faces and [2] loops needed) and nothing else written.
+ *  e. report_host [16] int64: [0] n_verts | n_faces << 32   [1] faces out   [2] loops found   [3] holes filled   [4] faces
+ *     added   [5] loops too long   [6] loops blocked   [7] boundary edges of the input   [8] boundary edges of the output
+ *     [9] connected groups of the boundary edges of the output (edges that share a vertex are connected; "holes left" of
+ *     p2s_mesh_repair)   [10] the longest filled loop   [11] edges of more than two faces in the output, which is the
+ *     input's count   [12..15] 0.
+ *  f. no call adds an edge of more than two faces; a vertex whose faces formed one fan still has one fan; the call is
+ *     idempotent for a fixed max_hole_edges: applied to its own output it fills nothing and returns the same face bytes
+ *     (proofs: csrc/p2s_meshholes.inl).  Not covered: no vertex is added and large fills are not refined (Liepa's stages 2
+ *     and 3); no dihedral-angle weight; the fill is not tested for intersections with the rest of the mesh
+ *     (p2s_mesh_check finds such pairs afterwards); the outer boundary of an open sheet is a hole like any other if it
+ *     is short enough.
+ * Scratch comes from the device's block cache and returns to it before the call ends.  Synchronises `stream`. */
+int p2s_mesh_fill_holes(const float *verts_dev, int64_t n_verts, const int32_t *faces_dev, int64_t n_faces, int max_hole_edges,
+                        int32_t *faces_out_dev, int64_t cap_faces, int32_t *face_src_out_dev, int32_t *holes_out_dev,
+                        double *hole_area_out_dev, int64_t cap_holes, int64_t *report_host, int device, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * "next" row: the pairs of faces of a handle's mesh that intersect, and its non-manifold vertices -- what
  * the verdict "a volume" of p2s_mesh_repair (trimesh's is_volume) does not see, and what the pseudonormal sign of
  * p2s_mesh_distance assumes absent.  The project's own definition (trimesh offers none); every result is a function of

@@ -164,6 +164,8 @@ PROTOTYPES = {
                                  ctypes.POINTER(c_int64), c_int, c_void_p]),
     'p2s_mesh_manifold': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                   ctypes.POINTER(c_int64), c_int, c_void_p]),
+    'p2s_mesh_fill_holes': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                    ctypes.POINTER(c_int64), c_int, c_void_p]),
 }
 
 

@@ -41,6 +41,7 @@
 //  9. p2s_meshsimplify.inl: simplification by quadric vertex clustering, with the repair's face hash and the edge table
 // 10. p2s_meshcomponents.inl: connected components with their measures, the sub-mesh of a face mask
 // 11. p2s_meshmanifold.inl: faces removed at edges of more than two faces, non-manifold vertices split
+// 12. p2s_meshholes.inl: boundary loops closed by their minimum-area triangulation (one workgroup per loop, the table in LDS)
 //
 // The pseudonormal sign holds for ONE closed surface that does not intersect itself.  A closed mesh of several connected
 // components may be a union of overlapping solids (the reference's 00011084 is: 170 of its 2,000 GT queries lie just outside
@@ -988,3 +989,5 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
 #include "p2s_meshcomponents.inl"
 // ---- 11. 2-manifold repair: faces removed at edges of more than two faces, non-manifold vertices split
 #include "p2s_meshmanifold.inl"
+// ---- 12. holes closed by the minimum-area triangulation of their boundary loops
+#include "p2s_meshholes.inl"

@@ -233,7 +233,8 @@ __global__ __launch_bounds__(256) void p2s_rp_par_apply_kernel(const int *__rest
     if (bad && r == (int)f) atomicAdd(&ctr[1], 1ull);
 }
 
-// boundary edges (one face) as that face traverses them: outgoing / incoming count per vertex, the vertex after it
+// boundary edges (one face) as that face traverses them: outgoing / incoming count per vertex, the vertex after it.  unor
+// (faces of components that cannot be oriented) may be NULL: p2s_mesh_fill_holes has none, and blocked is not touched then
 __global__ __launch_bounds__(256) void p2s_rp_boundary_kernel(const int *__restrict__ faces, long long F, EdgeTable t,
                                                               const unsigned char *__restrict__ unor, int *outc, int *inc, int *nxt, int *blocked) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(256) void p2s_rp_boundary_kernel(const int *__restr
     atomicAdd(&outc[a], 1);
     atomicAdd(&inc[b], 1);
     nxt[a] = b;                                  // used only where outc[a] == 1: one writer
-    if (unor[f]) {
+    if (unor && unor[f]) {
         blocked[a] = 1;
         blocked[b] = 1;
     }
@@ -323,12 +324,17 @@ __global__ __launch_bounds__(256) void p2s_rp_bcount_kernel(const int *__restric
 
 // ctr[0] boundary edges, ctr[1] edges of more than two faces, ctr[2] edges of two faces that traverse them the same way
 __global__ __launch_bounds__(256) void p2s_rp_edge_stats_kernel(EdgeTable t, unsigned long long *__restrict__ ctr) {
-    const unsigned i = blockIdx.x * 256 + threadIdx.x;
-    if (i > t.mask || t.key[i] == EDGE_EMPTY) return;
-    const int c0 = t.cnt[2 * i], c1 = t.cnt[2 * i + 1];
-    if (c0 + c1 == 1) atomicAdd(&ctr[0], 1ull);
-    else if (c0 + c1 > 2) atomicAdd(&ctr[1], 1ull);
-    else if (c0 != 1) atomicAdd(&ctr[2], 1ull);
+    unsigned long long boundary = 0, overfull = 0, same_way = 0;
+    for (unsigned long long i = blockIdx.x * 256ull + threadIdx.x; i <= t.mask; i += gridDim.x * 256ull) {      // any grid
+        if (t.key[i] == EDGE_EMPTY) continue;
+        const int c0 = t.cnt[2 * i], c1 = t.cnt[2 * i + 1];
+        boundary += c0 + c1 == 1;
+        overfull += c0 + c1 > 2;
+        same_way += c0 + c1 == 2 && c0 != 1;
+    }
+    wave_count(&ctr[0], boundary);               // one atomic per wave: a mesh of many boundary edges queued on one address
+    wave_count(&ctr[1], overfull);
+    wave_count(&ctr[2], same_way);
 }
 __global__ __launch_bounds__(256) void p2s_rp_open_kernel(const int *__restrict__ faces, long long F, EdgeTable t, const int *__restrict__ parent,
                                                           int *__restrict__ open) {

@@ -5,8 +5,8 @@ the project's own definition -- not vcglib's and not MeshLab's filters.  Vertice
 compared: the split leaves vertices of equal coordinates, which a later weld (``clean.repair``) merges again.  Torch tensors
 are containers only; no CPU fallback.
 
-``python -m points2surf_amd.manifold --indir DIR --outdir DIR2 [--edges split|remove] [--max_hole_edges 30] [--dataset FILE]
-[--gpu_idx I]`` reads every mesh of ``DIR`` that mesh_formats can read (with ``--dataset``: the shapes that the list names),
+``python -m points2surf_amd.manifold --indir DIR --outdir DIR2 [--edges split|remove] [--max_hole_edges 30] [--fill fan|area]
+[--dataset FILE] [--gpu_idx I]`` reads every mesh of ``DIR`` that mesh_formats can read (with ``--dataset``: the shapes that the list names),
 writes ``DIR2/<stem>.ply`` and ``DIR2/manifold_report.csv`` with one row per mesh.  A mesh whose output is newer than its input
 keeps its file and its row.  A mesh that fails is named in the report with the reason; the run goes on.
 
@@ -16,7 +16,9 @@ sequence implies: the repair call fills holes of up to ``--max_hole_edges`` edge
 also welds equal coordinates, orients the components and flips inverted ones; a fan fill may itself create an edge of three
 faces; so it is the last call, in mode 2, that guarantees the result.  The watertight / winding_consistent / is_volume bits of
 the report are the repair's, taken BEFORE that last call.  How many faces ``remove`` costs on real reconstructions nobody has
-measured.  Nothing chooses between the two automatically.
+measured.  Nothing chooses between the two automatically.  ``--fill area`` (opt-in; ``fan`` is the default and changes nothing)
+replaces the fans: the repair call fills nothing, and BEHIND the last call ``holes.fill`` closes loops of up to ``--max_hole_edges``
+edges (0 .. 128) by their minimum-area triangulation, which never adds an edge of more than two faces.
 """
 import argparse
 import csv
@@ -36,6 +38,7 @@ from .simplify import _device, _names
 
 P2S_EINVAL = -1
 EDGES = ('split', 'remove')
+FILLS = ('fan', 'area')
 REPORT_KEYS = ('verts_in', 'faces_in', 'verts_out', 'faces_out', 'nonmanifold_edges_in', 'faces_removed', 'vertices_split', 'vertices_added',
                'vertices_dropped', 'boundary_edges_in', 'boundary_edges_out', 'rejoined_edges', 'hook_rounds')
 REPORT_FILE = 'manifold_report.csv'
@@ -110,13 +113,33 @@ def manifold(verts, faces, edges='split', split=True, device=None, want_map=Fals
     return vo[:r['verts_out']], fo[:r['faces_out']], r
 
 
-def remove_fill_split(verts, faces, max_hole_edges=30, device=None):
+def _fill(fill, max_hole_edges):
+    if fill not in FILLS:
+        raise ValueError('fill must be one of %s (got %r)' % (', '.join(FILLS), fill))
+    most = 64 if fill == 'fan' else 128
+    if not 0 <= int(max_hole_edges) <= most:
+        raise ValueError('max_hole_edges must lie in 0 .. %d (got %r)' % (most, max_hole_edges))
+
+
+def remove_fill_split(verts, faces, max_hole_edges=30, device=None, fill='fan'):
     """the reference script's sequence (see the head of this file): mode 1, ``clean.repair(max_hole_edges)``, mode 2 ->
     (verts, faces, report): the report of the last call with 'verts_in', 'faces_in', 'nonmanifold_edges_in', 'faces_removed' and
-    'boundary_edges_in' of the first, and 'repair': the report of the repair call"""
+    'boundary_edges_in' of the first, and 'repair': the report of the repair call.  ``fill='area'``: the repair fills nothing
+    (``max_hole_edges=0``: weld, orient, flip), and behind mode 2 ``holes.fill(max_hole_edges)`` (0 .. 128) closes the loops by
+    their minimum-area triangulation, which adds no edge of more than two faces; the report then holds 'fill', the report of
+    that call, and its 'faces_out' and 'boundary_edges_out'"""
     from . import clean
-    if not 0 <= int(max_hole_edges) <= 64:
-        raise ValueError('max_hole_edges must lie in 0 .. 64 (got %r)' % (max_hole_edges,))
+    _fill(fill, max_hole_edges)
+    if fill == 'area':
+        from . import holes
+        v1, f1, first = manifold(verts, faces, edges='remove', split=False, device=device)
+        v2, f2, _, mid = clean.repair(v1, f1, max_hole_edges=0, device=device)
+        v3, f3, last = manifold(v2, f2, edges='split', device=device)
+        v4, f4, filled = holes.fill(v3, f3, max_hole_edges=int(max_hole_edges), device=device)
+        for k in ('verts_in', 'faces_in', 'nonmanifold_edges_in', 'faces_removed', 'boundary_edges_in'):
+            last[k] = first[k]
+        last.update(repair=mid, fill=filled, faces_out=filled['faces_out'], boundary_edges_out=filled['boundary_edges_out'])
+        return v4, f4, last
     v1, f1, first = manifold(verts, faces, edges='remove', split=False, device=device)
     v2, f2, _, mid = clean.repair(v1, f1, max_hole_edges=int(max_hole_edges), device=device)
     v3, f3, last = manifold(v2, f2, edges='split', device=device)
@@ -126,14 +149,14 @@ def remove_fill_split(verts, faces, max_hole_edges=30, device=None):
     return v3, f3, last
 
 
-def manifold_file(file_in, file_out, edges='split', max_hole_edges=30, device=None):
+def manifold_file(file_in, file_out, edges='split', max_hole_edges=30, device=None, fill='fan'):
     """``file_in`` (any type of mesh_formats) made 2-manifold into the PLY ``file_out``; the report of ``manifold`` (split) or of
-    ``remove_fill_split`` (remove)"""
+    ``remove_fill_split`` (remove, with ``fill``)"""
     _mode(edges, True)
     v, f = _formats.read_mesh(file_in)
     v, f = np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(f).astype(np.int32).reshape(-1, 3)
     if edges == 'remove':
-        vo, fo, rep = remove_fill_split(v, f, max_hole_edges=max_hole_edges, device=device)
+        vo, fo, rep = remove_fill_split(v, f, max_hole_edges=max_hole_edges, device=device, fill=fill)
     else:
         vo, fo, rep = manifold(v, f, device=device)
     os.makedirs(os.path.dirname(os.path.abspath(file_out)), exist_ok=True)
@@ -146,14 +169,21 @@ def _row(name, edges, rep):
     row.update({k: rep[k] for k in REPORT_COLUMNS if k in rep})
     if 'repair' in rep:
         row.update({k: rep['repair'][k] for k in ('holes_filled', 'faces_added', 'watertight', 'winding_consistent', 'is_volume')})
+    if 'fill' in rep:                                   # fill='area': the holes were closed behind the repair, by holes.fill
+        row.update({k: rep['fill'][k] for k in ('holes_filled', 'faces_added')})
     row.update(mesh=name, edges=edges, verdict='closed' if rep['boundary_edges_out'] == 0 else 'open')      # 2-manifold either way
     return row
 
 
-def manifold_dir(indir, outdir, edges='split', max_hole_edges=30, dataset=None, device=None):
+def manifold_dir(indir, outdir, edges='split', max_hole_edges=30, dataset=None, device=None, fill='fan'):
     """every mesh of ``indir`` as ``outdir/<stem>.ply`` and ``outdir/manifold_report.csv``; a mesh whose output is newer than its
-    input keeps its file and its row of the earlier report.  Returns the files written by this run."""
+    input keeps its file and its row of the earlier report.  Returns the files written by this run.  ``fill='area'`` with
+    ``edges='remove'`` is named 'remove+area' in the report's column 'edges'."""
     _mode(edges, True)
+    if edges == 'remove':
+        _fill(fill, max_hole_edges)
+        if fill == 'area':
+            edges = 'remove+area'
     os.makedirs(outdir, exist_ok=True)
     report_path = os.path.join(outdir, REPORT_FILE)
     old = {}
@@ -169,7 +199,8 @@ def manifold_dir(indir, outdir, edges='split', max_hole_edges=30, dataset=None, 
             rows.append(prev)
             continue
         try:
-            rows.append(_row(name, edges, manifold_file(f_in, f_out, edges=edges, max_hole_edges=max_hole_edges, device=device)))
+            rows.append(_row(name, edges, manifold_file(f_in, f_out, edges=edges.split('+')[0], max_hole_edges=max_hole_edges, device=device,
+                                                        fill=fill)))
             written.append(f_out)
         except Exception as e:                          # named in the report; the run goes on
             if os.path.isfile(f_out):
@@ -192,14 +223,20 @@ def main(argv=None):
     ap.add_argument('--edges', choices=EDGES, default='split',
                     help='split: vertices are split, no face is lost.  remove: the reference script\'s sequence -- faces removed at edges of more '
                          'than two faces, holes filled, vertices split; how many faces it costs on real reconstructions is unmeasured')
-    ap.add_argument('--max_hole_edges', type=int, default=30, help='with --edges remove: fill holes of up to this many edges (0 .. 64)')
+    ap.add_argument('--max_hole_edges', type=int, default=30,
+                    help='with --edges remove: fill holes of up to this many edges (0 .. 64; with --fill area 0 .. 128)')
+    ap.add_argument('--fill', choices=FILLS, default='fan',
+                    help='with --edges remove: fan is the fan of clean.repair; area closes the loops behind the split by their minimum-area '
+                         'triangulation (points2surf_amd.holes), which adds no edge of more than two faces')
     ap.add_argument('--dataset', default=None, help='a list of shape names: only these meshes')
     ap.add_argument('--gpu_idx', type=int, default=0)
     opt = ap.parse_args(argv)
-    if not 0 <= opt.max_hole_edges <= 64:
-        ap.error('--max_hole_edges must lie in 0 .. 64')
+    most = 128 if opt.edges == 'remove' and opt.fill == 'area' else 64
+    if not 0 <= opt.max_hole_edges <= most:
+        ap.error('--max_hole_edges must lie in 0 .. %d' % most)
     device = _engine.select_device(opt.gpu_idx)
-    for f in manifold_dir(opt.indir, opt.outdir, edges=opt.edges, max_hole_edges=opt.max_hole_edges, dataset=opt.dataset, device=device):
+    for f in manifold_dir(opt.indir, opt.outdir, edges=opt.edges, max_hole_edges=opt.max_hole_edges, dataset=opt.dataset, device=device,
+                          fill=opt.fill):
         print(f)
     print(os.path.join(opt.outdir, REPORT_FILE))
     return 0
