@@ -751,6 +751,54 @@ int p2s_mesh_fill_holes(const float *verts_dev, int64_t n_verts, const int32_t *
                         double *hole_area_out_dev, int64_t cap_holes, int64_t *report_host, int device, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The vertices of a triangle mesh smoothed: `iterations` rounds of the umbrella operator with uniform
+ * weights, a half-step with lambda and, if mu != 0, a half-step with mu (Taubin 1995, "lambda | mu"; MeshLab's "Taubin
+ * Smooth" has the same defaults 0.5 and -0.53).  mu = 0 is plain Laplacian smoothing.  Faces are not touched; no vertex is
+ * added, removed or renumbered.  The project's own definition, not vcglib's.  Every result is a function of the input alone
+ * (integer atomics only, float64 sums in one stated order): equal inputs give equal bytes.  Vertices are connected by INDEX:
+ * nothing is welded (p2s_mesh_repair first).  Called by nothing else in the library: opt-in.
+ *  a. arguments are checked before the device is touched; the message names the offending one.  An index out of range, a
+ *     non-finite vertex or a face with a repeated index: P2S_EINVAL, before anything dereferences it, and nothing is written.
+ *     n_verts, n_faces <= 2^27.  iterations in 0 .. 10000.  lambda finite, 0 < lambda <= 1.  mu finite, -2 <= mu <= 0.
+ *     boundary_mode in 0 .. 2.  verts_out_dev [n_verts][3] is not NULL when n_verts > 0 and must not overlap verts_dev: the
+ *     update is simultaneous and does not run in place.  fixed_dev [n_verts] uint8 and class_out_dev [n_verts] uint8 may be
+ *     NULL.  n_faces = 0 or iterations = 0 is legal: the output is the input's bytes, the report and the classes are filled.
+ *  b. neighbours: N(i) of a vertex i are the other ends of the undirected edges of the face list at i, each once however
+ *     many faces have the edge, taken in ASCENDING vertex index.
+ *  c. classes, one byte per vertex in class_out_dev; the first that applies:
+ *       4 masked: fixed_dev[i] != 0
+ *       5 unreferenced: no edge
+ *       3 on an edge of more than two faces (modes 0 and 1): fixed
+ *       2 boundary, fixed: on an edge of exactly one face, and either mode 0, or mode 1 with a number of such edges at i
+ *         other than two
+ *       1 boundary, on the curve: mode 1 and exactly two edges of exactly one face at i; its N(i) is the two other ends of
+ *         those edges only (ascending), so a boundary curve is smoothed as a curve
+ *       0 free: all of N(i)
+ *     In mode 2 every referenced, unmasked vertex is class 0.  Classes 2 .. 5 are fixed: the vertex keeps its input bytes,
+ *     the sign of a zero included; its neighbours still read it.
+ *  d. one half-step with weight w: every vertex of class 0 or 1, with N(i) = j1 < j2 < .. < jd, reads the float32 positions
+ *     of the previous half-step and writes, per coordinate, in float64 with contraction off:
+ *         s = p_j1 (converted to float64);  s = s + p_jk for k = 2 .. d;  m = s / (double) d;
+ *         p' = (float) (p_i + w * (m - p_i)),  the conversion rounded to nearest even, subnormal results kept.
+ *     An iteration is a half-step with lambda, then, if mu != 0, one with mu.  Positions are float32 between half-steps.
+ *     There is no limit on d.  If an output coordinate is not finite the call fails with P2S_EINVAL ("the result is not
+ *     finite"): the report is filled, nothing else is written.
+ *  e. report_host [16] int64: [0] n_verts | n_faces << 32   [1] .. [6] the vertices of the classes 0 .. 5   [7] undirected
+ *     edges   [8] the largest |N(i)| used (over the classes 0 and 1; 0 if there is none)   [9] half-steps run: iterations,
+ *     twice that if mu != 0, and 0 if no vertex is of class 0 or 1   [10] the bits of the float64 maximum over the vertices
+ *     of (dx dx + dy dy) + dz dz between input and output, in float64 from the stored float32 values (where [11] > 0: over
+ *     the vertices whose output is finite)   [11] non-finite output coordinates   [12..15] 0.
+ *  f. the result is a function of the vertex array and of the SET of undirected edges with their face counts: reordering
+ *     the faces, rotating or flipping their corners changes no output byte.  Renumbering the vertices may change the last
+ *     bit, since the summation follows the index.  Not covered: cotangent or any other weight that depends on the geometry;
+ *     a feature-preserving filter; a test of the smoothed mesh for self-intersections (p2s_mesh_check finds them
+ *     afterwards).  With mu = 0 a closed mesh shrinks; lambda | mu shrinks far less and is no exact volume preservation.
+ * Scratch comes from the device's block cache and returns to it before the call ends.  Synchronises `stream`. */
+int p2s_mesh_smooth(const float *verts_dev, int64_t n_verts, const int32_t *faces_dev, int64_t n_faces, int iterations, double lambda,
+                    double mu, int boundary_mode, const uint8_t *fixed_dev, float *verts_out_dev, uint8_t *class_out_dev,
+                    int64_t *report_host, int device, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * "next" row: the pairs of faces of a handle's mesh that intersect, and its non-manifold vertices -- what
  * the verdict "a volume" of p2s_mesh_repair (trimesh's is_volume) does not see, and what the pseudonormal sign of
  * p2s_mesh_distance assumes absent.  The project's own definition (trimesh offers none); every result is a function of

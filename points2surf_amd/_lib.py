@@ -166,6 +166,8 @@ PROTOTYPES = {
                                   ctypes.POINTER(c_int64), c_int, c_void_p]),
     'p2s_mesh_fill_holes': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                     ctypes.POINTER(c_int64), c_int, c_void_p]),
+    'p2s_mesh_smooth': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p,
+                                c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p]),
 }
 
 

@@ -991,3 +991,5 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
 #include "p2s_meshmanifold.inl"
 // ---- 12. holes closed by the minimum-area triangulation of their boundary loops
 #include "p2s_meshholes.inl"
+// ---- 13. vertices moved by the umbrella operator: Taubin and Laplacian smoothing
+#include "p2s_meshsmooth.inl"
