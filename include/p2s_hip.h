@@ -791,12 +791,73 @@ int p2s_mesh_fill_holes(const float *verts_dev, int64_t n_verts, const int32_t *
  *  f. the result is a function of the vertex array and of the SET of undirected edges with their face counts: reordering
  *     the faces, rotating or flipping their corners changes no output byte.  Renumbering the vertices may change the last
  *     bit, since the summation follows the index.  Not covered: cotangent or any other weight that depends on the geometry;
- *     a feature-preserving filter; a test of the smoothed mesh for self-intersections (p2s_mesh_check finds them
- *     afterwards).  With mu = 0 a closed mesh shrinks; lambda | mu shrinks far less and is no exact volume preservation.
+ *     a test of the smoothed mesh for self-intersections (p2s_mesh_check finds them afterwards).  This filter rounds every
+ *     crease; the feature-preserving one is p2s_mesh_denoise below.
+ *     With mu = 0 a closed mesh shrinks; lambda | mu shrinks far less and is no exact volume preservation.
  * Scratch comes from the device's block cache and returns to it before the call ends.  Synchronises `stream`. */
 int p2s_mesh_smooth(const float *verts_dev, int64_t n_verts, const int32_t *faces_dev, int64_t n_faces, int iterations, double lambda,
                     double mu, int boundary_mode, const uint8_t *fixed_dev, float *verts_out_dev, uint8_t *class_out_dev,
                     int64_t *report_host, int device, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A triangle mesh denoised with its sharp edges kept: the face normals are filtered first, then the
+ * vertices are moved toward the filtered normals (Sun, Rosin, Martin and Langbein, "Fast and effective feature-preserving
+ * mesh denoising", TVCG 2007; the weight max(0, ni . nj - T)^2 needs +, -, *, / and sqrt only, which are correctly rounded,
+ * where a Gaussian bilateral weight needs an exp).  Faces are not touched; no vertex is added, removed or renumbered.  The
+ * project's own definition.  Every result is a function of the input alone (integer atomics only, float64 sums in one stated
+ * order): equal inputs give equal bytes.  Called by nothing else in the library: opt-in.
+ *  a. arguments are checked before the device is touched; the message names the offending one.  An index out of range, a
+ *     non-finite vertex or a face with a repeated index: P2S_EINVAL, before anything dereferences it, and nothing is written.
+ *     n_verts, n_faces <= 2^27.  threshold (T) finite, 0 <= T < 1.  normal_iterations and vertex_iterations in 0 .. 10000.
+ *     boundary_mode 0 (boundary vertices fixed) or 1 (free).  verts_out_dev [n_verts][3] is not NULL when n_verts > 0 and
+ *     must not overlap verts_dev: the update is simultaneous and does not run in place.  fixed_dev [n_verts] uint8,
+ *     normals_out_dev [n_faces][3] float and class_out_dev [n_verts] uint8 may be NULL.  n_faces = 0 or both counts 0 is
+ *     legal: the output is the input's bytes, and the report, the classes and the normals are filled.
+ *  b. the geometric normal of a face (a, b, c), in float64 from the float32 positions with contraction off:
+ *         e1 = b - a, e2 = c - a per coordinate;  m = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), every
+ *         product rounded, then the difference;  l = sqrt((mx mx + my my) + mz mz);  n = (float) (m / l) per coordinate.
+ *     If l is 0 or not finite the normal is (0, 0, 0) and the face is DEAD: it contributes nothing anywhere and keeps its
+ *     zero normal.  Every other face is live.
+ *  c. neighbours: N(i) of a face i are the faces, dead ones and i itself included, that share at least one vertex INDEX
+ *     with i, each once however many vertices it shares, taken in ASCENDING face index.
+ *  d. one normal iteration: every live face i reads the float32 normals of the previous iteration (the update is
+ *     simultaneous) and computes in float64, s = (0, 0, 0) at first, for j in N(i) in order:
+ *         d = (nix njx + niy njy) + niz njz;  if d > T:  w = (d - T) (d - T);  s = s + w nj per coordinate (a rounded
+ *         product, then a rounded sum);
+ *     then l = sqrt((sx sx + sy sy) + sz sz) and n' = (float) (s / l); if l is 0 or not finite the face keeps its normal.
+ *     d = T contributes nothing, and a dead neighbour has d = 0 <= T.  Normals are float32 between iterations.  After
+ *     normal_iterations rounds they are the TARGET normals, which normals_out_dev receives (with 0 rounds: the geometric
+ *     ones).
+ *  e. classes, one byte per vertex in class_out_dev; the first that applies:
+ *       2 masked: fixed_dev[i] != 0
+ *       3 unreferenced: in no face
+ *       4 no live face at the vertex
+ *       1 boundary, fixed: mode 0 and the vertex lies on an edge of exactly one face (dead faces count as faces here)
+ *       0 free
+ *     Classes 1 .. 4 keep their input bytes, the sign of a zero included; the faces around them still read them.
+ *  f. one vertex iteration: every vertex p of class 0, with the live faces f1 < f2 < .. < fk that hold it, reads the
+ *     float32 positions of the previous iteration (the update is simultaneous) and computes in float64, s = (0, 0, 0) at
+ *     first, per face with the corners (a, b, c) as stored and the target normal n:
+ *         g = ((a + b) + c) / 3.0 per coordinate;  d = (nx (gx - px) + ny (gy - py)) + nz (gz - pz);  s = s + n d per
+ *         coordinate;
+ *     then p' = (float) (p + s / (double) k), rounded to nearest even, subnormal results kept.  If an output coordinate is not
+ *     finite the call fails with P2S_EINVAL ("the result is not finite"): the report is filled, nothing else is written.
+ *  g. report_host [16] int64: [0] n_verts | n_faces << 32   [1] .. [5] the vertices of the classes 0 .. 4   [6] dead faces
+ *     [7] the largest |N(i)| over the live faces (0 if there is none)   [8] normal iterations run: normal_iterations, and
+ *     0 if no face is live   [9] vertex iterations run: vertex_iterations, and 0 if no vertex is of class 0   [10] the
+ *     bits of the float64 maximum over the vertices of (dx dx + dy dy) + dz dz between input and output, as for
+ *     p2s_mesh_smooth (0 if [9] is 0)   [11] non-finite output coordinates   [12..15] 0.
+ *  h. the result depends on the arrays as given: the sums follow the face index and a centroid the stored corner order, so
+ *     renumbering faces or vertices, or rotating a face's corners, may change the last bit.  Flipping a face flips its
+ *     normal, and faces of opposite orientation do not see each other (d < 0 <= T): orient the mesh first
+ *     (p2s_mesh_repair).  Faces are connected by vertex INDEX: nothing is welded.  Limits: the face weights are uniform (no
+ *     area weight); T is the caller's, nothing chooses it; a fan of d faces at one vertex costs O(d^2) per normal
+ *     iteration (9 M neighbour visits at d = 3,000); the result is not tested for self-intersections (p2s_mesh_check finds
+ *     them afterwards).
+ * Scratch comes from the device's block cache and returns to it before the call ends.  Synchronises `stream`. */
+int p2s_mesh_denoise(const float *verts_dev, int64_t n_verts, const int32_t *faces_dev, int64_t n_faces, double threshold,
+                     int normal_iterations, int vertex_iterations, int boundary_mode, const uint8_t *fixed_dev, float *verts_out_dev,
+                     float *normals_out_dev, uint8_t *class_out_dev, int64_t *report_host, int device, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * "next" row: the pairs of faces of a handle's mesh that intersect, and its non-manifold vertices -- what

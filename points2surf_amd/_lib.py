@@ -168,6 +168,8 @@ PROTOTYPES = {
                                     ctypes.POINTER(c_int64), c_int, c_void_p]),
     'p2s_mesh_smooth': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p,
                                 c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p]),
+    'p2s_mesh_denoise': (c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.c_double, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p]),
 }
 
 

@@ -42,6 +42,8 @@
 // 10. p2s_meshcomponents.inl: connected components with their measures, the sub-mesh of a face mask
 // 11. p2s_meshmanifold.inl: faces removed at edges of more than two faces, non-manifold vertices split
 // 12. p2s_meshholes.inl: boundary loops closed by their minimum-area triangulation (one workgroup per loop, the table in LDS)
+// 13. p2s_meshsmooth.inl: vertices moved by the umbrella operator over a sorted CSR of the edge table
+// 14. p2s_meshdenoise.inl: face normals filtered over the faces that share a vertex, vertices moved toward them
 //
 // The pseudonormal sign holds for ONE closed surface that does not intersect itself.  A closed mesh of several connected
 // components may be a union of overlapping solids (the reference's 00011084 is: 170 of its 2,000 GT queries lie just outside
@@ -993,3 +995,5 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
 #include "p2s_meshholes.inl"
 // ---- 13. vertices moved by the umbrella operator: Taubin and Laplacian smoothing
 #include "p2s_meshsmooth.inl"
+// ---- 14. denoising that keeps sharp edges: face normals filtered, vertices moved toward them
+#include "p2s_meshdenoise.inl"

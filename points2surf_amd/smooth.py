@@ -3,8 +3,9 @@ with lambda and one with mu (Taubin 1995, "lambda | mu"; mu = 0 is plain Laplaci
 terraces of an iso-surface, and the "Taubin Smooth" step of the usual iso-surface -> clean -> smooth -> simplify sequence.  It
 runs in libp2s_hip.so (p2s_mesh_smooth); the definition is in include/p2s_hip.h.  This is the project's own definition -- not
 vcglib's and not MeshLab's filter.  Faces are not touched and vertices are connected by INDEX: run ``clean.repair`` first.
-The smoothed mesh is not tested for self-intersections (``gt_sdf.TriMesh.check`` finds them).  Nothing else in the package
-calls this.  Torch tensors are containers only; no CPU fallback.
+The smoothed mesh is not tested for self-intersections (``gt_sdf.TriMesh.check`` finds them).  The umbrella operator rounds
+every crease: the filter that keeps sharp edges is ``denoise``.  Nothing else in the package calls this.
+Torch tensors are containers only; no CPU fallback.
 
 The defaults (10 iterations, lambda 0.5, mu -0.53) are MeshLab's Taubin defaults.  Nobody has measured them on reconstructions
 of this project: they are a starting point, not a recommendation.
@@ -69,6 +70,18 @@ def _ptr(t):
     return _engine._ptr(t) if t is not None and t.numel() else None
 
 
+def _fixed_mask(fixed, V, dev):
+    """``fixed`` [V] (bool or integer, numpy array or tensor, may be None) as a uint8 device tensor of zeros and ones"""
+    if fixed is None:
+        return None
+    if isinstance(fixed, np.ndarray):
+        fixed = torch.from_numpy(np.ascontiguousarray(fixed != 0))
+    fx = (fixed.to(dev) != 0).to(torch.uint8).contiguous()
+    if tuple(fx.shape) != (V,):
+        raise ValueError('fixed must be [%d] (got %s)' % (V, tuple(fx.shape)))
+    return fx
+
+
 def smooth(verts, faces, iterations=10, lam=0.5, mu=-0.53, boundary='fixed', fixed=None, device=None, want_class=False):
     """``verts`` [V, 3] float32, ``faces`` [F, 3] int32 (numpy arrays or tensors) -> (verts_out, faces, report): the moved
     vertices as a new float32 device tensor, the faces as an int32 device tensor (untouched) and the report dict (REPORT_KEYS).
@@ -80,13 +93,7 @@ def smooth(verts, faces, iterations=10, lam=0.5, mu=-0.53, boundary='fixed', fix
     lib = _lib.load()
     v, f = _components._mesh(verts, faces, dev)
     V, F = int(v.shape[0]), int(f.shape[0])
-    fx = None
-    if fixed is not None:
-        if isinstance(fixed, np.ndarray):
-            fixed = torch.from_numpy(np.ascontiguousarray(fixed != 0))
-        fx = (fixed.to(dev) != 0).to(torch.uint8).contiguous()
-        if tuple(fx.shape) != (V,):
-            raise ValueError('fixed must be [%d] (got %s)' % (V, tuple(fx.shape)))
+    fx = _fixed_mask(fixed, V, dev)
     rep = (ctypes.c_int64 * 16)()
     with torch.cuda.device(dev):
         vo = torch.empty((V, 3), dtype=torch.float32, device=dev)
