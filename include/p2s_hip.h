@@ -860,6 +860,59 @@ int p2s_mesh_denoise(const float *verts_dev, int64_t n_verts, const int32_t *fac
                      float *normals_out_dev, uint8_t *class_out_dev, int64_t *report_host, int device, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A shaded picture of a handle's mesh: what the reference leaves to an external viewer behind
+ * source/figure/distance_vis.py.  The project's own definition.  Everything is float64 with contraction off and uses
+ * + - * / sqrt min max floor copysign and comparisons only, dot = (x x' + y y') + z z', sums of three terms left to right:
+ * equal inputs give equal bytes, and tests/figure_model.py restates it in numpy.  No floating-point atomic.
+ *  a. refusals, each P2S_EINVAL with a message and nothing written, in this order: m, prm or rgb_out_dev NULL; width or
+ *     height < 1; samples outside 1 .. 4; ao_rays outside 0 .. 64; ao_dirs_dev NULL with ao_rays > 0 (or not NULL with 0);
+ *     projection or shading outside 0 .. 1; width * height * samples^2 > 2^28; a camera vector, the extent of the projection
+ *     in use (which is also > 0), ao_radius, ao_bias, ambient, diffuse, base_rgb or background_rgb not finite (|x| > 1e300);
+ *     right, up, forward not orthonormal (a dot product more than 2^-40 from 1 or 0); ao_radius or ao_bias < 0; then, with
+ *     the handle's device current: vertex_rgb_dev, ao_dirs_dev or an output that is not memory of that device.
+ *  b. samples.  Pixel (i, j), i from the left and j from the top, has ss x ss samples (a, b), ss = samples:
+ *         sx = (2 (i + (a + 0.5) / ss)) / W - 1        sy = 1 - (2 (j + (b + 0.5) / ss)) / H
+ *     pinhole (projection 0):       o = eye,  d = (forward + (sx tan_half_w) right) + (sy tan_half_h) up   (not normalised: t
+ *                                   is in units of d, as in p2s_mesh_raycast)
+ *     orthographic (projection 1):  o = (eye + (sx half_w) right) + (sy half_h) up,  d = forward
+ *     The sample image has W ss columns and H ss rows; sample (X, Y) = (i ss + a, j ss + b) is entry Y (W ss) + X.
+ *  c. the primary hit is p2s_mesh_raycast's of that ray with t_max = +inf, every rule of that section included:
+ *     depth_out_dev and face_out_dev [H ss][W ss] (each may be NULL) equal what it returns, bit for bit; a miss is +inf, -1.
+ *  d. shading of a hit on face f with the corners A, B, C in the order the handle stores them (an inward-oriented closed mesh
+ *     is stored flipped: B and C swapped): e1 = B - A, e2 = C - A, nf = e1 x e2, s = o - A, q = s x d, dn = d . nf,
+ *     u = -(e2 . q) / dn, v = (e1 . q) / dn, w = (1 - u) - v.  Normal: the stored unit normal of f; with shading 1 and no
+ *     corner flagged as touching a sliver or zero-area face, m = (w N_A + u N_B) + v N_C per coordinate with N the handle's
+ *     angle-weighted vertex normal (fixed point / 2^40, exact), and n = m / sqrt(m . m) unless m . m is 0 or not finite.
+ *     dl = d / sqrt(d . d), c = n . dl; if c > 0 both n and c change sign; lambert = -c (a two-sided headlight).
+ *     Albedo: base_rgb, or with vertex_rgb_dev [V][3] float (V the handle's vertices; the values are not checked) per
+ *     channel (w C_A + u C_B) + v C_C.
+ *  e. ambient occlusion, ao_rays = K > 0: sg = copysign(1, nz), a = -1 / (sg + nz), b = (nx ny) a,
+ *     t1 = (1 + ((sg nx) nx) a, sg b, -(sg nx)), t2 = (b, sg + (ny ny) a, -ny) (Duff et al., JCGT 2017); for every row h of
+ *     ao_dirs_dev [K][3] float64 (unit, z >= 0; not checked: a non-finite row is never occluded)
+ *     dir = (hx t1 + hy t2) + hz n per coordinate, from p = (o + t d) + ao_bias n; the ray is occluded iff any face is hit
+ *     with t in (0, ao_radius] under the acceptance rules of c (ao_radius 0: none is).  ao = (K - occluded) / K; 1 if K = 0.
+ *  f. sample colour per channel = min(max(albedo (ambient ao + diffuse lambert), 0), 1) (a NaN gives 0); a miss gives
+ *     background_rgb clamped likewise.  Pixel = (the sum of its samples from 0.0, b outer and a inner) / ss^2;
+ *     byte = floor(255 sqrt(x) + 0.5): gamma 2, because sqrt is correctly rounded everywhere.  rgb_out_dev [H][W][3].
+ *  g. stats_host [8] (may be NULL): primary rays, primary hits, occlusion rays, occlusion rays occluded, ray-triangle tests
+ *     (both walks), 0, 0, 0.  A traversal stack overflow (impossible for an index of at most 7 levels) fails the call with
+ *     P2S_EHIP as in p2s_mesh_raycast.
+ * Limits: one headlight; no shadow but the occlusion term; no texture; no transparency; the regular sample grid aliases on
+ * features thinner than a sample.  Scratch (84 bytes per sample) comes from the device's block cache.  Synchronises `stream`. */
+typedef struct {
+    int32_t width, height, samples;       /* W, H, ss per axis (1 .. 4) */
+    int32_t projection, shading;          /* 0 pinhole, 1 orthographic; 0 flat, 1 smooth */
+    int32_t ao_rays;                      /* K, 0 .. 64 */
+    double  eye[3], right[3], up[3], forward[3];
+    double  tan_half_w, tan_half_h;       /* pinhole */
+    double  half_w, half_h;               /* orthographic */
+    double  ao_radius, ao_bias, ambient, diffuse;
+    double  base_rgb[3], background_rgb[3];
+} p2s_render_params;
+int p2s_mesh_render(p2s_trimesh_t m, const p2s_render_params *prm, const float *vertex_rgb_dev, const double *ao_dirs_dev,
+                    uint8_t *rgb_out_dev, double *depth_out_dev, int32_t *face_out_dev, int64_t *stats_host, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * "next" row: the pairs of faces of a handle's mesh that intersect, and its non-manifold vertices -- what
  * the verdict "a volume" of p2s_mesh_repair (trimesh's is_volume) does not see, and what the pseudonormal sign of
  * p2s_mesh_distance assumes absent.  The project's own definition (trimesh offers none); every result is a function of

@@ -170,6 +170,7 @@ PROTOTYPES = {
                                 c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p]),
     'p2s_mesh_denoise': (c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.c_double, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, ctypes.POINTER(c_int64), c_int, c_void_p]),
+    'p2s_mesh_render': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
 }
 
 
@@ -177,6 +178,16 @@ class TofSensor(ctypes.Structure):
     """mirror of ``p2s_tof_sensor``"""
     _fields_ = [('width', ctypes.c_int32), ('height', ctypes.c_int32), ('tan_half_w', ctypes.c_double),
                 ('tan_half_h', ctypes.c_double), ('max_distance', ctypes.c_double)]
+
+
+class RenderParams(ctypes.Structure):
+    """mirror of ``p2s_render_params``"""
+    _fields_ = [('width', ctypes.c_int32), ('height', ctypes.c_int32), ('samples', ctypes.c_int32), ('projection', ctypes.c_int32),
+                ('shading', ctypes.c_int32), ('ao_rays', ctypes.c_int32), ('eye', ctypes.c_double * 3), ('right', ctypes.c_double * 3),
+                ('up', ctypes.c_double * 3), ('forward', ctypes.c_double * 3), ('tan_half_w', ctypes.c_double),
+                ('tan_half_h', ctypes.c_double), ('half_w', ctypes.c_double), ('half_h', ctypes.c_double), ('ao_radius', ctypes.c_double),
+                ('ao_bias', ctypes.c_double), ('ambient', ctypes.c_double), ('diffuse', ctypes.c_double),
+                ('base_rgb', ctypes.c_double * 3), ('background_rgb', ctypes.c_double * 3)]
 
 
 class WorkerStreams(ctypes.Structure):

@@ -44,6 +44,7 @@
 // 12. p2s_meshholes.inl: boundary loops closed by their minimum-area triangulation (one workgroup per loop, the table in LDS)
 // 13. p2s_meshsmooth.inl: vertices moved by the umbrella operator over a sorted CSR of the edge table
 // 14. p2s_meshdenoise.inl: face normals filtered over the faces that share a vertex, vertices moved toward them
+// 15. p2s_meshrender.inl: shaded pictures of the handle's mesh -- the first-hit walk over camera rays, any-hit occlusion rays
 //
 // The pseudonormal sign holds for ONE closed surface that does not intersect itself.  A closed mesh of several connected
 // components may be a union of overlapping solids (the reference's 00011084 is: 170 of its 2,000 GT queries lie just outside
@@ -997,3 +998,5 @@ extern "C" int p2s_mesh_winding(p2s_trimesh_t m, const float *query_dev, int64_t
 #include "p2s_meshsmooth.inl"
 // ---- 14. denoising that keeps sharp edges: face normals filtered, vertices moved toward them
 #include "p2s_meshdenoise.inl"
+// ---- 15. shaded pictures: primary rays through the first-hit walk, shading and any-hit occlusion rays, the resolve
+#include "p2s_meshrender.inl"
