@@ -40,6 +40,7 @@ namespace {
 #include "p2s_devprim.inl"          // f2o / o2f
 
 constexpr int PS_MIN_DEPTH = 3, PS_MAX_DEPTH = 9;
+// PS_TX / PS_TY / PS_TZ, PS_MAX_PART and PS_CHECK_EVERY are mirrored at the top of tests/test_gpu_poisson.py: change both
 constexpr int PS_TX = 8, PS_TY = 8, PS_TZ = 32;                  // stencil tile: axis 0, 1, 2 (axis 2 fastest)
 constexpr int PS_LY = PS_TY + 2, PS_LZ = PS_TZ + 2, PS_LX = PS_TX + 2;
 constexpr int PS_MAX_PART = 1024;                                // partial sums per reduction

@@ -1,7 +1,9 @@
 """float64 restatement of the Screened Poisson baseline (include/p2s_hip.h) with scipy.sparse: the box,
 the levels, W, the 1-D matrices, A and b as Kronecker products, the cascade solved to 1e-12, iso, the volume with its
 border rule.  The yardstick of points2surf_amd/csrc/p2s_poisson.hip; also the sums over absolute values that bound the
-rounding of the device's float32 pieces."""
+rounding of the device's float32 pieces.  Level (sparse, Kronecker products) is the definition; FreeLevel applies the same
+operators separably, for the depths at which the products are out of reach; one_step_cascade is the cascade cut after one CG
+step per level, in float64 and with the device's float32 stores."""
 import numpy as np
 import scipy.sparse as sp
 import scipy.sparse.linalg as spl
@@ -111,6 +113,150 @@ class Level:
         """the sum over the absolute values of the terms of A x"""
         ax = np.abs(np.asarray(x, np.float64).reshape(-1))
         return self.A0_abs @ ax + self.lam * (self.WtW @ ax)
+
+
+def _f32(x):
+    """rounded to float32, held as float64"""
+    return np.asarray(x, np.float64).astype(np.float32).astype(np.float64)
+
+
+def _same(x):
+    return x
+
+
+def tri_1d(R, h, rnd=_same):
+    """the 1-D matrices as (diagonal [R], the coefficient of x[i - 1], the coefficient of x[i + 1]): m, s, g"""
+    def ends(inside, end):
+        d = np.full(R, rnd(inside))
+        d[0] = d[-1] = rnd(end)
+        return d
+    gd = np.zeros(R)
+    gd[0], gd[-1] = -0.5, 0.5
+    return ((ends(2.0 * h / 3.0, h / 3.0), rnd(h / 6.0), rnd(h / 6.0)), (ends(2.0 / h, 1.0 / h), rnd(-1.0 / h), rnd(-1.0 / h)),
+            (gd, 0.5, -0.5))
+
+
+def tri_abs(t):
+    return np.abs(t[0]), abs(t[1]), abs(t[2])
+
+
+def tri_apply(t, x, axis):
+    """a tridiagonal 1-D matrix along one axis of a [R, R, R] array, by slicing"""
+    d, below, above = t
+    x = np.moveaxis(x, axis, 0)
+    y = d[:, None, None] * x
+    y[1:] += below * x[:-1]
+    y[:-1] += above * x[1:]
+    return np.moveaxis(y, 0, axis)
+
+
+class FreeLevel:
+    """Level without a Kronecker product: the same fields and methods (no A, A0, WtW), the 1-D matrices applied along one
+    axis at a time, the screen term as lam W^T (W x).  dtype=np.float32 rounds what the device holds in float32 -- the 1-D
+    coefficients, the weights, v, b, diag, u = W x and the result of apply -- to float32 after it is formed in float64: the
+    device's stores, not its order of operations.  W64 keeps the float64 weights (the device's iso uses those)."""
+
+    def __init__(self, points, normals, depth, point_weight=4.0, scale=1.1, dtype=np.float64):
+        rnd = self.rnd = _f32 if dtype == np.float32 else _same
+        lo, side = box(points, scale)
+        self.lo, self.R, self.h = lo, 2 ** depth + 1, side / 2 ** depth
+        R, h = self.R, self.h
+        nrm = np.asarray(normals, np.float32).astype(np.float64)
+        n = nrm.shape[0]
+        self.W64, cell = weights(points, lo, h, R)
+        self.W = self.W64.copy()
+        self.W.data = rnd(self.W.data)
+        self.Wt = self.W.T.tocsr()
+        self.n_occ = int(np.unique(cell).size)
+        self.a = self.n_occ * h * h / n
+        self.lam = point_weight * self.a / h
+        self.m, self.s, self.g = tri_1d(R, h, rnd)
+        self.v = rnd((self.a / h ** 3) * (self.Wt @ (-nrm)))
+        self.v_abs = (self.a / h ** 3) * (self.Wt @ np.abs(nrm))
+        self.b = rnd(self._rhs(self.v, self.m, self.g))
+        self.b_abs = self._rhs(self.v_abs, tri_abs(self.m), tri_abs(self.g))
+        dm, ds = self.m[0], self.s[0]
+        outer = lambda p, q, r: p[:, None, None] * q[None, :, None] * r[None, None, :]
+        stencil = rnd(outer(ds, dm, dm) + outer(dm, ds, dm) + outer(dm, dm, ds)).reshape(-1)
+        self.diag = rnd(stencil + self.lam * np.asarray(self.W.power(2).sum(axis=0)).reshape(-1))
+
+    def _rhs(self, v, m, g):
+        R = self.R
+        vx, vy, vz = (v[:, a].reshape(R, R, R) for a in range(3))
+        return (tri_apply(g, tri_apply(m, tri_apply(m, vx, 2), 1), 0) + tri_apply(m, tri_apply(g, tri_apply(m, vy, 2), 1), 0) +
+                tri_apply(m, tri_apply(m, tri_apply(g, vz, 2), 1), 0)).reshape(-1)
+
+    def _stencil(self, x, m, s):
+        x = x.reshape(self.R, self.R, self.R)
+        mz, sz = tri_apply(m, x, 2), tri_apply(s, x, 2)
+        return (tri_apply(s, tri_apply(m, mz, 1), 0) + tri_apply(m, tri_apply(s, mz, 1) + tri_apply(m, sz, 1), 0)).reshape(-1)
+
+    def apply(self, x):
+        x = np.asarray(x, np.float64).reshape(-1)
+        return self.rnd(self._stencil(x, self.m, self.s) + self.lam * (self.Wt @ self.rnd(self.W @ x)))
+
+    def apply_abs(self, x):
+        """the sum over the absolute values of the terms of A x"""
+        ax = np.abs(np.asarray(x, np.float64).reshape(-1))
+        return self._stencil(ax, tri_abs(self.m), tri_abs(self.s)) + self.lam * (self.Wt @ (self.W @ ax))
+
+
+def prolong(xc, Rc, odd_weight=0.5):
+    """prolong_matrix(Rc) @ xc without the matrix.  odd_weight is the weight of each of the two coarse neighbours of an odd
+    node along one axis: 0.5 is the definition, another value is a deliberately wrong prolongation for checking that a
+    test would notice one."""
+    x = np.asarray(xc, np.float64).reshape(Rc, Rc, Rc)
+    for axis in range(3):
+        x = np.moveaxis(x, axis, 0)
+        y = np.empty((2 * x.shape[0] - 1,) + x.shape[1:])
+        y[0::2] = x
+        y[1::2] = odd_weight * (x[:-1] + x[1:])
+        x = np.moveaxis(y, 0, axis)
+    return x.reshape(-1)
+
+
+def one_step_cascade(points, normals, depth, dtype=np.float64, point_weight=4.0, scale=1.1, odd_weight=0.5):
+    """(x of the finest level, its FreeLevel): per level 3 .. depth exactly one Jacobi-preconditioned CG step from x0 = 0 or
+    the prolongation of the level below: r = b - A x0, z = r / diag, alpha = r.z / z.A z, x = x0 + alpha z.
+    dtype=np.float64 is the yardstick; dtype=np.float32 rounds every stored vector (x, r, p = z, A p, u), alpha and what
+    FreeLevel rounds to float32 after each step; the dot products stay float64, as on the device."""
+    rnd = _f32 if dtype == np.float32 else _same
+    x, lev = None, None
+    for d in range(MIN_DEPTH, depth + 1):
+        lev = FreeLevel(points, normals, d, point_weight, scale, dtype)
+        x0 = np.zeros(lev.R ** 3) if x is None else rnd(prolong(x, (lev.R + 1) // 2, odd_weight))
+        r = rnd(lev.b - lev.apply(x0))
+        p = rnd(r / lev.diag)
+        ap = lev.apply(p)
+        alpha = rnd(np.dot(r, p) / np.dot(p, ap))
+        x = rnd(x0 + alpha * p)
+    return x, lev
+
+
+def piece_cases():
+    """name -> (points, normals, scale): the inputs of the node-by-node comparisons of one level"""
+    rng = np.random.default_rng(5)
+    unit = np.array([[0.0, 0.6, 0.8]], np.float32)
+    corners = np.array([[0, 0, 0], [1, 1, 1]], np.float32)
+    out = {}
+    # one point inside a cell; two points without normals span the box
+    out['inside'] = (np.concatenate([np.array([[0.30, 0.41, 0.52]], np.float32), corners]),
+                     np.concatenate([unit, np.zeros((2, 3), np.float32)]), 1.1)
+    # one point exactly on a node of both depths; scale 1.0 puts the corner points on the last node (the clamp, t = 1)
+    out['on_node_scale1'] = (np.concatenate([np.array([[0.5, 0.25, 0.75]], np.float32), corners]),
+                             np.concatenate([unit, np.array([[1, 0, 0], [0, -2, 0.5]], np.float32)]), 1.0)
+    # 300 identical points in one cell and 5 elsewhere: the ends of the cell sort's segments
+    few = rng.random((5, 3)).astype(np.float32)
+    out['dense_cell'] = (np.concatenate([np.repeat(np.array([[0.61, 0.33, 0.47]], np.float32), 300, 0), few, corners]),
+                         np.concatenate([np.repeat(unit, 300, 0), rng.standard_normal((5, 3)).astype(np.float32),
+                                         np.zeros((2, 3), np.float32)]), 1.1)
+    out['sphere'] = sphere(2000, 3) + (1.1,)
+    # normals of length 0 for half of the points; scale 1.0: the extreme points of a real cloud on the last node
+    pts, nrm = sphere(2000, 4)
+    nrm = nrm.copy()
+    nrm[::2] = 0.0
+    out['half_zero_scale1'] = (pts, nrm, 1.0)
+    return out
 
 
 def prolong_matrix(Rc):
